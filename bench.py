@@ -12,8 +12,14 @@ src/taylor_adaptive_batch.cpp:1417) / wall time, aggregated over all ranks (weak
 integrates `--systems` independent ICs, different seeds; the only collective on the path is the
 final all_gather of the states, the `ensemble_propagate_*` contract).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set-up, W warmup steps, K timed steps, the outputs of
+the last timed step (--dump-outputs) and the one result line. --full adds the legs which measure something else: the
+other workloads of the default line (two-body, N = 64, the general-DAG paths, divergent step counts, events, the long
+horizon) and the CPU baselines.
 """
 import argparse
 import json
@@ -77,6 +83,9 @@ DEFAULT_SYSTEMS = {"outer_ss": 1048576, "two_body": 4194304, "nbody64": 65536, "
                    "sine_lattice16_mixed": 262144}
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 FP64_PEAK_TFLOPS = 78.6  # vector FP64
+# Bound on what --dump-outputs writes (larger ensembles are sampled) and the seed of the sample.
+DUMP_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 20240601
 
 
 def make_integrator(hy, configs, workload, n_systems, seed, device=0):
@@ -356,9 +365,33 @@ def measure_traffic(workload, n):
     return traffic / steps_per_launch, "same-run rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of this command (2 x FETCH + WRITE)"
 
 
-def run_workload(ctx, workload, n, steps, warmup):
+def dump_sample(n, bytes_per_system, budget=DUMP_BYTES):
+    """Indices of the systems whose outputs --dump-outputs writes: all of them if they fit in the budget, else a fixed,
+    seeded sample (sorted), so that two runs with the same arguments write the same systems."""
+    k = max(1, min(n, budget // bytes_per_system))
+    if k == n:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(ta, out_dir):
+    """What a caller of the timed propagate_until() holds after the last timed step, as float64 .npy files under out_dir:
+    the state (dim, k), the double-length time (time_hi, time_lo) and the per-system result of the call (outcome, min_h,
+    max_h, n_steps), for the systems listed in sample_index.npy (see dump_sample())."""
+    # (dim rows of state + 2 time words + 4 result words + the index, 8 bytes each.)
+    idx = dump_sample(ta.batch_size, (ta.dim + 7) * 8)
+    hi, lo = ta.dtime
+    oc, mn, mx, ns = ta.propagate_res_arrays()
+    arrays = {"state": ta.state[:, idx], "time_hi": hi[idx], "time_lo": lo[idx], "outcome": oc[idx], "min_h": mn[idx],
+              "max_h": mx[idx], "n_steps": ns[idx], "sample_index": idx}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def run_workload(ctx, workload, n, steps, warmup, dump_dir=None):
     """One timed leg: `warmup` untimed + `steps` timed propagate_until() calls over n systems per GPU. Returns the bench
-    line of the leg on rank 0 (None elsewhere)."""
+    line of the leg on rank 0 (None elsewhere); with dump_dir, rank 0 writes the outputs of its last timed call there."""
     torch, hy, configs, hens, dist = ctx["torch"], ctx["hy"], ctx["configs"], ctx["hens"], ctx["dist"]
     rank, world, distributed, dev, dev_index = ctx["rank"], ctx["world"], ctx["distributed"], ctx["dev"], ctx["dev_index"]
     out = None
@@ -466,6 +499,8 @@ def run_workload(ctx, workload, n, steps, warmup):
     if rank == 0:
         from heyoka_amd import codegen_check, roofline
 
+        if dump_dir is not None:
+            dump_outputs(ta, dump_dir)
         n_eq, n_u = ta.dim, ta.n_uvars
         f_alg, b_tape = roofline.counts_for(ta)
         f_survey = WORKLOADS[workload]
@@ -587,8 +622,10 @@ def run_workload(ctx, workload, n, steps, warmup):
                 "algorithmic_flop_per_system_step": f_alg,
                 "algorithmic_bytes_per_system_step": b_tape,
                 # Launch by launch: adaptive step counts make the launches differ (and, for one system per workgroup,
-                # the launch cannot end before its slowest system: see steps_per_system_last_launch).
-                "per_launch": [{"kernel_ms": float(k), "system_steps": float(s_)} for k, s_ in zip(kern_ms, steps_per_call_all)],
+                # the launch cannot end before its slowest system: see steps_per_system_last_launch). --full only: the
+                # list grows with --steps, and the line of a plain run stays short whatever the number of steps.
+                "per_launch": ([{"kernel_ms": float(k), "system_steps": float(s_)} for k, s_ in zip(kern_ms, steps_per_call_all)]
+                               if ctx.get("full") else None),
                 "steps_per_system_last_launch": {"mean": float(ns.mean()), "max": int(ns.max()), "min": int(ns.min()),
                                                  "p99": float(np.percentile(ns, 99))},
                 "algorithmic_counts_source": "heyoka_amd/roofline.py on the decomposition of this integrator "
@@ -811,9 +848,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--systems", type=int, default=0, help="systems per GPU (default: the BASELINE.json size)")
     ap.add_argument("--workload", default="outer_ss", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the extra workloads (outer Solar System at N = 1) and the "
+                    "CPU baselines, and list the launches one by one in the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (state, time, per-system results; a fixed sample of at "
+                    "most 48 MiB) as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="skip the short two-body / N = 64 legs which follow the outer-Solar-System measurement at N = 1")
+                    help="with --full: skip the legs which follow the outer-Solar-System measurement at N = 1")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-long-horizon", action="store_true", help="skip the long-horizon leg of the extra workloads (~30 s)")
     ap.add_argument("--long-horizon-years", type=float, default=1.0e4)
@@ -826,6 +869,8 @@ def main():
     ap.add_argument("--single-device", action="store_true",
                     help="debug: all ranks share GPU 0 (use with --backend gloo to exercise the N > 1 path on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -869,12 +914,13 @@ def main():
 
     ctx = dict(torch=torch, hy=hy, configs=configs, hens=hens, dist=(dist if distributed else None), rank=rank, world=world,
                distributed=distributed, dev=dev, dev_index=dev_index, backend=args.backend,
-               collective_timeout=args.collective_timeout, measure_traffic=bool(args.measure_traffic) and world == 1)
+               collective_timeout=args.collective_timeout, measure_traffic=bool(args.measure_traffic) and world == 1,
+               full=args.full)
     n = args.systems if args.systems > 0 else DEFAULT_SYSTEMS[args.workload]
-    out = run_workload(ctx, args.workload, n, args.steps, args.warmup)
+    out = run_workload(ctx, args.workload, n, args.steps, args.warmup, dump_dir=args.dump_outputs)
     gather_failed = bool(out.pop("_gather_failed", False)) if out is not None else False
     if rank == 0:
-        if world == 1 and not args.no_extra_workloads and args.workload == "outer_ss":
+        if args.full and world == 1 and not args.no_extra_workloads and args.workload == "outer_ss":
             # The other two single-GPU measurement points of BASELINE.json (configs 3 and 5) as short legs of the same run,
             # each with its own roofline: the two-body problem (small DAG, jets in registers: FP64-bound) and
             # model::nbody(64) (block mode, jets on a tape: HBM-bound, counter traffic when a matching summary is
@@ -920,7 +966,7 @@ def main():
                 except Exception as e:
                     extra.append({"config": {"workload": "outer_ss_long_horizon"}, "error": "%s: %s" % (type(e).__name__, e)})
             out["extra_workloads"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, out.pop("_dt"), args.cpu_seconds)
         out.pop("_dt", None)
         print(json.dumps(out))
