@@ -65,6 +65,11 @@ struct grid_kargs {
     double *acc_max_h;
     // (... and whether the lane's last step was clamped to its remaining time: hy_kargs::grid_done.)
     const double *grid_done;
+    // (... and the stepper's count of systems which went non-finite in the launch, hy_kargs::counters[0]; nonzero with the
+    // reference's semantics: the launch is rolled back, nothing is recorded - counters[3] = 1 tells the host. Null: no check.)
+    const unsigned *launch_nf;
+    // (The grid index of every lane before this sweep's samples: hy_grid_unsample takes them back. Null: not kept.)
+    unsigned *gidx_prev;
 };
 
 // Code generator from the configuration field (0 automatic: the wave-cluster generator is tried first and falls back
@@ -1145,7 +1150,11 @@ const std::vector<double> &tab_core::update_d_output(const std::vector<double> &
     d.check_tc_not_stale();
     std::vector<double> hs(d.N);
     if (rel_time) {
-        hs = t;
+        // Relative to the CURRENT time, i.e. to the end of the last step: h' = last_h + t (:2276-2280).
+        const auto &lh = get_last_h();
+        for (std::uint32_t i = 0; i < d.N; ++i) {
+            hs[i] = lh[i] + t[i];
+        }
     } else {
         d.times_to_host();
         const auto &lh = get_last_h();
@@ -2181,7 +2190,8 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
                                d.d_tlo.as<double>(), d.d_lasth.as<double>(), d.d_outcome.as<long long>(),
                                b_rem_hi.as<double>(), b_rem_lo.as<double>(), b_mdt.as<double>(), b_tdir.as<int>(),
                                d.d_lim.as<double>(), nullptr, d.d_minh.as<double>(), d.d_maxh.as<double>(),
-                               d.d_nsteps.as<unsigned long long>(), b_cnt.as<unsigned>(), N, 0u, nullptr, nullptr, nullptr, nullptr, nullptr};
+                               d.d_nsteps.as<unsigned long long>(), b_cnt.as<unsigned>(), N, 0u, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               nullptr, nullptr};
             d.grid_mod->launch("hy_until_post", N, 256, &a, sizeof(a), d.stream);
             unsigned cnt[3] = {0, 0, 0};
             b_cnt.download(cnt, sizeof(cnt), d.stream);
@@ -2275,6 +2285,8 @@ struct hy_grid_args {
     double *acc_min_h;
     double *acc_max_h;
     const double *grid_done;
+    const unsigned *launch_nf;
+    unsigned *gidx_prev;
 };
 
 // Post-step kernel of the device-driven propagate_until() lock-step loop (callbacks / continuous output): the
@@ -2331,9 +2343,20 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
     const u64 N = a.N;
     if (i >= N) return;
+    if (a.launch_nf != nullptr && *a.launch_nf != 0u) {
+        if (i == 0u) a.counters[3] = 1u;
+        return;
+    }
+    if (a.gidx_prev != nullptr) a.gidx_prev[i] = a.gidx[i];
     const i64 oc = a.outcome[i];
     const double h = a.last_h[i];
     if (oc == HY_OC_ERR_NF_STATE) {
+        // (A launch of several steps per lane - per-lane semantics: the steps before the non-finite one count.)
+        if (a.acc_n_steps != nullptr) {
+            a.acc_n_steps[i] += a.n_steps[i];
+            a.acc_min_h[i] = hy_min(a.acc_min_h[i], a.min_h[i]);
+            a.acc_max_h[i] = hy_max(a.acc_max_h[i], a.max_h[i]);
+        }
         hy_count(a.counters + 1, true);
         return;
     }
@@ -2412,6 +2435,22 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
     a.lim[i] = lim;
     hy_count(a.counters, g < ng);
 }
+
+// A sweep in which a lane went non-finite: the reference leaves its loop right after that step, before the dense output of
+// the step (src/taylor_adaptive_batch.cpp:1962-1968; the samples of a step are taken at the top of the NEXT iteration,
+// :1800-1871) - the samples hy_grid_post has just taken in the other lanes are NaN again.
+extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (i >= N) return;
+    const unsigned g1 = a.gidx[i];
+    for (unsigned g = a.gidx_prev[i]; g < g1; ++g) {
+        for (unsigned v = 0; v < HY_DIM; ++v) {
+            a.out[((u64)g * HY_DIM + v) * N + i] = __builtin_nan("");
+        }
+    }
+}
 )HIP";
     return src.str();
 }
@@ -2439,18 +2478,10 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     device_buffer b_grid(grid.size() * dsz, d.device), b_out(d_out != nullptr ? 0u : out_doubles * dsz, d.device);
     double *const out_ptr = d_out != nullptr ? d_out : b_out.as<double>();
     device_buffer b_rem_hi(N * dsz, d.device), b_rem_lo(N * dsz, d.device), b_mdt(N * dsz, d.device);
-    device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(4u * sizeof(unsigned), d.device);
+    device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(4u * sizeof(unsigned), d.device),
+        b_gidx_prev(N * sizeof(unsigned), d.device);
     b_grid.upload(grid.data(), grid.size() * dsz, d.stream);
-    // Row 0 = current state, everything else NaN until reached.
-    if (d_out == nullptr) {
-        b_out.upload(retval.data(), retval.size() * dsz, d.stream);
-    } else {
-        // NOTE: the all-ones byte pattern is a (quiet) NaN.
-        device_fill_bytes(out_ptr, 0xFF, out_doubles * dsz, d.device, d.stream);
-        d.to_device();
-        device_copy(out_ptr, d.d_state.get(), static_cast<std::size_t>(dim) * N * dsz, d.device, d.stream);
-    }
-    std::vector<double> rhi(N), rlo(N), lim(N), mn(N, pinf), mx(N, 0.);
+    std::vector<double> rhi(N), rlo(N), lim(N), mn(N, pinf), mx(N, 0.), tg(N);
     std::vector<unsigned> gidx(N, 1u);
     std::vector<unsigned long long> ns(N, 0u);
     for (std::uint32_t i = 0; i < N; ++i) {
@@ -2459,17 +2490,33 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         const auto dt_limit
             = t_dir[i] != 0 ? std::min(dfloat(max_delta_ts[i]), rem[i]) : std::max(dfloat(-max_delta_ts[i]), rem[i]);
         lim[i] = static_cast<double>(dt_limit);
+        tg[i] = n_grid > 1u ? grid[static_cast<std::size_t>(N) + i] : 0.;
     }
-    b_rem_hi.upload(rhi.data(), N * dsz, d.stream);
-    b_rem_lo.upload(rlo.data(), N * dsz, d.stream);
     b_mdt.upload(max_delta_ts.data(), N * dsz, d.stream);
     b_tdir.upload(t_dir.data(), N * sizeof(int), d.stream);
-    b_gidx.upload(gidx.data(), N * sizeof(unsigned), d.stream);
-    d.d_lim.upload(lim.data(), N * dsz, d.stream);
-    d.d_lim_src = nullptr;
-    d.d_minh.upload(mn.data(), N * dsz, d.stream);
-    d.d_maxh.upload(mx.data(), N * dsz, d.stream);
-    d.d_nsteps.upload(ns.data(), N * sizeof(unsigned long long), d.stream);
+    device_buffer b_next_tg(N * dsz, d.device);
+    // The samples and the per-lane bookkeeping at the first grid point: at the start, and again after a rollback (below).
+    const auto init_grid_state = [&]() {
+        // Row 0 = current state, everything else NaN until reached.
+        if (d_out == nullptr) {
+            b_out.upload(retval.data(), retval.size() * dsz, d.stream);
+        } else {
+            // NOTE: the all-ones byte pattern is a (quiet) NaN.
+            device_fill_bytes(out_ptr, 0xFF, out_doubles * dsz, d.device, d.stream);
+            d.to_device();
+            device_copy(out_ptr, d.d_state.get(), static_cast<std::size_t>(dim) * N * dsz, d.device, d.stream);
+        }
+        b_rem_hi.upload(rhi.data(), N * dsz, d.stream);
+        b_rem_lo.upload(rlo.data(), N * dsz, d.stream);
+        b_gidx.upload(gidx.data(), N * sizeof(unsigned), d.stream);
+        d.d_lim.upload(lim.data(), N * dsz, d.stream);
+        d.d_lim_src = nullptr;
+        d.d_minh.upload(mn.data(), N * dsz, d.stream);
+        d.d_maxh.upload(mx.data(), N * dsz, d.stream);
+        d.d_nsteps.upload(ns.data(), N * sizeof(unsigned long long), d.stream);
+        b_next_tg.upload(tg.data(), N * dsz, d.stream);
+    };
+    init_grid_state();
 
     d.prop_res_override.reset();
     d.fix_step_limit = false;
@@ -2485,7 +2532,15 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     // it stores; hy_grid_post then evaluates the dense output of that step. A launch per grid interval instead of a launch
     // per step: the lock-step loop was at 0.7 of the rate of the propagation loop (ramp-up / drain and clock of 2-ms
     // launches). max_steps counts lock-step iterations of the batch: with a step limit the single-step sweeps stay.
-    const bool multi_step = tc_on_demand && d.emitted.grid_multi_step && max_steps == 0u && d.batch_semantics != 1;
+    // With the reference's semantics (batch_semantics == 0) a lane which goes non-finite stops the whole batch after THAT
+    // sweep (src/taylor_adaptive_batch.cpp:1936-2000), i.e. after the same number of steps in every lane. The launches
+    // take every lane to its own grid crossing - after a few launches the lanes have taken different numbers of steps -, so
+    // a launch in which a lane goes non-finite sends the whole call back to the snapshot taken before the FIRST launch
+    // (state, times; samples and per-lane bookkeeping from the host; hy_grid_post records nothing of that launch), and the
+    // grid is redone from its start in single-step sweeps. batch_semantics == 2 keeps the per-lane behaviour.
+    bool multi_step = tc_on_demand && d.emitted.grid_multi_step && max_steps == 0u && d.batch_semantics != 1;
+    const bool multi_step_chosen = multi_step;
+    std::size_t n_launches = 0, n_rollbacks = 0;
     device_buffer b_acc_ns(multi_step ? N * sizeof(unsigned long long) : 0u, d.device), b_acc_min(multi_step ? N * dsz : 0u, d.device),
         b_acc_max(multi_step ? N * dsz : 0u, d.device), b_grid_done(multi_step ? N * dsz : 0u, d.device);
     if (multi_step) {
@@ -2498,14 +2553,12 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         b_acc_ns.upload(ns.data(), N * sizeof(unsigned long long), d.stream);
         b_acc_min.upload(mn.data(), N * dsz, d.stream);
         b_acc_max.upload(mx.data(), N * dsz, d.stream);
-    }
-    device_buffer b_next_tg(tc_on_demand ? N * dsz : 0u, d.device);
-    if (tc_on_demand) {
-        std::vector<double> tg(N);
-        for (std::uint32_t i = 0; i < N; ++i) {
-            tg[i] = grid[static_cast<std::size_t>(N) + i];
+        if (d.batch_semantics == 0) {
+            d.before_kernel();
+            d.snapshot_for_rollback();
         }
-        b_next_tg.upload(tg.data(), N * dsz, d.stream);
+    }
+    if (tc_on_demand) {
         d.tc_threshold = b_next_tg.as<double>();
     }
     const struct thr_reset {
@@ -2552,6 +2605,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         } else {
             d.run_step_impl(nullptr, true);
         }
+        ++n_launches;
         any_step = true;
         d.ensure_tc_expanded();
         b_cnt.zero(d.stream);
@@ -2562,11 +2616,28 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                            d.d_nsteps.as<unsigned long long>(), b_cnt.as<unsigned>(), N, n_grid,
                            tc_on_demand ? b_next_tg.as<double>() : nullptr,
                            multi_step ? b_acc_ns.as<unsigned long long>() : nullptr, multi_step ? b_acc_min.as<double>() : nullptr,
-                           multi_step ? b_acc_max.as<double>() : nullptr, multi_step ? b_grid_done.as<double>() : nullptr};
+                           multi_step ? b_acc_max.as<double>() : nullptr, multi_step ? b_grid_done.as<double>() : nullptr,
+                           (multi_step && d.batch_semantics == 0) ? d.d_counters.as<unsigned>() : nullptr,
+                           b_gidx_prev.as<unsigned>()};
         d.grid_mod->launch("hy_grid_post", N, 256, &a, sizeof(a), d.stream);
-        unsigned cnt[3] = {0, 0, 0};
+        unsigned cnt[4] = {0, 0, 0, 0};
         b_cnt.download(cnt, sizeof(cnt), d.stream);
+        if (cnt[3] != 0u) {
+            // A lane went non-finite inside a multi-step launch: back to the start of the grid, and all of it again in
+            // single-step sweeps.
+            d.rollback_to_snapshot();
+            init_grid_state();
+            iter_counter = 0;
+            multi_step = false;
+            ++n_rollbacks;
+            continue;
+        }
         if (cnt[1] != 0u) {
+            // (Lock-step sweeps: no samples of this step, src/taylor_adaptive_batch.cpp:1962-1968. The multi-step launches of
+            // batch_semantics == 2 keep theirs: every lane on its own.)
+            if (!multi_step) {
+                d.grid_mod->launch("hy_grid_unsample", N, 256, &a, sizeof(a), d.stream);
+            }
             // A non-finite state was detected: stop (the outcomes of the last step are reported). With coefficients on
             // demand the lanes which did not reach a grid point in this sweep hold the coefficients of OLDER steps:
             // get_tc() / update_d_output() refuse to hand those out as the last step's (tc_stale).
@@ -2598,6 +2669,21 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
             d.prop_res_override = taylor_outcome::step_limit;
             break;
         }
+    }
+    if (detail::log_enabled(log_level::debug)) {
+        detail::log_message(
+            log_level::debug,
+            std::string("propagate_grid() loop: ")
+                + (multi_step_chosen ? "multi-step launches (one per grid interval and lane: no callback, no events, no "
+                                       "max_steps, Taylor coefficients on demand)"
+                                     : (!tc_on_demand ? "single-step sweeps (a callback, events or a single grid point: "
+                                                        "the coefficients of every step)"
+                                                      : "single-step sweeps (the stepper has no multi-step grid mode, "
+                                                        "max_steps > 0 or lock-step semantics)"))
+                + ", " + std::to_string(n_launches) + " stepper launches for " + std::to_string(n_grid - 1u)
+                + " grid intervals"
+                + (n_rollbacks != 0u ? ", a non-finite lane: rolled back to the start of the grid and redone in single-step sweeps"
+                                     : ""));
     }
     if (multi_step && any_step) {
         // (The accumulated counters / extrema take the place of the last launch's own.)

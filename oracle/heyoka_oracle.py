@@ -1115,6 +1115,177 @@ class OracleIntegrator:
         # truncation only matters when time_lo != 0 and is irrelevant for the golden vectors.
         return self.propagate_until(tf, **kw)
 
+    def _dense(self, i, h):
+        """Dense output of lane i at h from the Taylor coefficients."""
+        B, p = self.batch_size, self.order
+        tc = self.tc.reshape(self.n_eq, p + 1, B)[:, :, i]
+        out = np.empty(self.n_eq)
+        for v in range(self.n_eq):
+            if self.high_accuracy:
+                res, comp, cur_h = tc[v, 0], 0.0, h
+                for k in range(1, p + 1):
+                    tmp = tc[v, k] * cur_h
+                    y = tmp - comp
+                    t = res + y
+                    comp = (t - res) - y
+                    res = t
+                    cur_h = cur_h * h
+            else:
+                res = tc[v, p]
+                for k in range(1, p + 1):
+                    res = tc[v, p - k] + res * h
+            out[v] = res
+        return out
+
+    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None):
+        """propagate_grid_impl() of src/taylor_adaptive_batch.cpp:1546-2055, line by line: lock-step sweeps of step(wtc=True),
+        dense output of the step which spans a grid time at the offset the reference computes in double-length arithmetic.
+        grid: (n_grid,) for every lane or (n_grid, batch_size). Returns (prop_res, out) with out[point, var, lane], NaN in the
+        rows which were not reached. callback(self) -> bool is invoked once per sweep, like the reference's step callback."""
+        B, dim = self.batch_size, self.n_eq
+        g = np.array(grid, dtype=np.float64)
+        if g.ndim == 1:
+            g = np.repeat(g[:, None], B, axis=1)
+        if g.size == 0:
+            raise ValueError("Cannot invoke propagate_grid() in an adaptive Taylor integrator in batch mode if the time grid is empty")
+        if g.ndim != 2 or g.shape[1] != B:
+            raise ValueError("Invalid grid size detected in propagate_grid()")
+        n_grid = g.shape[0]
+        md = np.full(B, np.inf) if max_delta_t is None else np.broadcast_to(np.array(max_delta_t, dtype=np.float64), (B,)).copy()
+        # max_delta_t checks (:1606-1615).
+        if np.any(np.isnan(md)):
+            raise ValueError("A nan max_delta_t was passed to the propagate_grid() function of an adaptive Taylor integrator in batch mode")
+        if np.any(md <= 0):
+            raise ValueError("A non-positive max_delta_t was passed to the propagate_grid() function of an adaptive Taylor integrator "
+                             "in batch mode")
+        # Grid checks (:1620-1675): finite, monotonic, one direction for every lane (taken from lane 0, whose first two
+        # points must differ), starting from the current time.
+        if not (np.all(np.isfinite(self.time_hi)) and np.all(np.isfinite(self.time_lo))):
+            raise ValueError("Cannot invoke propagate_grid() in an adaptive Taylor integrator in batch mode if the current time is not finite")
+        if not np.all(np.isfinite(g)):
+            raise ValueError("A non-finite time value was passed to propagate_grid() in an adaptive Taylor integrator in batch mode")
+        if n_grid > 1:
+            if g[1, 0] == g[0, 0]:
+                raise ValueError("A non-monotonic time grid was passed to propagate_grid() in an adaptive Taylor integrator in batch mode")
+            direction = g[1, 0] > g[0, 0]
+            if np.any((g[1] > g[0]) != direction) or np.any((g[2:] > g[1:-1]) != direction):
+                raise ValueError("A non-monotonic time grid was passed to propagate_grid() in an adaptive Taylor integrator in batch mode")
+        if np.any(self.time_hi != g[0]):
+            raise ValueError("When invoking propagate_grid(), the first element of the time grid must match the current time coordinate")
+        out = np.full((n_grid, dim, B), np.nan)
+        # To the first grid point (the double-length correction of the current time), with the coefficients (:1690-1714).
+        pr = self._lockstep_until(g[0], md, max_steps)
+        if any(r[0] != OC_TIME_LIMIT for r in pr):
+            self.prop_res = [(r[0], math.inf, 0.0, 0) for r in pr]
+            return self.prop_res, out
+        out[0] = self.state.reshape(dim, B)
+        rem = [_df_sub((g[-1, i], 0.0), (self.time_hi[i], self.time_lo[i])) for i in range(B)]
+        if not all(math.isfinite(r[0]) and math.isfinite(r[1]) for r in rem):
+            raise ValueError("The final time passed to the propagate_grid() function of an adaptive Taylor integrator in batch mode "
+                             "results in an overflow condition")
+        t_dir = [r >= (0.0, 0.0) for r in rem]
+        it, ts_count, mn, mx = 0, [0] * B, [math.inf] * B, [0.0] * B
+        gidx = [1] * B
+        while any(k < n_grid for k in gidx):
+            # Time range of the last step, and every grid point it serves (:1782-1871).
+            t0, t1, tstart = [], [], []
+            for i in range(B):
+                cur = (self.time_hi[i], self.time_lo[i])
+                cmp_ = _df_sub(cur, (self.last_h[i], 0.0))
+                t0.append(min(cur, cmp_))
+                t1.append(max(cur, cmp_))
+                tstart.append(cmp_)
+            dflags = [True] * B
+            while True:
+                counter = 0
+                for i in range(B):
+                    if dflags[i] and gidx[i] < n_grid:
+                        tg = (g[gidx[i], i], 0.0)
+                        dflags[i] = (t0[i] <= tg <= t1[i]) or rem[i] == (0.0, 0.0)
+                        counter += dflags[i]
+                    else:
+                        dflags[i] = False
+                if counter == 0:
+                    break
+                for i in range(B):
+                    if dflags[i]:
+                        # update_d_output(): hd = time - ((t_hi, t_lo) - last_h), in double-length, rounded (:2281-2286).
+                        hd = _df_sub((g[gidx[i], i], 0.0), tstart[i])[0]
+                        out[gidx[i], :, i] = self._dense(i, hd)
+                        gidx[i] += 1
+                if not any(k < n_grid for k in gidx):
+                    break
+            if not any(k < n_grid for k in gidx):
+                break
+            # Interruptions: cb_stop, a stopping terminal event, step_limit (:1889-1898).
+            if any(r[0] == OC_CB_STOP or OC_SUCCESS < r[0] < 0 or r[0] == OC_STEP_LIMIT for r in self.prop_res):
+                break
+            # The next sweep, limited by max_delta_t and the remaining time (:1915-1930).
+            lims = np.array([_df_to_d(_df_min((md[i], 0.0), rem[i]) if t_dir[i] else _df_max((-md[i], 0.0), rem[i])) for i in range(B)])
+            res = self.step(lims, wtc=True)
+            nfs, pr = False, []
+            for i, (oc, h) in enumerate(res):
+                if oc == OC_ERR_NF_STATE:
+                    nfs = True
+                else:
+                    ts_count[i] += int(h != 0)
+                    if oc == OC_SUCCESS:
+                        mn[i], mx[i] = min(mn[i], abs(h)), max(mx[i], abs(h))
+                    if h == rem[i][0]:
+                        rem[i] = (0.0, 0.0)
+                    else:
+                        rem[i] = _df_sub((g[-1, i], 0.0), (self.time_hi[i], self.time_lo[i]))
+                pr.append((oc, mn[i], mx[i], ts_count[i]))
+            self.prop_res = pr
+            if nfs:
+                break
+            it += 1
+            if callback is not None and not callback(self):
+                self.prop_res = [(OC_CB_STOP,) + r[1:] for r in pr]
+            elif it == max_steps:
+                self.prop_res = [(OC_STEP_LIMIT,) + r[1:] for r in pr]
+        return self.prop_res, out
+
+    def _lockstep_until(self, tf, md, max_steps):
+        """propagate_until_impl() (src/taylor_adaptive_batch.cpp:1338-1530) with write_tc = true, through self.step()."""
+        B = self.batch_size
+        tf = np.broadcast_to(np.array(tf, dtype=np.float64), (B,))
+
+        def rem_of(i):
+            return _df_sub((tf[i], 0.0), (self.time_hi[i], self.time_lo[i]))
+
+        rem = [rem_of(i) for i in range(B)]
+        t_dir = [r >= (0.0, 0.0) for r in rem]
+        ts_count, mn, mx = [0] * B, [math.inf] * B, [0.0] * B
+        it = 0
+        while True:
+            lims = np.array([_df_to_d(_df_min((md[i], 0.0), rem[i]) if t_dir[i] else _df_max((-md[i], 0.0), rem[i])) for i in range(B)])
+            res = self.step(lims, wtc=True)
+            n_done, nfs, ste, pr = 0, False, False, []
+            for i, (oc, h) in enumerate(res):
+                if oc == OC_ERR_NF_STATE:
+                    nfs = True
+                else:
+                    ts_count[i] += int(h != 0)
+                    if oc == OC_SUCCESS:
+                        mn[i], mx[i] = min(mn[i], abs(h)), max(mx[i], abs(h))
+                    ste = ste or (OC_SUCCESS < oc < 0)
+                    if h == rem[i][0]:
+                        n_done += 1
+                        rem[i] = (0.0, 0.0)
+                    else:
+                        rem[i] = rem_of(i)
+                pr.append((oc, mn[i], mx[i], ts_count[i]))
+            self.prop_res = pr
+            if nfs:
+                return pr
+            it += 1
+            if n_done == B or ste:
+                return pr
+            if it == max_steps:
+                self.prop_res = [(OC_STEP_LIMIT,) + r[1:] for r in pr]
+                return self.prop_res
+
 
 def dfloat_add(ahi, alo, bhi, blo):
     rh, rl = ctypes.c_double(), ctypes.c_double()
@@ -1123,6 +1294,41 @@ def dfloat_add(ahi, alo, bhi, blo):
         ctypes.byref(rl)
     )
     return rh.value, rl.value
+
+
+def _eft_add_knuth(a, b):
+    x = a + b
+    z = x - a
+    return x, (a - (x - z)) + (b - z)
+
+
+def _eft_add_dekker(a, b):
+    x = a + b
+    return x, (a - x) + b
+
+
+def _df_add(a, b):
+    """dfloat addition of include/heyoka/detail/dfloat.hpp:128-147 on (hi, lo) tuples (tuple order is dfloat's operator<)."""
+    x_hi, y_hi = _eft_add_knuth(a[0], b[0])
+    x_lo, y_lo = _eft_add_knuth(a[1], b[1])
+    u, v = _eft_add_dekker(x_hi, y_hi + x_lo)
+    return _eft_add_dekker(u, v + y_lo)
+
+
+def _df_sub(a, b):
+    return _df_add(a, (-b[0], -b[1]))
+
+
+def _df_min(a, b):
+    return b if b < a else a
+
+
+def _df_max(a, b):
+    return b if a < b else a
+
+
+def _df_to_d(a):
+    return a[0]
 
 
 def ensemble_propagate_until(sys, state, n_systems, batch_size, t_final, tol=None, high_accuracy=False, pars=None,
@@ -1494,28 +1700,6 @@ class OracleEventIntegrator(OracleIntegrator):
         if pars.size == self.pars.size:
             self.pars = pars
         self.sys = sysv
-
-    def _dense(self, i, h):
-        """Dense output of lane i at h from the Taylor coefficients."""
-        B, p = self.batch_size, self.order
-        tc = self.tc.reshape(self.n_eq, p + 1, B)[:, :, i]
-        out = np.empty(self.n_eq)
-        for v in range(self.n_eq):
-            if self.high_accuracy:
-                res, comp, cur_h = tc[v, 0], 0.0, h
-                for k in range(1, p + 1):
-                    tmp = tc[v, k] * cur_h
-                    y = tmp - comp
-                    t = res + y
-                    comp = (t - res) - y
-                    res = t
-                    cur_h = cur_h * h
-            else:
-                res = tc[v, p]
-                for k in range(1, p + 1):
-                    res = tc[v, p - k] + res * h
-            out[v] = res
-        return out
 
     def step(self, max_delta_ts=None, wtc=False, backward=False):
         B, p = self.batch_size, self.order

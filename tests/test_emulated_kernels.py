@@ -242,3 +242,31 @@ def test_emulated_v5_propagation_from_grid_point_to_grid_point():
     assert np.all(r2["time_hi"] == 1.0) and np.all(r2["outcome"] == int(hy.taylor_outcome.time_limit))
     # hy_kargs::grid_done: 1 for the systems whose last step was clamped to the remaining time, 0 for a grid-point exit.
     assert np.all(r2["grid_done"] == 1.0) and np.all(r["grid_done"] == 0.0)
+
+
+def test_emulated_v5_grid_launch_with_a_lane_which_goes_nonfinite():
+    """The multi-step grid launch (hy_kargs::pad bit 2, a.tc_thr) with a system which goes non-finite between two grid points
+    (Jupiter falling radially onto the Sun, t = 0.597): that system ends with err_nf_state and the counters of the steps
+    BEFORE the non-finite one - its own lock-step propagation in the oracle (hy_grid_post adds them with per-lane semantics;
+    with the reference's semantics the host rolls the launch back, counters[0] says so) - while the others run on to the
+    grid point."""
+    n = 5
+    st = configs.outer_ss_state(n, perturb=1e-6, seed=3).reshape(36, n).copy()
+    st[6:9, 1] = st[0:3, 1] + np.array([2.25, 0.0, 0.0])
+    st[9:12, 1] = st[3:6, 1]
+    ta = _outer_ss("v5")
+    k = emu.EmulatedKernel(ta.hip_source)
+    p = ta.order
+    r = k.run(st, np.zeros(n), np.zeros(n), mode=1, tfin=np.full(n, 4.0), lim=np.full(n, 0.01), pad=4, tc_thr=np.full(n, 1.0),
+              want_tc_rows=36 * (p + 1), max_grid=1)
+    assert r["counters"][0] == 1
+    assert r["outcome"][1] == int(hy.taylor_outcome.err_nf_state)
+    ok = [0, 2, 3, 4]
+    assert np.all(r["time_hi"][ok] >= 1.0) and np.all(r["time_hi"][ok] - r["last_h"][ok] < 1.0)
+    solo = ho.OracleIntegrator(ho.nbody(6, masses=M, Gconst=G), st[:, 1:2], 1, high_accuracy=True)
+    (oc, mn, mx, ns), = solo.propagate_until(4.0, max_delta_t=0.01)
+    assert oc == ho.OC_ERR_NF_STATE
+    print("[emulated v5, diverging system] steps %d (oracle %d), min |h| %.17g (oracle %.17g), max |h| %.17g (oracle %.17g)"
+          % (int(r["n_steps"][1]), ns, r["min_h"][1], mn, r["max_h"][1], mx))
+    assert int(r["n_steps"][1]) == ns
+    assert abs(r["max_h"][1] - mx) <= 1e-9 * mx and abs(r["min_h"][1] - mn) <= 1e-9 * mn

@@ -350,3 +350,138 @@ def test_bracket_solver_is_algorithm_748_with_the_reference_budget():
     assert ho._bracketed_root([1.0, 0.0, 1.0], 0.0, 1.0)[1] == 1
     # A root exactly at an end is returned as it is.
     assert ho._bracketed_root([0.0, 1.0], 0.0, 1.0) == (0.0, 0)
+
+
+# ---- propagate_grid() of the oracle (src/taylor_adaptive_batch.cpp:1546-2055), the yardstick of the GPU grid tests ----
+def test_oracle_propagate_grid_tutorial_known_answers(golden):
+    """doc/tut_adaptive.rst:324-325 (the values test_propagate_grid checks on the GPU) and the propagate_grid() of the events
+    tutorial (doc/tut_events.rst: propagate_grid(1 .. 10) after the first terminal event and propagate_until(1))."""
+    ta = ho.OracleIntegrator(pendulum(), [[0.05] * 3, [0.025] * 3], 3)
+    pr, out = ta.propagate_grid(np.linspace(0.0, 1.0, 11))
+    assert out.shape == (11, 2, 3)
+    assert sig_close(out[4, 0, 0], 0.0232578) and sig_close(out[4, 1, 0], -0.14078)
+    assert np.array_equal(out[0], [[0.05] * 3, [0.025] * 3]) and not np.isnan(out).any()
+    assert all(r[0] == ho.OC_TIME_LIMIT for r in pr) and np.array_equal(ta.time_hi, [1.0] * 3)
+    assert np.max(np.abs(out[-1] - ta.state.reshape(2, 3))) <= 10 * EPS
+
+    g = golden["events_tutorial"]["terminal_drag_toggle"]
+    x, v = ho.var("x"), ho.var("v")
+
+    def toggle(ta, d_sgn, idx):
+        ta.pars[0] = 1.0 if ta.pars[0] == 0 else 0.0
+        return True
+
+    te = ho.OracleEventIntegrator([(x, v), (v, -9.8 * ho.sin(x) - ho.par(0) * v)], g["ic"], 1,
+                                  t_events=[ho.t_event(v, toggle)], pars=[0.0])
+    while te.step()[0][0] == ho.OC_SUCCESS:
+        pass
+    te.propagate_until(1.0)
+    pr, out = te.propagate_grid(np.array(g["grid"], dtype=float))
+    assert pr[0][0] == ho.OC_TIME_LIMIT and te.time_hi[0] == g["grid"][-1]
+    assert np.max(np.abs(out[:, :, 0] - np.array(g["grid_states"]))) <= 1e-13
+
+
+def _grid_rows_vs_until(sys_fn, st, n, grid, max_delta_t=None, t0=None):
+    ta = ho.OracleIntegrator(sys_fn(), st, n, time=t0)
+    if t0 is not None:
+        for _ in range(3):
+            ta.step()
+        grid = grid + ta.time_hi[None, :]
+        grid[0] = ta.time_hi
+    start = (ta.state.copy(), ta.time_hi.copy(), ta.time_lo.copy())
+    pr, out = ta.propagate_grid(grid, max_delta_t=max_delta_t)
+    assert all(r[0] == ho.OC_TIME_LIMIT for r in pr) and not np.isnan(out).any()
+    err = 0.0
+    for k in range(1, grid.shape[0]):
+        tu = ho.OracleIntegrator(sys_fn(), start[0], n)
+        tu.time_hi, tu.time_lo = start[1].copy(), start[2].copy()
+        tu.propagate_until(grid[k], max_delta_t=max_delta_t)
+        err = max(err, float(np.max(np.abs(out[k] - tu.state.reshape(-1, n)) / np.max(np.abs(tu.state.reshape(-1, n)), axis=1, keepdims=True))))
+    return start, pr, out, err
+
+
+def test_oracle_propagate_grid_against_propagate_until_to_every_grid_point():
+    """Every sample of the grid oracle against the oracle's propagate_until() to that grid time from the same start: forward,
+    backward, per-lane grids, several grid points per step, max_delta_t below the natural step, and a start time of 1e4 with
+    a nonzero low part (three free steps from t = 1e4, as the double-length time of a long run)."""
+    n = 5
+    rng = np.random.RandomState(8)
+    st = np.stack([rng.uniform(-0.5, 0.5, n), rng.uniform(-0.5, 0.5, n)])
+    spacing = np.array([0.03, 0.05, 0.07, 0.11, 0.13])
+    for sign in (1.0, -1.0):
+        for mdt, t0 in ((None, None), (0.02, None), (None, 1e4 + 0.1)):
+            grid = sign * np.outer(np.arange(12.0), spacing)
+            start, pr, out, err = _grid_rows_vs_until(pendulum, st, n, grid, max_delta_t=mdt, t0=t0)
+            # (Step sizes of this pendulum: about 0.2 - several grid points per step without max_delta_t.)
+            assert err <= 1e3 * EPS, (sign, mdt, t0, err / EPS)
+            if t0 is not None:
+                assert np.all(start[2] != 0.0), start[2]
+            if mdt is not None:
+                assert all(r[3] >= int(np.ceil(11 * spacing[i] / mdt)) for i, r in enumerate(pr))
+
+
+def test_oracle_propagate_grid_rejects_what_the_reference_rejects():
+    """The argument checks of propagate_grid_impl() (:1596-1675): nan or non-positive max_delta_t, equal first two grid points
+    in lane 0 (the direction comes from lane 0), lanes going the other way, non-monotonic or non-finite points, a first grid
+    point other than the current time. A refused call changes nothing."""
+    ta = ho.OracleIntegrator(pendulum(), [[0.05] * 2, [0.025] * 2], 2)
+    grid = np.outer(np.linspace(0.0, 1.0, 5), [1.0, 1.0])
+    for bad in (np.nan, 0.0, -1.0):
+        with pytest.raises(ValueError, match="nan max_delta_t" if bad != bad else "non-positive max_delta_t"):
+            ta.propagate_grid(grid, max_delta_t=bad)
+    for g in (np.array([[0.0, 0.0], [0.0, 0.5], [1.0, 1.0]]),  # a tie in lane 0
+              np.array([[0.0, 0.0], [0.5, -0.5], [1.0, -1.0]]),  # lane 1 backward
+              np.array([[0.0, 0.0], [0.5, 0.5], [0.4, 1.0]])):  # not monotonic
+        with pytest.raises(ValueError, match="non-monotonic time grid"):
+            ta.propagate_grid(g)
+    with pytest.raises(ValueError, match="non-finite time value"):
+        ta.propagate_grid(np.array([[0.0, 0.0], [np.inf, 1.0]]))
+    with pytest.raises(ValueError, match="must match the current time coordinate"):
+        ta.propagate_grid(np.array([[0.1, 0.0], [1.0, 1.0]]))
+    assert np.array_equal(ta.state, [0.05, 0.05, 0.025, 0.025]) and np.array_equal(ta.time_hi, [0.0, 0.0])
+
+
+def _collision_state(n, d=2.25):
+    """Outer Solar Systems; in lane 1 Jupiter falls radially onto the Sun from distance d (AU): the state goes non-finite at
+    t = 0.597 for d = 2.25, strictly between grid points of the grids below."""
+    from heyoka_amd import configs
+
+    st = configs.outer_ss_state(n, perturb=1e-6, seed=3).reshape(36, n).copy()
+    st[6:9, 1] = st[0:3, 1] + np.array([d, 0.0, 0.0])
+    st[9:12, 1] = st[3:6, 1]
+    return st
+
+
+def test_oracle_propagate_grid_a_nonfinite_lane_stops_the_batch_after_that_sweep():
+    """A lane which goes non-finite between two grid points stops the WHOLE batch after that sweep (:1936-2000): the healthy
+    lanes keep the time, the samples and the step count of that sweep (a lane on its own runs on); the non-finite lane's
+    counters are those before its last step. A lane non-finite from the start: nothing is sampled, counters reset."""
+    from heyoka_amd import configs
+
+    M, G = configs.OUTER_SS_MASSES, configs.OUTER_SS_G
+    n = 5
+    st = _collision_state(n)
+    grid = np.linspace(0.0, 4.0, 9)
+    ta = ho.OracleIntegrator(ho.nbody(6, masses=M, Gconst=G), st, n, high_accuracy=True)
+    pr, out = ta.propagate_grid(grid, max_delta_t=0.01)
+    oc = [r[0] for r in pr]
+    assert oc[1] == ho.OC_ERR_NF_STATE and all(o == ho.OC_TIME_LIMIT for i, o in enumerate(oc) if i != 1)
+    sweeps = pr[0][3]
+    ok = [0, 2, 3, 4]
+    assert all(pr[i][3] == sweeps for i in ok) and 0 < pr[1][3] < sweeps
+    # (The non-finite lane stopped between grid points 1 and 2; the healthy lanes at sweep `sweeps`, short of the end.)
+    assert np.all(np.abs(ta.time_hi[ok] - 0.01 * sweeps) <= 1e-12) and 0.5 < 0.01 * sweeps < 4.0
+    reached = grid <= 0.01 * sweeps
+    assert np.array_equal(np.isnan(out[:, 0, ok]), np.repeat(~reached[:, None], 4, axis=1))
+    assert not np.isnan(out[:2, :, 1]).any() and np.isnan(out[2:, :, 1]).all()
+    # A healthy lane on its own runs through the grid: the same samples bit for bit where the batch reached them.
+    solo = ho.OracleIntegrator(ho.nbody(6, masses=M, Gconst=G), st[:, :1], 1, high_accuracy=True)
+    pr1, out1 = solo.propagate_grid(grid, max_delta_t=0.01)
+    assert pr1[0][0] == ho.OC_TIME_LIMIT and pr1[0][3] > sweeps
+    assert np.array_equal(out1[reached, :, 0], out[reached, :, 0])
+    # Non-finite from the start: the initial propagate_until() already stops (outcomes kept, counters reset, all NaN).
+    st0 = configs.outer_ss_state(n, perturb=1e-6, seed=3).reshape(36, n).copy()
+    st0[7, 2] = np.nan
+    tb = ho.OracleIntegrator(ho.nbody(6, masses=M, Gconst=G), st0, n, high_accuracy=True)
+    pr0, out0 = tb.propagate_grid(grid)
+    assert pr0[2][0] == ho.OC_ERR_NF_STATE and all(r[1:] == (np.inf, 0.0, 0) for r in pr0) and np.isnan(out0).all()
