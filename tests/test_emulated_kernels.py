@@ -270,3 +270,121 @@ def test_emulated_v5_grid_launch_with_a_lane_which_goes_nonfinite():
           % (int(r["n_steps"][1]), ns, r["min_h"][1], mn, r["max_h"][1], mx))
     assert int(r["n_steps"][1]) == ns
     assert abs(r["max_h"][1] - mx) <= 1e-9 * mx and abs(r["min_h"][1] - mn) <= 1e-9 * mn
+
+
+# ---- batch-size independence (the CPU half of tests/test_batch_independence.py) ----
+def _independence_kernels():
+    from heyoka_amd import mixed_models as mm
+
+    def outer(kernel, **kw):
+        return lambda: (_outer_ss(kernel, **kw), lambda n: configs.outer_ss_state(n, perturb=1e-3, seed=9), {})
+
+    def cloud(nb):
+        def state(n):
+            rng = np.random.RandomState(40 + nb)
+            pos = rng.uniform(-3.0, 3.0, (nb, 3, n)) + 6.0 * np.arange(nb)[:, None, None] * np.array([1.0, 0.3, -0.2])[None, :, None]
+            vel = rng.uniform(-0.3, 0.3, (nb, 3, n))
+            return np.concatenate([np.concatenate([pos[b], vel[b]], axis=0) for b in range(nb)], axis=0)
+
+        masses = list(1.0 / (1.0 + np.arange(nb)) ** 2)
+        return lambda: (hy.taylor_adaptive_batch(hy.model.nbody(nb, masses=masses), None, 64, high_accuracy=True, cluster_kernel="v5"), state, {})
+
+    def lattice():
+        ta = hy.taylor_adaptive_batch(mm.sine_lattice(hy, 16), None, 64)
+        return ta, lambda n: mm.sine_lattice_state(16, n), {"scratch_per_wave": (ta.order + 1) * 4 * 64}
+
+    def staged():
+        ta = hy.taylor_adaptive_batch(hy.model.nbody(6, masses=M, Gconst=G), None, 64, high_accuracy=True, emitter="table")
+        return ta, lambda n: configs.outer_ss_state(n, perturb=1e-3, seed=9), {}
+
+    # name: (builder of (integrator, states, extra launch arguments), expected mode, systems per wavefront / workgroup,
+    # horizon of the propagation through the work queue or None)
+    return {
+        "v5": (outer("v5"), "mode v5", 4, 2.0), "v5-nofrx": (outer("v5-nofrx"), "mode v5", 4, 2.0),
+        "v3": (outer("v3"), "mode v3", 2, None), "v2": (outer("v2"), "mode v2", 4, None),
+        "v5-nbody3": (cloud(3), "mode v5", 8, 6.0), "v5-nbody4": (cloud(4), "mode v5", 4, 6.0), "v5-nbody8": (cloud(8), "mode v5", 2, 6.0),
+        "multi-class": (lattice, "2 classes of clusters", 4, None), "staged": (staged, "table mode (staged)", 1, None),
+    }
+
+
+@pytest.mark.parametrize("name", sorted(_independence_kernels()))
+def test_emulated_kernels_results_do_not_depend_on_the_batch_size(name):
+    """The integration of a system depends on nothing but that system: one step with all Taylor coefficients of 1, 2, 3,
+    S - 1, S and S + 1 systems (S: the systems of a wavefront, or of a workgroup for the staged stepper) and of a window
+    of a larger batch gives BIT FOR BIT the columns of the run of that larger batch (2 S + 3 systems): states, times, step
+    sizes, outcomes and every Taylor coefficient. For the one-lane-per-pair kernel also a propagation with per-system
+    final times through the work queue of ONE workgroup, the larger batch 5 systems beyond what the workgroup keeps in
+    flight (as test_emulated_v5_propagation_through_the_work_queue_with_refill: 37 systems on 32 slots), so that systems
+    which were REFILLED into the lanes of a finished system are compared with their own first-fill runs - counters and
+    smallest / largest steps included. One compilation per kernel. The GPU half - every family, the
+    propagation loops, the grid, events - is tests/test_batch_independence.py; a difference there which this test does not
+    show is the hardware's side of the packing (cross-lane operations with idle lanes, LDS slabs of absent systems, launch
+    geometry), not the generators' arithmetic."""
+    from test_batch_independence import systems_per_unit
+
+    build, want, S_expected, horizon = _independence_kernels()[name]
+    ta, state, extra = build()
+    assert want in ta.hip_source_mode, ta.hip_source_mode
+    S = systems_per_unit(ta.hip_source_mode)
+    assert S == S_expected, ta.hip_source_mode
+    k = emu.EmulatedKernel(ta.hip_source)
+    sizes = sorted({1, 2, 3, S - 1, S, S + 1} - {0})
+    window = np.arange(3, 3 + S + 1)
+    n_big = max(2 * S + 3, 5)
+    st = state(n_big)
+    rows = st.shape[0] * (ta.order + 1)
+    big = k.run(st, np.zeros(n_big), np.zeros(n_big), mode=0, lim=np.full(n_big, np.inf), want_tc_rows=rows, **extra)
+    assert np.all(big["last_h"] > 0) and np.isfinite(big["tc"]).all()
+    for idx in [np.arange(n) for n in sizes] + [window]:
+        n = len(idx)
+        part = k.run(st[:, idx], np.zeros(n), np.zeros(n), mode=0, lim=np.full(n, np.inf), want_tc_rows=rows, **extra)
+        for key in ("state", "time_hi", "time_lo", "last_h", "outcome", "tc"):
+            assert np.array_equal(part[key], big[key][..., idx]), (name, "step", key, "systems %d .. %d" % (idx[0], idx[-1]))
+    if horizon is None:
+        return
+    # The propagation: ONE workgroup keeps `slots` systems in flight, the larger run holds 5 more - the systems slots ..
+    # slots + 4 are pulled from the queue by the lanes of systems which have finished and inherit their registers and
+    # bookkeeping slabs (the retire / refill path). The small prefixes and the window slots - 2 .. slots + 4 on their own
+    # are all first-fill systems: refilled and first-fill runs of the same system are compared bit for bit.
+    assert "snew < N" in ta.hip_source  # (this kernel has the refill path)
+    slots = k.block // k.lanes_per_system
+    n_prop = slots + 5
+    st = state(n_prop)
+    tf = horizon * np.random.RandomState(1).uniform(0.5, 1.5, n_prop)
+    bigp = k.run(st, np.zeros(n_prop), np.zeros(n_prop), mode=1, tfin=tf, max_grid=1, **extra)
+    assert np.array_equal(bigp["time_hi"], tf) and np.unique(bigp["n_steps"]).size > 1
+    for idx in [np.arange(n) for n in sizes] + [window, np.arange(slots - 2, n_prop)]:
+        n = len(idx)
+        part = k.run(st[:, idx], np.zeros(n), np.zeros(n), mode=1, tfin=tf[idx], max_grid=1, **extra)
+        for key in ("state", "time_hi", "time_lo", "last_h", "outcome", "n_steps", "min_h", "max_h"):
+            assert np.array_equal(part[key], bigp[key][..., idx]), (name, "propagation", key, "systems %d .. %d" % (idx[0], idx[-1]))
+
+
+def test_batch_independence_families_select_their_kernels():
+    """Every family of tests/test_batch_independence.py reaches the kernel it names (no GPU is needed to generate the
+    source), the source of a family is the same for every batch size, and S - the systems which one wavefront or
+    workgroup serves, as the GPU test derives it from hip_source_mode - is what DESIGN.md tabulates."""
+    import test_batch_independence as tbi
+
+    S_table = {"v5": 4, "v5_32_lanes": 2, "v5_8_lanes_lds_jets": 8, "v5_16_lanes_lds_jets": 4, "v5_events": 4, "v3": 2, "v3_64_lanes": 1,
+               "v2": 4, "v2_aliased": 4, "multi_class": 4, "unrolled": 64, "unrolled_two_waves": 64, "unrolled_register_jets": 64,
+               "staged": 1, "table_hbm": 64, "staged_functions": 1, "table_hbm_functions": 64, "block_centres": 1, "block_v2": 1,
+               "block_v2_nbody64": 1}
+    assert set(S_table) == set(tbi.FAMILIES)
+    assert tbi.sizes_for(4, 131) == [1, 2, 3, 4, 5, 9, 65] and tbi.sizes_for(1, 131) == [1, 2, 3, 65]
+    assert tbi.sizes_for(64, 131) == [1, 2, 3, 63, 64, 65, 129] and tbi.sizes_for(8, 131) == [1, 2, 3, 7, 8, 9, 17, 65]
+    assert tbi.sizes_for(2, 131) == [1, 2, 3, 5, 65]
+    for name, fam in tbi.FAMILIES.items():
+        kw = dict(fam.get("kw", {}))
+        src = set()
+        for n in (1, 3, tbi.N_POOL):
+            if fam.get("events"):
+                kw.update(tbi._outer_ss_events(hy, []))
+            with tbi._env(fam.get("env")):
+                ta = hy.taylor_adaptive_batch(fam["sys"](hy), None, n, **kw)
+            for w in fam["want"]:
+                assert w in ta.hip_source_mode, (name, w, ta.hip_source_mode)
+            assert fam.get("not_want", "\0") not in ta.hip_source_mode, (name, ta.hip_source_mode)
+            assert tbi.systems_per_unit(ta.hip_source_mode) == S_table[name], (name, ta.hip_source_mode)
+            src.add(ta.hip_source)
+        assert len(src) == 1, name + ": the generated source depends on the batch size"
