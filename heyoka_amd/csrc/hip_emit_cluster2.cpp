@@ -46,6 +46,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // (profiles/experiments/ab.py compares variants inside one process). Every flag switches OFF one of the round-5 items:
     //   nomsq     three accumulators for the half sums of squares (one per coordinate) instead of one;
     //   nopack2   the final evaluation of a partially filled owner slot as a full two-series pass;
+    //   notailrd  the jet reads of the final evaluation behind the step size instead of ahead of the selector;
     const auto v5_flag = [&opts](const char *name) {
         if (opts.dev.v5_opts.empty()) {
             return false;
@@ -3093,6 +3094,74 @@ const bool hy_tc_only = HY_M4 && ((a.pad & 2) != 0);
     }
     // NOTE: rho = exp(log(x) / order) (hy_root): the minimum of the two estimates is taken on the exponents (exp is
     // monotone and keeps NaNs: the same selection as min(rho_o, rho_om1), src/taylor_02.cpp:1050-1072, one exp less).
+    // The passes of the final evaluation of the one-lane kernel, in order: one per variable with a jet column (ow), with the
+    // variable derived from it (dv: x' = v, at most one - chains of length <= 2); `packed` = the partially filled owner
+    // slot which runs one series per lane. rows / facs: the names of the jet rows (and of the factors RN(1 / k) of a packed
+    // pass) where their LDS reads have been issued ahead of the selector - empty otherwise.
+    struct tail_pass {
+        const owner_slot *ow, *dv;
+        bool packed;
+        std::vector<std::string> rows, facs;
+    };
+    std::vector<tail_pass> tail_passes;
+    for (const auto &rg : rounds) {
+        for (const auto &gr : rg) {
+            for (const auto &ow : gr.owners) {
+                if (!one_lane || ow.derived) {
+                    continue;
+                }
+                const owner_slot *dv = nullptr;
+                for (const auto &o2 : gr.owners) {
+                    if (o2.derived && o2.parent == ow.col) {
+                        dv = &o2;
+                    }
+                }
+                tail_passes.push_back({&ow, dv, dv != nullptr && pk_tbl.count(ow.col) != 0u, {}, {}});
+            }
+        }
+    }
+    // (Doubles between two rows of a jet column.)
+    const auto kstride = static_cast<std::uint64_t>(spw) * n_colp;
+    // The jet reads of the final evaluation (one-lane kernel, jets in LDS, compensated sums): issued HERE, ahead of the
+    // selector's log / exp chain, which covers their latency - the history registers are dead in the tail, so the 20 rows
+    // of a pass fit. "notailrd" among HEYOKA_AMD_V5_OPTS leaves them behind the step size, where the series consume them.
+    std::uint32_t n_trd = 0, n_trd_used = 0;
+    if (one_lane && !m4 && jet_lds && opts.high_accuracy && packed_tail && !v5_flag("notailrd")) {
+        src << "// (Jet reads of the final evaluation issued ahead of the selector.)\n";
+        const auto hoist = [&](const std::string &ex) {
+            auto nm = "trd" + std::to_string(n_trd++);
+            src << "const double " << nm << " = " << ex << ";\n";
+            return nm;
+        };
+        for (auto &tp : tail_passes) {
+            const auto cs = std::to_string(tp.ow->col);
+            if (tp.packed) {
+                // (Row k of the lane's series at pk_jh[(k - 1) * stride], its factor at pk_fh[k]: see the pass below.)
+                const auto &tb = pk_tbl.at(tp.ow->col);
+                src << "const double *const pk_jh" << cs << " = jetw + q * " << jet_sys(*tp.ow) << "u + hy_utbl[" << tb[1] * L << "u + l];\n";
+                src << "const double *const pk_fh" << cs << " = lds_fac + hy_utbl[" << tb[2] * L << "u + l];\n";
+                tp.rows.resize(order + 1u);
+                tp.facs.resize(order + 1u);
+                for (std::uint32_t k = 1; k <= order; ++k) {
+                    tp.rows[k] = hoist("pk_jh" + cs + "[" + std::to_string((k - 1u) * kstride) + "]");
+                    tp.facs[k] = hoist("pk_fh" + cs + "[" + std::to_string(k) + "]");
+                }
+            } else {
+                for (std::uint32_t k = 0; k <= order; ++k) {
+                    tp.rows.push_back(hoist("jr" + cs + "[" + std::to_string(k * kstride) + "]"));
+                }
+            }
+        }
+        src << "__builtin_amdgcn_sched_barrier(0);\n";
+    }
+    // (A value the final evaluation reads: the name it was given above, or the read itself.)
+    const auto tail_val = [&n_trd_used](const std::vector<std::string> &names, std::uint32_t k, const std::string &ex) {
+        if (names.empty()) {
+            return ex;
+        }
+        ++n_trd_used;
+        return names.at(k);
+    };
     if (packed_tail) {
         // log(num / m) = log(num) - log(m): no quotients (0 -> +inf, inf -> -inf, inf - inf -> nan as for the quotient).
         src << "const double nw = (hy_q0 & (nv <= 1.0)) ? 1.0 : nv;\n";
@@ -3234,124 +3303,117 @@ lim = fin ? 0.0 : lim;
     // src/taylor_00.cpp:279-460). The jets live in LDS (or in the per-wave scratch), so the evaluation is spread
     // evenly over the lanes of the group: slot h, lane l <-> column h * L + l, ceil(n_eq / L) slots instead of
     // one per owner slot (3 instead of 4 for the 36 variables of the outer Solar System on 16 lanes).
-    const auto kstride = static_cast<std::uint64_t>(spw) * n_colp;
     // (name of the new value, where the current value is read, where the new one goes)
     std::vector<std::tuple<std::string, std::string, std::string>> upd;
-    if (one_lane) {
-        // One pass per glue round: the variable with a jet column (v) and the one derived from it (x' = v), whose
-        // coefficients are formed on the fly from the same column, x^[k] = v^[k-1] * RN(1 / k) - bit for bit the published
-        // coefficient (ssa_emitter::div_const() in its reciprocal form). Both sums of a lane share the loads of the column
-        // (one LDS read per order) and the powers of h; every pass is one instruction stream without selects.
-        for (const auto &rg : rounds) {
-            for (const auto &gr : rg) {
-                for (const auto &ow : gr.owners) {
-                    if (ow.derived) {
-                        continue;
-                    }
-                    // The variables derived from this one (at most one: chains of length <= 2).
-                    const owner_slot *dv = nullptr;
-                    for (const auto &o2 : gr.owners) {
-                        if (o2.derived && o2.parent == ow.col) {
-                            dv = &o2;
-                        }
-                    }
-                    const auto xn = "xn" + std::to_string(ow.col);
-                    const auto xd = dv != nullptr ? "xn" + std::to_string(dv->col) : std::string{};
-                    const auto colp = "jr" + std::to_string(ow.col);
-                    if (dv != nullptr && pk_tbl.count(ow.col) != 0u) {
-                        // A partially filled owner slot (18 velocity columns on 16 lanes leave 2): ONE series per lane - the
-                        // lanes [0, n) sum the velocity columns, the lanes [n, 2 n) the series derived from them, whose
-                        // coefficient k is row k - 1 of the same column times RN(1 / k); both kinds run the same statements, the
-                        // row shift sits in the lane's pointer and the factor (1 or RN(1 / k)) comes from a two-row table in LDS.
-                        // Six instructions per order instead of the ten of the two-series pass which 2 of 16 lanes used.
-                        const auto cs = std::to_string(ow.col);
-                        const auto &tb = pk_tbl.at(ow.col);
-                        // (The current value of the lane's variable: order-0 row of the column / entry of the derived variable.)
-                        src << "double *const pk_v" << cs << " = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[0] * L << "u + l];\n";
-                        src << "double " << xn << ";\n{\n";
-                        // (Row k of the lane's series at pk_j[(k - 1) * stride]: the velocity column from row 1 on, from row 0
-                        // on for the derived series.)
-                        src << "const double *const pk_j = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[1] * L << "u + l];\n";
-                        src << "const double *const pk_f = lds_fac + hy_utbl[" << tb[2] * L << "u + l];\n";
-                        src << "double res = pk_v" << cs << "[0], comp = 0.0, cur_h = h;\n";
-                        for (std::uint32_t k = 1; k <= order; ++k) {
-                            src << "{\nconst double ck = pk_j[" << (k - 1u) * kstride << "] * pk_f[" << k << "];\n"
-                                << "const double tmp = ck * cur_h;\nconst double y = tmp - comp;\nconst double t = res + y;\n"
-                                << "comp = (t - res) - y;\nres = t;\n";
-                            if (k < order) {
-                                src << "cur_h = cur_h * h;\n";
-                            }
-                            src << "}\n";
-                        }
-                        src << xn << " = res;\n}\n";
-                        upd.emplace_back(xn, "pk_v" + cs + "[0]", "pk_v" + cs + "[0]");
-                        continue;
-                    }
-                    src << "double " << xn << ";\n";
-                    if (dv != nullptr) {
-                        src << "double " << xd << ";\n";
-                    }
-                    src << "{\n";
-                    if (opts.high_accuracy) {
-                        src << "double cprev = " << colp << "[0];\ndouble res = cprev, comp = 0.0, cur_h = h;\n";
-                        if (dv != nullptr) {
-                            src << "double resd = " << row0_r(*dv) << ", compd = 0.0;\n";
-                        }
-                        for (std::uint32_t k = 1; k <= order; ++k) {
-                            src << "{\nconst double ck = " << colp << "[" << k * kstride << "];\n";
-                            if (dv != nullptr) {
-                                src << "const double cd = cprev * " << fp_literal(1. / static_cast<double>(k)) << ";\n"
-                                    << "const double tmpd = cd * cur_h;\nconst double yd = tmpd - compd;\n"
-                                    << "const double td = resd + yd;\ncompd = (td - resd) - yd;\nresd = td;\n";
-                            }
-                            src << "const double tmp = ck * cur_h;\nconst double y = tmp - comp;\nconst double t = res + y;\n"
-                                << "comp = (t - res) - y;\nres = t;\ncprev = ck;\n";
-                            if (k < order) {
-                                src << "cur_h = cur_h * h;\n";
-                            }
-                            src << "}\n";
-                        }
+    // One pass per glue round: the variable with a jet column (v) and the one derived from it (x' = v), whose
+    // coefficients are formed on the fly from the same column, x^[k] = v^[k-1] * RN(1 / k) - bit for bit the published
+    // coefficient (ssa_emitter::div_const() in its reciprocal form). Both sums of a lane share the loads of the column
+    // (one LDS read per order) and the powers of h; every pass is one instruction stream without selects.
+    for (const auto &tp : tail_passes) {
+        const auto &ow = *tp.ow;
+        const auto *const dv = tp.dv;
+        const auto xn = "xn" + std::to_string(ow.col);
+        const auto xd = dv != nullptr ? "xn" + std::to_string(dv->col) : std::string{};
+        const auto colp = "jr" + std::to_string(ow.col);
+        if (tp.packed) {
+            // A partially filled owner slot (18 velocity columns on 16 lanes leave 2): ONE series per lane - the
+            // lanes [0, n) sum the velocity columns, the lanes [n, 2 n) the series derived from them, whose
+            // coefficient k is row k - 1 of the same column times RN(1 / k); both kinds run the same statements, the
+            // row shift sits in the lane's pointer and the factor (1 or RN(1 / k)) comes from a two-row table in LDS.
+            // Six instructions per order instead of the ten of the two-series pass which 2 of 16 lanes used.
+            const auto cs = std::to_string(ow.col);
+            const auto &tb = pk_tbl.at(ow.col);
+            // (The current value of the lane's variable: order-0 row of the column / entry of the derived variable.)
+            src << "double *const pk_v" << cs << " = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[0] * L << "u + l];\n";
+            src << "double " << xn << ";\n{\n";
+            // (Row k of the lane's series at pk_j[(k - 1) * stride]: the velocity column from row 1 on, from row 0
+            // on for the derived series.)
+            if (tp.rows.empty()) {
+                src << "const double *const pk_j = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[1] * L << "u + l];\n";
+                src << "const double *const pk_f = lds_fac + hy_utbl[" << tb[2] * L << "u + l];\n";
+            }
+            src << "double res = pk_v" << cs << "[0], comp = 0.0, cur_h = h;\n";
+            for (std::uint32_t k = 1; k <= order; ++k) {
+                src << "{\nconst double ck = " << tail_val(tp.rows, k, "pk_j[" + std::to_string((k - 1u) * kstride) + "]") << " * "
+                    << tail_val(tp.facs, k, "pk_f[" + std::to_string(k) + "]") << ";\n"
+                    << "const double tmp = ck * cur_h;\nconst double y = tmp - comp;\nconst double t = res + y;\n"
+                    << "comp = (t - res) - y;\nres = t;\n";
+                if (k < order) {
+                    src << "cur_h = cur_h * h;\n";
+                }
+                src << "}\n";
+            }
+            src << xn << " = res;\n}\n";
+            upd.emplace_back(xn, "pk_v" + cs + "[0]", "pk_v" + cs + "[0]");
+            continue;
+        }
+        src << "double " << xn << ";\n";
+        if (dv != nullptr) {
+            src << "double " << xd << ";\n";
+        }
+        src << "{\n";
+        if (opts.high_accuracy) {
+            src << "double cprev = " << tail_val(tp.rows, 0, colp + "[0]") << ";\ndouble res = cprev, comp = 0.0, cur_h = h;\n";
+            if (dv != nullptr) {
+                src << "double resd = " << row0_r(*dv) << ", compd = 0.0;\n";
+            }
+            for (std::uint32_t k = 1; k <= order; ++k) {
+                src << "{\nconst double ck = " << tail_val(tp.rows, k, colp + "[" + std::to_string(k * kstride) + "]") << ";\n";
+                if (dv != nullptr) {
+                    src << "const double cd = cprev * " << fp_literal(1. / static_cast<double>(k)) << ";\n"
+                        << "const double tmpd = cd * cur_h;\nconst double yd = tmpd - compd;\n"
+                        << "const double td = resd + yd;\ncompd = (td - resd) - yd;\nresd = td;\n";
+                }
+                src << "const double tmp = ck * cur_h;\nconst double y = tmp - comp;\nconst double t = res + y;\n"
+                    << "comp = (t - res) - y;\nres = t;\ncprev = ck;\n";
+                if (k < order) {
+                    src << "cur_h = cur_h * h;\n";
+                }
+                src << "}\n";
+            }
+        } else {
+            // Horner from the highest order down: the derived series needs the column shifted by one.
+            src << "double res = " << colp << "[" << order * kstride << "];\n";
+            if (dv != nullptr) {
+                src << "double resd = " << colp << "[" << (order - 1u) * kstride << "] * "
+                    << fp_literal(1. / static_cast<double>(order)) << ";\n";
+            }
+            for (std::uint32_t k = 1; k <= order; ++k) {
+                const auto kk = order - k;
+                src << "res = " << colp << "[" << kk * kstride << "] + res * h;\n";
+            }
+            if (dv != nullptr) {
+                for (std::uint32_t k = 1; k <= order; ++k) {
+                    const auto kk = order - k;
+                    if (kk >= 1u) {
+                        src << "resd = (" << colp << "[" << (kk - 1u) * kstride << "] * "
+                            << fp_literal(1. / static_cast<double>(kk)) << ") + resd * h;\n";
                     } else {
-                        // Horner from the highest order down: the derived series needs the column shifted by one.
-                        src << "double res = " << colp << "[" << order * kstride << "];\n";
-                        if (dv != nullptr) {
-                            src << "double resd = " << colp << "[" << (order - 1u) * kstride << "] * "
-                                << fp_literal(1. / static_cast<double>(order)) << ";\n";
-                        }
-                        for (std::uint32_t k = 1; k <= order; ++k) {
-                            const auto kk = order - k;
-                            src << "res = " << colp << "[" << kk * kstride << "] + res * h;\n";
-                        }
-                        if (dv != nullptr) {
-                            for (std::uint32_t k = 1; k <= order; ++k) {
-                                const auto kk = order - k;
-                                if (kk >= 1u) {
-                                    src << "resd = (" << colp << "[" << (kk - 1u) * kstride << "] * "
-                                        << fp_literal(1. / static_cast<double>(kk)) << ") + resd * h;\n";
-                                } else {
-                                    src << "resd = " << row0_r(*dv) << " + resd * h;\n";
-                                }
-                            }
-                        }
-                    }
-                    src << xn << " = res;\n";
-                    if (dv != nullptr) {
-                        src << xd << " = resd;\n";
-                    }
-                    src << "}\n";
-                    // (Event equations inside the stepper: the order-0 rows stay what they were - the Taylor coefficients
-                    // leave through the cooperative store behind the step - and the new state waits in the slab, which is
-                    // dead between the last order and the next step.)
-                    const auto new_at = [&](const owner_slot &o) {
-                        return ev_inline ? ("slab[" + std::to_string(o.col * L) + "u + l]") : row0_w(o);
-                    };
-                    upd.emplace_back(xn, row0_r(ow), new_at(ow));
-                    if (dv != nullptr) {
-                        upd.emplace_back(xd, row0_r(*dv), new_at(*dv));
+                        src << "resd = " << row0_r(*dv) << " + resd * h;\n";
                     }
                 }
             }
         }
+        src << xn << " = res;\n";
+        if (dv != nullptr) {
+            src << xd << " = resd;\n";
+        }
+        src << "}\n";
+        // (Event equations inside the stepper: the order-0 rows stay what they were - the Taylor coefficients
+        // leave through the cooperative store behind the step - and the new state waits in the slab, which is
+        // dead between the last order and the next step.)
+        const auto new_at = [&](const owner_slot &o) {
+            return ev_inline ? ("slab[" + std::to_string(o.col * L) + "u + l]") : row0_w(o);
+        };
+        upd.emplace_back(xn, row0_r(ow), new_at(ow));
+        if (dv != nullptr) {
+            upd.emplace_back(xd, row0_r(*dv), new_at(*dv));
+        }
+    }
+    if (n_trd_used != n_trd) {
+        // (Every read issued ahead of the selector must be the one its series consumes.)
+        throw std::logic_error("hy_taylor (one lane per pair): " + std::to_string(n_trd - n_trd_used)
+                               + " jet reads of the final evaluation were issued ahead of the selector and not consumed");
     }
     for (std::uint32_t c = 0; !one_lane && c < n_hslots; ++c) {
         upd.emplace_back("xn" + std::to_string(c), "hc" + std::to_string(c) + "[0]", "hc" + std::to_string(c) + "[0]");
