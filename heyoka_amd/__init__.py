@@ -59,6 +59,8 @@ __all__ = [
     "device_count",
     "version",
     "native_event_counter",
+    "native_event_recorder",
+    "event_log",
 ]
 
 _builtin_sum = sum
@@ -869,6 +871,32 @@ class native_event_counter:
         return int(self._c.value)
 
 
+class native_event_recorder(native_event_counter):
+    """A callback which lives in the library (hy_event_recorder_nt / hy_event_recorder_t of the C ABI) and records its
+    invocations in the integrator's event log (``ta.event_log``): system, event, trigger time, direction and the state at
+    that instant - on the device when every event of the integrator has a library-side callback. ``.value``: the number
+    of invocations; as a terminal callback it always continues."""
+
+
+class event_log:
+    """The rows of an integrator's event log as arrays, in the order in which the callbacks would have been invoked:
+    ``system``, ``terminal`` (bool), ``idx`` (event index within its class), ``d_sgn``, ``time`` / ``time_lo`` (trigger
+    time, double-length), ``root`` (offset from the beginning of the step), ``abs_der`` (|d eq/dt| at the root), ``state``
+    of shape (n, dim) or None with the states switched off. ``rows``: the raw (n, 8 [+ dim]) array."""
+
+    def __init__(self, rows, with_states):
+        self.rows = rows
+        self.system = rows[:, 0].astype(np.int64)
+        self.terminal = rows[:, 1] == 0.0
+        self.idx = rows[:, 2].astype(np.int64)
+        self.d_sgn = rows[:, 3].astype(np.int64)
+        self.time, self.time_lo, self.root, self.abs_der = rows[:, 4], rows[:, 5], rows[:, 6], rows[:, 7]
+        self.state = rows[:, 8:] if with_states else None
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+
 class nt_event:
     """nt_event_batch<double> (include/heyoka/events.hpp): ``callback(ta, time, d_sgn, batch_idx)``."""
 
@@ -972,6 +1000,8 @@ class taylor_adaptive_batch:
         if t_events or nt_events:
             # C trampolines: look the Python integrator up by handle, record exceptions (re-raised after the C call).
             def make_nt(ev):
+                if isinstance(ev.callback, native_event_recorder):
+                    return ctypes.cast(lib.hy_event_recorder_nt, _lib.NT_EVENT_CB)
                 if isinstance(ev.callback, native_event_counter):
                     return ctypes.cast(lib.hy_event_counter_nt, _lib.NT_EVENT_CB)
 
@@ -987,6 +1017,8 @@ class taylor_adaptive_batch:
             def make_t(ev):
                 if ev.callback is None:
                     return ctypes.cast(None, _lib.T_EVENT_CB)
+                if isinstance(ev.callback, native_event_recorder):
+                    return ctypes.cast(lib.hy_event_recorder_t, _lib.T_EVENT_CB)
                 if isinstance(ev.callback, native_event_counter):
                     return ctypes.cast(lib.hy_event_counter_t, _lib.T_EVENT_CB)
 
@@ -1046,6 +1078,63 @@ class taylor_adaptive_batch:
         keys = ("steps", "ms_upload", "ms_stepper", "ms_detection", "ms_bookkeeping_flags", "ms_update_records",
                 "tc_regeneration_launches", "systems_with_events")
         return dict(zip(keys, [float(x) for x in out]))
+
+    # ---- event log (native_event_recorder) ----
+    @property
+    def event_log_size(self):
+        return int(lib.hy_tab_event_log_size(self._h))
+
+    @property
+    def event_log_row_size(self):
+        """Doubles per row: 8 + dim, or 8 with the states switched off."""
+        return int(lib.hy_tab_event_log_row_doubles(self._h))
+
+    @property
+    def event_log_capacity(self):
+        """Rows the device buffer of the log holds before it grows."""
+        return int(lib.hy_tab_event_log_capacity(self._h))
+
+    def get_event_log(self, first=0, count=None):
+        """Copy of the rows [first, first + count) of the event log (see ``event_log``)."""
+        n = self.event_log_size
+        count = n - int(first) if count is None else int(count)
+        rows = np.empty((max(count, 0), self.event_log_row_size))
+        raise_for(lib.hy_tab_get_event_log(self._h, int(first), count, rows.ctypes.data))
+        return event_log(rows, self.event_log_states)
+
+    @property
+    def event_log(self):
+        return self.get_event_log()
+
+    @property
+    def event_log_device(self):
+        """Zero-copy __cuda_array_interface__ view of the rows, shape (n, row size); valid until the next call which
+        steps or clears. None if the log is empty."""
+        ptr, n, w = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint32()
+        raise_for(lib.hy_tab_event_log_device(self._h, ctypes.byref(ptr), ctypes.byref(n), ctypes.byref(w)))
+        if not ptr.value:
+            return None
+        return _DeviceArray(ptr.value, (n.value, w.value), self)
+
+    def clear_event_log(self):
+        raise_for(lib.hy_tab_clear_event_log(self._h))
+
+    def event_log_reserve(self, rows):
+        raise_for(lib.hy_tab_event_log_reserve(self._h, int(rows)))
+
+    @property
+    def event_log_states(self):
+        return bool(lib.hy_tab_get_event_log_states(self._h))
+
+    @event_log_states.setter
+    def event_log_states(self, on):
+        raise_for(lib.hy_tab_set_event_log_states(self._h, 1 if on else 0))
+
+    def event_log_code_object(self, which):
+        """gfx950 code object of the event-log kernels: 0 row headers, 1 dense output over the rows."""
+        data, n = ctypes.c_void_p(), ctypes.c_size_t()
+        raise_for(lib.hy_tab_event_log_code_object(self._h, int(which), ctypes.byref(data), ctypes.byref(n)))
+        return ctypes.string_at(data.value, n.value)
 
     def reset_cooldowns(self, batch_idx=None):
         raise_for(lib.hy_tab_reset_cooldowns(self._h, -1 if batch_idx is None else int(batch_idx)))

@@ -178,6 +178,19 @@ SIGNATURES = [
     ("hy_tab_with_events", c_int, [c_void_p]),
     ("hy_event_counter_nt", None, [c_void_p, ctypes.c_double, c_int, ctypes.c_uint32, c_void_p]),
     ("hy_event_counter_t", c_int, [c_void_p, c_int, ctypes.c_uint32, c_void_p]),
+    ("hy_event_recorder_nt", None, [c_void_p, ctypes.c_double, c_int, ctypes.c_uint32, c_void_p]),
+    ("hy_event_recorder_t", c_int, [c_void_p, c_int, ctypes.c_uint32, c_void_p]),
+    ("hy_tab_event_log_size", ctypes.c_uint64, [c_void_p]),
+    ("hy_tab_event_log_row_doubles", ctypes.c_uint32, [c_void_p]),
+    ("hy_tab_event_log_capacity", ctypes.c_uint64, [c_void_p]),
+    ("hy_tab_get_event_log", c_int, [c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
+    ("hy_tab_event_log_device", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("hy_tab_clear_event_log", c_int, [c_void_p]),
+    ("hy_tab_event_log_reserve", c_int, [c_void_p, ctypes.c_uint64]),
+    ("hy_tab_set_event_log_states", c_int, [c_void_p, c_int]),
+    ("hy_tab_get_event_log_states", c_int, [c_void_p]),
+    ("hy_tab_event_log_code_object", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    ("hy_event_detection_source", c_void_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("hy_tab_set_event_timing", c_int, [c_void_p, c_int]),
     ("hy_tab_get_event_stats", c_int, [c_void_p, c_void_p]),
     ("hy_tab_reset_cooldowns", c_int, [c_void_p, ctypes.c_int64]),

@@ -772,6 +772,10 @@ hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state
                 if (cb == &hy_event_counter_t && user != nullptr) {
                     e.native_counter = static_cast<std::uint64_t *>(user);
                 }
+                if (cb == &hy_event_recorder_t) {
+                    e.recorder = true;
+                    e.native_counter = static_cast<std::uint64_t *>(user);
+                }
             }
             c.t_events.push_back(std::move(e));
         }
@@ -786,6 +790,10 @@ hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state
                     cb(static_cast<hy_tab>(ctx), tm, d_sgn, idx, user);
                 };
                 if (cb == &hy_event_counter_nt && user != nullptr) {
+                    e.native_counter = static_cast<std::uint64_t *>(user);
+                }
+                if (cb == &hy_event_recorder_nt) {
+                    e.recorder = true;
                     e.native_counter = static_cast<std::uint64_t *>(user);
                 }
             }
@@ -850,6 +858,79 @@ int hy_event_counter_t(hy_tab, int, uint32_t, void *user)
 {
     __atomic_fetch_add(static_cast<std::uint64_t *>(user), std::uint64_t(1), __ATOMIC_RELAXED);
     return 1;
+}
+
+// Native callbacks which record: the row of the event log is written by the step itself (the callback is recognised by its
+// address); what is left to do here is the optional count.
+void hy_event_recorder_nt(hy_tab, double, int, uint32_t, void *user)
+{
+    if (user != nullptr) {
+        __atomic_fetch_add(static_cast<std::uint64_t *>(user), std::uint64_t(1), __ATOMIC_RELAXED);
+    }
+}
+int hy_event_recorder_t(hy_tab, int, uint32_t, void *user)
+{
+    if (user != nullptr) {
+        __atomic_fetch_add(static_cast<std::uint64_t *>(user), std::uint64_t(1), __ATOMIC_RELAXED);
+    }
+    return 1;
+}
+uint64_t hy_tab_event_log_size(hy_tab t)
+{
+    return t->core.get_event_log_size();
+}
+uint32_t hy_tab_event_log_row_doubles(hy_tab t)
+{
+    return t->core.get_event_log_row_size();
+}
+uint64_t hy_tab_event_log_capacity(hy_tab t)
+{
+    return t->core.get_event_log_capacity();
+}
+int hy_tab_get_event_log(hy_tab t, uint64_t first, uint64_t count, double *out)
+{
+    return guarded([&] { t->core.get_event_log(first, count, out); });
+}
+int hy_tab_event_log_device(hy_tab t, const double **rows, uint64_t *n_rows, uint32_t *row_doubles)
+{
+    return guarded([&] {
+        *rows = t->core.event_log_device();
+        *n_rows = t->core.get_event_log_size();
+        *row_doubles = t->core.get_event_log_row_size();
+    });
+}
+int hy_tab_clear_event_log(hy_tab t)
+{
+    return guarded([&] { t->core.clear_event_log(); });
+}
+int hy_tab_event_log_reserve(hy_tab t, uint64_t rows)
+{
+    return guarded([&] { t->core.event_log_reserve(rows); });
+}
+int hy_tab_set_event_log_states(hy_tab t, int on)
+{
+    return guarded([&] { t->core.set_event_log_states(on != 0); });
+}
+int hy_tab_get_event_log_states(hy_tab t)
+{
+    return t->core.get_event_log_states() ? 1 : 0;
+}
+int hy_tab_event_log_code_object(hy_tab t, int which, const char **data, size_t *size)
+{
+    return guarded([&] {
+        const auto &co = t->core.event_log_code_object(which);
+        *data = co.data();
+        *size = co.size();
+    });
+}
+char *hy_event_detection_source(uint32_t order, uint32_t n_t_events, uint32_t n_nt_events)
+{
+    try {
+        return dup_str(detail::make_event_detection_source(order, detail::ed_max_detected(order, n_t_events, n_nt_events)));
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
 }
 
 // Logger (include/heyoka/logging.hpp:19-24): level 0 trace ... 5 critical, 6 off; default 3 (warn). A sink of the caller's
@@ -1261,6 +1342,7 @@ int hy_compile_aux_kernels(uint32_t order, uint32_t dim, int high_accuracy)
         hiprtc_compile_source(detail::make_cout_source(order, dim, high_accuracy != 0));
         hiprtc_compile_source(detail::make_grid_source(order, dim, high_accuracy != 0));
         hiprtc_compile_source(detail::make_event_detection_source(order, detail::ed_max_detected(order, 1, 1)));
+        hiprtc_compile_source(detail::make_event_recorder_source(detail::ed_max_detected(order, 1, 1)));
     });
 }
 hy_cfunc hy_cfunc_new(const hy_expr *fn, size_t n_fn, const hy_expr *vars, size_t n_vars, int device)

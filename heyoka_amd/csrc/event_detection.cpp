@@ -668,4 +668,160 @@ extern "C" __global__ void __launch_bounds__(256) hy_copy_arrays(const hy_copy_a
     return src.str();
 }
 
+std::string make_event_recorder_source(std::uint32_t max_detected)
+{
+    std::ostringstream src;
+    src << emit_detail::prelude;
+    src << "#define HY_MAXD " << max_detected << "u\n";
+    src << R"HIP(
+struct hy_evr_args {
+    const double *ed_out;
+    const unsigned *counts;
+    const double *dout_h;
+    const double *time_hi, *time_lo;
+    const i64 *outcome;
+    const int *is_rec;
+    unsigned *lane_rows;
+    u64 *blk;
+    u64 *total;
+    double *rows;
+    u64 N;
+    unsigned n_te, n_nte, row_doubles, pad;
+};
+
+// Does the c-th detected non-terminal event of the lane get a row? Its callback records, and it triggers before the
+// lane's first terminal event (the step ends there: |root| < |h|, src/taylor_adaptive_batch.cpp:837-871).
+__device__ __forceinline__ bool hy_evr_nt_row(const hy_evr_args &a, const double *nte, unsigned c, unsigned c_te, double h)
+{
+    return a.is_rec[a.n_te + (unsigned)nte[c * 4u]] != 0 && (c_te == 0u || fabs(nte[c * 4u + 1u]) < fabs(h));
+}
+
+// Rows of lane j in this step: the callbacks the host loop would have run for it which are recording callbacks. first:
+// the lane's first terminal event (smallest |root|, the earliest detected among equals: hy_ev_native); n_nt: the rows of
+// non-terminal events.
+__device__ unsigned hy_evr_lane(const hy_evr_args &a, u64 j, unsigned &first, unsigned &n_nt)
+{
+    const u64 N = a.N;
+    const unsigned c_te = a.counts[j], c_nte = a.counts[N + j];
+    first = 0u;
+    n_nt = 0u;
+    if (c_te + c_nte == 0u || a.outcome[j] == HY_OC_ERR_NF_STATE) return 0u;
+    const double h = a.dout_h[j];
+    const double *te = a.ed_out + (j * HY_MAXD) * 4u;
+    const double *nte = a.ed_out + ((N + j) * HY_MAXD) * 4u;
+    for (unsigned c = 1; c < c_te; ++c) {
+        if (fabs(te[c * 4u + 1u]) < fabs(te[first * 4u + 1u])) first = c;
+    }
+    for (unsigned c = 0; c < c_nte; ++c) {
+        if (hy_evr_nt_row(a, nte, c, c_te, h)) ++n_nt;
+    }
+    return n_nt + ((c_te != 0u && a.is_rec[(unsigned)te[first * 4u]] != 0) ? 1u : 0u);
+}
+
+// Rows per lane and their sum per workgroup of 256 lanes.
+extern "C" __global__ void __launch_bounds__(256) hy_evr_count(const hy_evr_args a)
+{
+    __shared__ unsigned ws[4];
+    const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
+    unsigned first, n_nt;
+    const unsigned r = (j < a.N) ? hy_evr_lane(a, j, first, n_nt) : 0u;
+    if (j < a.N) a.lane_rows[j] = r;
+    unsigned s = r;
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if ((threadIdx.x & 63u) == 0u) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0u) a.blk[blockIdx.x] = (u64)ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// Inclusive scan of one value per thread over the workgroup of 256 (Hillis-Steele in LDS).
+template <typename T>
+__device__ __forceinline__ T hy_evr_scan256(T *sh, T v)
+{
+    const unsigned t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (unsigned d = 1; d < 256u; d <<= 1) {
+        const T x = (t >= d) ? sh[t - d] : (T)0;
+        __syncthreads();
+        sh[t] += x;
+        __syncthreads();
+    }
+    return sh[t];
+}
+
+// Exclusive scan of the workgroup sums, in place: ONE workgroup which walks them 256 at a time and carries the running
+// total from pass to pass (65 536 lanes per pass) - nothing waits for another workgroup. total[0]: rows of the step.
+extern "C" __global__ void __launch_bounds__(256) hy_evr_scan(const hy_evr_args a)
+{
+    __shared__ u64 sh[256];
+    const u64 nb = (a.N + 255u) / 256u;
+    u64 carry = 0;
+    for (u64 base = 0; base < nb; base += 256u) {
+        const u64 i = base + threadIdx.x;
+        const u64 v = (i < nb) ? a.blk[i] : 0ull;
+        const u64 incl = hy_evr_scan256(sh, v);
+        if (i < nb) a.blk[i] = carry + (incl - v);
+        carry += sh[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) a.total[0] = carry;
+}
+
+__device__ __forceinline__ void hy_evr_header(double *row, u64 j, unsigned cls, const double *ev, hy_df t0)
+{
+    hy_df r;
+    r.hi = ev[1];
+    r.lo = 0.0;
+    // (Trigger time: new_time - h + root in double-length arithmetic, the value the host loop hands to a callback.)
+    const hy_df tt = hy_df_add(t0, r);
+    row[0] = (double)j;
+    row[1] = (double)cls;
+    row[2] = ev[0];
+    row[3] = ev[2];
+    row[4] = tt.hi;
+    row[5] = tt.lo;
+    row[6] = ev[1];
+    row[7] = ev[3];
+}
+
+// Row headers of the step, in batch order; within a lane the non-terminal events by ascending |root| (stable in
+// detection order, like the sort of src/detail/event_detection.cpp:771-781), then the first terminal event.
+extern "C" __global__ void __launch_bounds__(256) hy_evr_write(const hy_evr_args a)
+{
+    __shared__ unsigned sh[256];
+    const u64 N = a.N;
+    const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
+    const unsigned r = (j < N) ? a.lane_rows[j] : 0u;
+    const unsigned incl = hy_evr_scan256(sh, r);
+    if (r == 0u) return;
+    const u64 off = a.blk[blockIdx.x] + (u64)(incl - r);
+    unsigned first, n_nt;
+    hy_evr_lane(a, j, first, n_nt);
+    const unsigned c_te = a.counts[j], c_nte = a.counts[N + j];
+    const double h = a.dout_h[j];
+    const double *te = a.ed_out + (j * HY_MAXD) * 4u;
+    const double *nte = a.ed_out + ((N + j) * HY_MAXD) * 4u;
+    hy_df nt, hh;
+    nt.hi = a.time_hi[j];
+    nt.lo = a.time_lo[j];
+    hh.hi = h;
+    hh.lo = 0.0;
+    const hy_df t0 = hy_df_sub(nt, hh);
+    for (unsigned c = 0; c < c_nte; ++c) {
+        if (!hy_evr_nt_row(a, nte, c, c_te, h)) continue;
+        const double ar = fabs(nte[c * 4u + 1u]);
+        unsigned rank = 0;
+        for (unsigned q = 0; q < c_nte; ++q) {
+            if (q == c || !hy_evr_nt_row(a, nte, q, c_te, h)) continue;
+            const double aq = fabs(nte[q * 4u + 1u]);
+            if (aq < ar || (aq == ar && q < c)) ++rank;
+        }
+        hy_evr_header(a.rows + (off + rank) * a.row_doubles, j, 1u, nte + c * 4u, t0);
+    }
+    if (r != n_nt) hy_evr_header(a.rows + (off + n_nt) * a.row_doubles, j, 0u, te + first * 4u, t0);
+}
+)HIP";
+    return src.str();
+}
+
 } // namespace heyoka_amd::detail

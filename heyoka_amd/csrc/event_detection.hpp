@@ -52,6 +52,8 @@ struct core_nt_event {
     event_direction dir = event_direction::any;
     // (See core_t_event::native_counter: hy_event_counter_nt.)
     std::uint64_t *native_counter = nullptr;
+    // (See core_t_event::recorder: hy_event_recorder_nt.)
+    bool recorder = false;
 };
 
 struct core_t_event {
@@ -62,6 +64,10 @@ struct core_t_event {
     // The callback is the library's own counting callback (hy_event_counter_t of the C ABI: increments *counter and lets
     // the integration continue): nothing of the caller's runs, so the step applies it on the device.
     std::uint64_t *native_counter = nullptr;
+    // The callback is the library's recording callback (hy_event_recorder_t of the C ABI, the tag event_recorder of the
+    // C++ interface): every invocation appends a row to the integrator's event log (see event_log_header) and lets the
+    // integration continue; native_counter, if set, is incremented as by the counting callback.
+    bool recorder = false;
 };
 
 // One detected event of a lane: (event index, root (time from the beginning of the step), sign of the time
@@ -143,6 +149,34 @@ struct ep_kargs {
     int native;
     unsigned long long *ev_counts;
     const double *te_cd;
+};
+
+// ---- event log (library-side recording callbacks, core_*_event::recorder) ----
+// A row of the log: event_log_header doubles (system, class - 0 terminal / 1 non-terminal -, event index within the
+// class, d_sgn, trigger time hi, trigger time lo, root, |d eq/dt| at the root), then - unless the states are switched
+// off - the dim state variables at the trigger time.
+inline constexpr std::uint32_t event_log_header = 8;
+
+// HIP source of the kernels which turn the detected events of one step into the row headers of the log, in the order in
+// which the host loop would have invoked the callbacks: hy_evr_count (rows per lane + sums per workgroup of 256 lanes),
+// hy_evr_scan (one workgroup: exclusive scan of the workgroup sums, in as many passes of 256 as it takes), hy_evr_write
+// (in-workgroup scan, sort of the lane's events, headers). A module of its own: the event-detection module of an
+// integrator without recorders is not touched.
+std::string make_event_recorder_source(std::uint32_t max_detected);
+
+struct evr_kargs {
+    const double *ed_out;      // as ed_kargs::out
+    const unsigned *counts;    // as ed_kargs::counts
+    const double *dout_h;      // [N] final step sizes
+    const double *time_hi, *time_lo; // [N] after hy_ev_post
+    const long long *outcome;  // [N] after hy_ev_post / hy_ev_native
+    const int *is_rec;         // [n_te + n_nte] != 0: the event has a recording callback (terminal events first)
+    unsigned *lane_rows;       // [N] rows of the lane in this step
+    unsigned long long *blk;   // [ceil(N / 256)] sums per workgroup, then (after hy_evr_scan) their exclusive scan
+    unsigned long long *total; // [0] rows of this step
+    double *rows;              // first new row of the log
+    unsigned long long N;
+    unsigned n_te, n_nte, row_doubles, pad;
 };
 
 } // namespace detail

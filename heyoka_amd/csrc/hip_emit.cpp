@@ -1190,6 +1190,97 @@ emitted_module emit_event_jets(const taylor_program &p, const emit_options &opts
     return ret;
 }
 
+// The dense-output kernel of the event log (see hip_emit.hpp). One thread per row: the coefficient columns of the row's
+// system are read at stride N - uncoalesced, but the rows are few against N * dim * (order + 1).
+std::string make_event_log_dout_source(const taylor_program &p, const emit_options &opts)
+{
+    const auto n_eq = p.n_eq;
+    const auto order = opts.order;
+    std::ostringstream os;
+    os << emit_detail::prelude;
+    // n_rows != nullptr: the number of rows of the step is read from the device (written by hy_evr_scan), n_max bounds it.
+    os << "struct hy_drow_args { double *rows; const double *tc; const double *state; const u64 *n_rows; u64 n_max; u64 N; "
+          "unsigned row_doubles, pad; };\n";
+    const auto derived = [&](std::uint32_t i) {
+        return opts.compact_tc && p.sv_defs[i].type == operand::kind::uvar && p.sv_defs[i].idx < n_eq;
+    };
+    if (opts.compact_tc) {
+        // (The tables and the uncontracted product of hy_dout_c.)
+        os << "__device__ __forceinline__ double hy_mul_nc(double x, double y)\n{\n    double t = x * y;\n"
+              "    asm(\"\" : \"+v\"(t));\n    return t;\n}\n";
+        os << "__constant__ double hy_rk_c[" << (order + 1u) << "] = {0.0";
+        for (std::uint32_t k = 1; k <= order; ++k) {
+            os << "," << fp_literal(opts.exact_division ? static_cast<double>(k) : 1. / static_cast<double>(k));
+        }
+        os << "};\n__constant__ int hy_tc_parent[" << n_eq << "] = {";
+        for (std::uint32_t i = 0; i < n_eq; ++i) {
+            os << (derived(i) ? static_cast<long long>(p.sv_defs[i].idx) : -1ll) << ",";
+        }
+        os << "};\n__constant__ int hy_tc_child[" << n_eq << "] = {";
+        for (std::uint32_t j = 0; j < n_eq; ++j) {
+            long long child = -1;
+            for (std::uint32_t i = 0; i < n_eq; ++i) {
+                if (derived(i) && p.sv_defs[i].idx == j) {
+                    child = static_cast<long long>(i);
+                }
+            }
+            os << child << ",";
+        }
+        os << "};\n";
+    }
+    os << "extern \"C\" __global__ void __launch_bounds__(256) hy_dout_rows(const hy_drow_args a)\n{\n";
+    os << "const u64 N = a.N;\nconst u64 r = (u64)blockIdx.x * 256u + threadIdx.x;\n";
+    os << "u64 n = a.n_max;\nif (a.n_rows != nullptr && a.n_rows[0] < n) n = a.n_rows[0];\nif (r >= n) return;\n";
+    os << "double *row = a.rows + r * a.row_doubles;\nconst u64 s = (u64)row[0];\nif (s >= N) return;\n";
+    os << "double *out = row + 8;\n";
+    // (Terminal event: the step was truncated at the event, the state after the step is the state at the event.)
+    os << "if (row[1] == 0.0) {\nfor (unsigned i = 0; i < " << n_eq << "u; ++i) out[i] = a.state[(u64)i * N + s];\nreturn;\n}\n";
+    os << "const double h = row[6];\n";
+    if (opts.compact_tc) {
+        const std::string xk = opts.exact_division ? "(ck / hy_rk_c[k + 1u])" : "hy_mul_nc(ck, hy_rk_c[k + 1u])";
+        os << "for (unsigned j = 0; j < " << n_eq << "u; ++j) {\n";
+        os << "if (hy_tc_parent[j] >= 0) continue;\n";
+        os << "const int ch = hy_tc_child[j];\n";
+        os << "const double *c = a.tc + ((u64)j * " << (order + 1u) << "u) * N + s;\n";
+        os << "const double x0 = (ch >= 0) ? a.tc[((u64)(unsigned)(ch < 0 ? 0 : ch) * " << (order + 1u) << "u) * N + s] : 0.0;\n";
+        if (opts.high_accuracy) {
+            os << "double ck = c[0];\n";
+            os << "double rv = ck, cv = 0.0, rx = x0, cx = 0.0, cur_h = h;\n";
+            os << "for (unsigned k = 0; k < " << order << "u; ++k) {\n";
+            os << "{\nconst double tmp = " << xk << " * cur_h;\nconst double y = tmp - cx;\nconst double t = rx + y;\n";
+            os << "cx = (t - rx) - y;\nrx = t;\n}\n";
+            os << "ck = c[(u64)(k + 1u) * N];\n";
+            os << "{\nconst double tmp = ck * cur_h;\nconst double y = tmp - cv;\nconst double t = rv + y;\n";
+            os << "cv = (t - rv) - y;\nrv = t;\n}\n";
+            os << "cur_h = cur_h * h;\n}\n";
+        } else {
+            os << "double ck = c[(u64)" << order << "u * N];\ndouble rv = ck, rx = 0.0;\n";
+            os << "for (unsigned k = " << order - 1u << "u;; --k) {\n";
+            os << "ck = c[(u64)k * N];\nrv = ck + rv * h;\n";
+            os << "rx = (k == " << order - 1u << "u) ? " << xk << " : (" << xk << " + rx * h);\n";
+            os << "if (k == 0u) break;\n}\n";
+            os << "rx = x0 + rx * h;\n";
+        }
+        os << "out[j] = rv;\n";
+        os << "if (ch >= 0) out[(unsigned)ch] = rx;\n}\n}\n";
+    } else {
+        os << "for (unsigned i = 0; i < " << n_eq << "u; ++i) {\n";
+        os << "const double *c = a.tc + ((u64)i * " << (order + 1u) << "u) * N + s;\n";
+        if (opts.high_accuracy) {
+            os << "double res = c[0], comp = 0.0, cur_h = h;\n";
+            os << "for (unsigned k = 1; k <= " << order << "u; ++k) {\n";
+            os << "const double tmp = c[(u64)k * N] * cur_h;\nconst double y = tmp - comp;\nconst double t = res + y;\n";
+            os << "comp = (t - res) - y;\nres = t;\ncur_h = cur_h * h;\n}\n";
+        } else {
+            os << "double res = c[(u64)" << order << "u * N];\n";
+            os << "for (unsigned k = 1; k <= " << order << "u; ++k) {\n";
+            os << "res = c[(u64)(" << order << "u - k) * N] + res * h;\n}\n";
+        }
+        os << "out[i] = res;\n}\n}\n";
+    }
+    return os.str();
+}
+
 bool emit_event_jets_inline(const taylor_program &p, const emit_options &opts,
                             const std::function<std::string(std::uint32_t, std::uint32_t)> &sv,
                             const std::function<std::string(std::uint32_t, std::uint32_t, const std::string &)> &ev_store,

@@ -206,6 +206,13 @@ emitted_module emit_hip_module(const taylor_program &prog, const emit_options &o
 // (and the reason in why_not) when the event equations need too much of the decomposition.
 emitted_module emit_event_jets(const taylor_program &prog, const emit_options &opts, std::string &why_not);
 
+// Dense output over the ROWS of the event log (event_detection.hpp): hy_dout_rows evaluates the Taylor coefficients of
+// the row's system at the row's root and fills the state columns of the row, with the operations and the operation
+// order of hy_dout (full coefficients) or - emit_options::compact_tc - of hy_dout_c (the rows of the variables defined
+// by another state variable are derived: x^[k] = v^[k-1] / k); rows of terminal events copy the state after the step.
+// A module of its own, compiled only for integrators with recording callbacks.
+std::string make_event_log_dout_source(const taylor_program &prog, const emit_options &opts);
+
 // The same computation as straight-line statements for use INSIDE a stepper (the one-lane-per-pair kernel in mode 4): sv(i, k)
 // gives the expression of the order-k coefficient of state variable i (every use of a coefficient goes through ONE
 // definition: one LDS read), ev_store(event, k, value) the statement which publishes a coefficient of an event equation.

@@ -263,6 +263,46 @@ struct tab_core::impl {
     mutable bool ev_native = false;
     // (Page-locked landing area of the event records of a step: see pinned_buffer.)
     mutable pinned_buffer h_ev_rec;
+    // ---- event log (core_*_event::recorder, see event_detection.hpp) ----
+    // Rows of log_row_doubles() doubles in d_ev_log, log_rows of them valid; the buffer grows geometrically (device-to-device
+    // copy) before the kernels of a step write to it. log_stash: the rows while the integrator moves between devices.
+    bool ev_has_rec = false, log_states = true;
+    std::shared_ptr<const compiled_module> evr_cmod, drow_cmod;
+    mutable std::unique_ptr<aux_module> evr_mod, drow_mod;
+    mutable device_buffer d_ev_log, d_evr_isrec, d_evr_lane, d_evr_blk;
+    mutable std::uint64_t log_rows = 0, log_reserved = 0;
+    mutable std::vector<double> log_stash;
+    [[nodiscard]] std::uint32_t log_row_doubles() const
+    {
+        return event_log_header + (log_states ? dim : 0u);
+    }
+    [[nodiscard]] std::uint64_t log_capacity() const
+    {
+        return d_ev_log.bytes() / (log_row_doubles() * sizeof(double));
+    }
+    void log_grow(std::uint64_t rows) const
+    {
+        const auto rb = log_row_doubles() * sizeof(double);
+        if (!log_stash.empty()) {
+            // (Rows which came from another device.)
+            auto st = std::move(log_stash);
+            log_stash.clear();
+            log_grow(std::max<std::uint64_t>(rows, st.size() * sizeof(double) / rb));
+            device_copy(d_ev_log.get(), st.data(), st.size() * sizeof(double), device, stream);
+            stream_synchronize(device, stream);
+        }
+        if (rows <= log_capacity()) {
+            return;
+        }
+        const auto cap = std::max({rows, 2u * log_capacity(), log_reserved, std::uint64_t(1024)});
+        device_buffer nb(static_cast<std::size_t>(cap) * rb, device);
+        if (d_ev_log.bytes() != 0u) {
+            device_copy(nb.get(), d_ev_log.get(), static_cast<std::size_t>(log_rows) * rb, device, stream);
+        }
+        // (The old buffer is released once the copy has run: the release waits for the device.)
+        d_ev_log = std::move(nb);
+    }
+    void log_fill_states(std::uint64_t first_row, const unsigned long long *d_n_rows, std::uint64_t n_max) const;
     [[nodiscard]] bool is_cluster() const
     {
         // NOTE: true whenever the stepper does not need the tc buffer as its jet scratch (cluster / table
@@ -765,6 +805,21 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
     detail::log_message(log_level::trace, "Taylor batch hiprtc compilation runtime: " + sw_jit.str() + " ("
                                               + std::to_string(d.emitted.source.size()) + " bytes of HIP source)");
 
+    for (const auto &ev : d.tes) {
+        d.ev_has_rec = d.ev_has_rec || ev.recorder;
+    }
+    for (const auto &ev : d.ntes) {
+        d.ev_has_rec = d.ev_has_rec || ev.recorder;
+    }
+    if (d.ev_has_rec) {
+        // Recording callbacks: the kernels of the event log, in modules of their own.
+        auto eo_log = eo;
+        eo_log.compact_tc = d.cluster_events && d.emitted.compact_tc;
+        d.drow_cmod = hiprtc_compile_source(make_event_log_dout_source(d.prog, eo_log));
+        d.evr_cmod = hiprtc_compile_source(make_event_recorder_source(
+            ed_max_detected(d.order, static_cast<std::uint32_t>(d.tes.size()), static_cast<std::uint32_t>(d.ntes.size()))));
+    }
+
     d.sys = std::move(sys);
     d.last_h.assign(d.N, 0.);
     d.d_out.assign(static_cast<std::size_t>(d.dim) * d.N, 0.);
@@ -817,6 +872,11 @@ tab_core::tab_core(const tab_core &o) : m_impl(o.m_impl ? std::make_unique<impl>
     d.cluster_events = s.cluster_events;
     d.ev_emitted = s.ev_emitted;
     d.ev_cmod = s.ev_cmod;
+    // (The copy starts with an empty event log.)
+    d.ev_has_rec = s.ev_has_rec;
+    d.log_states = s.log_states;
+    d.evr_cmod = s.evr_cmod;
+    d.drow_cmod = s.drow_cmod;
     d.state = s.state;
     d.pars = s.pars;
     d.time_hi = s.time_hi;
@@ -1345,15 +1405,29 @@ void tab_core::impl::ensure_event_buffers()
         ed_slots = std::min<std::uint64_t>((static_cast<std::uint64_t>(n) + 63u) / 64u * 64u, max_slots);
         d_ed_wl = device_buffer(static_cast<std::size_t>(ed_slots) * per_slot, device);
         d_ev_cursor = device_buffer(4u * sizeof(unsigned long long), device);
-        // Library-side counting callbacks only (core_*_event::native_counter): the events are applied on the device.
+        // Library-side callbacks only - counting (core_*_event::native_counter) or recording (core_*_event::recorder): the
+        // events are applied on the device.
         ev_native = true;
         std::vector<double> te_cd;
+        std::vector<int> is_rec;
         for (const auto &ev : tes) {
-            ev_native = ev_native && ev.native_counter != nullptr;
+            ev_native = ev_native && (ev.native_counter != nullptr || ev.recorder);
             te_cd.push_back(ev.cooldown);
+            is_rec.push_back(ev.recorder ? 1 : 0);
         }
         for (const auto &ev : ntes) {
-            ev_native = ev_native && ev.native_counter != nullptr;
+            ev_native = ev_native && (ev.native_counter != nullptr || ev.recorder);
+            is_rec.push_back(ev.recorder ? 1 : 0);
+        }
+        if (ev_has_rec) {
+            drow_mod = std::make_unique<aux_module>(drow_cmod, device);
+        }
+        if (ev_native && ev_has_rec) {
+            evr_mod = std::make_unique<aux_module>(evr_cmod, device);
+            d_evr_isrec = device_buffer(is_rec.size() * sizeof(int), device);
+            d_evr_isrec.upload(is_rec.data(), is_rec.size() * sizeof(int), stream);
+            d_evr_lane = device_buffer(n * sizeof(unsigned), device);
+            d_evr_blk = device_buffer(((n + 255u) / 256u) * sizeof(unsigned long long), device);
         }
         if (ev_native) {
             d_ev_counts = device_buffer((tes.size() + ntes.size()) * sizeof(unsigned long long), device);
@@ -1398,7 +1472,10 @@ void tab_core::impl::launch_event_stepper(const std::vector<double> *lims)
     a.pad = 1;
     if (cluster_events && emitted.events_in_stepper) {
         tc_partial = false; // (nobody asked for the coefficients of the previous step: this step replaces them)
-        const bool all_now = ev_all_tc || tc_regenerated;
+        // (The state columns of the event log are evaluated from the coefficients of every lane with a recorded event. The
+        // stepper stores them on demand only where a TERMINAL event is possible - where a step may be truncated -, which
+        // does not cover the non-terminal events: with recording callbacks and the states on, every step stores them all.)
+        const bool all_now = ev_all_tc || tc_regenerated || (ev_has_rec && log_states);
         tc_regenerated = false;
         if (!all_now) {
             if (evs_state.bytes() == 0u) {
@@ -1458,6 +1535,22 @@ unsigned tab_core::impl::launch_event_detection(bool device_g_eps)
                       (cluster_events && emitted.events_in_stepper) ? d_selnorms.as<double>() : nullptr};
     ed_mod->launch("hy_detect_events", ed_slots, 64, &ea, sizeof(ea), stream);
     return 0;
+}
+
+// State columns of n_max rows of the log from first_row on (*d_n_rows of them, if given): dense output of the Taylor
+// coefficients of the step at the roots (hy_dout_rows, hip_emit.hpp).
+void tab_core::impl::log_fill_states(std::uint64_t first_row, const unsigned long long *d_n_rows, std::uint64_t n_max) const
+{
+    const struct {
+        double *rows;
+        const double *tc;
+        const double *state;
+        const unsigned long long *n_rows;
+        unsigned long long n_max, N;
+        unsigned row_doubles, pad;
+    } da{d_ev_log.as<double>() + first_row * log_row_doubles(), d_tc.as<double>(), d_state.as<double>(), d_n_rows, n_max, N,
+         log_row_doubles(), 0u};
+    drow_mod->launch("hy_dout_rows", n_max, 256, &da, sizeof(da), stream);
 }
 
 void tab_core::impl::step_with_events(const std::vector<double> &lims, bool wtc)
@@ -1597,6 +1690,12 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
         d_ev_rec = device_buffer(static_cast<std::size_t>(cur[0] + cur[0] / 2u + 1024u) * dsz, device);
     }
     pa.rec = d_ev_rec.as<double>();
+    // Recording callbacks applied on the device: the cursor of hy_ev_pre bounds the rows of this step (4 of its doubles per
+    // detected event, 8 more per lane with events); the log grows now, before anything writes to it.
+    const std::uint64_t log_ub = (ev_native && ev_has_rec) ? cur[0] / 4u : 0u;
+    if (log_ub != 0u) {
+        log_grow(log_rows + log_ub);
+    }
 
     // State update via dense output at the final step sizes (:781), then times / non-finite check / cooldowns /
     // outcomes / records.
@@ -1631,6 +1730,33 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
     if (ev_native && cur[0] != 0u) {
         ed_mod->launch("hy_ev_native", N, 256, &pa, sizeof(pa), stream);
     }
+    if (log_ub != 0u) {
+        // Rows of the log from the events of this step (event_detection.hpp): rows per lane and per workgroup, exclusive
+        // scan of the workgroup sums (the total lands in the spare word of the cursor, which the host reads anyway), row
+        // headers in batch order, state columns by dense output over the rows.
+        evr_kargs ra{};
+        ra.ed_out = d_ed_out.as<double>();
+        ra.counts = d_ed_counts.as<unsigned>();
+        ra.dout_h = d_douth.as<double>();
+        ra.time_hi = d_thi.as<double>();
+        ra.time_lo = d_tlo.as<double>();
+        ra.outcome = d_outcome.as<long long>();
+        ra.is_rec = d_evr_isrec.as<int>();
+        ra.lane_rows = d_evr_lane.as<unsigned>();
+        ra.blk = d_evr_blk.as<unsigned long long>();
+        ra.total = d_ev_cursor.as<unsigned long long>() + 3;
+        ra.rows = d_ev_log.as<double>() + log_rows * log_row_doubles();
+        ra.N = N;
+        ra.n_te = n_te;
+        ra.n_nte = n_nte;
+        ra.row_doubles = log_row_doubles();
+        evr_mod->launch("hy_evr_count", N, 256, &ra, sizeof(ra), stream);
+        evr_mod->launch("hy_evr_scan", 256, 256, &ra, sizeof(ra), stream);
+        evr_mod->launch("hy_evr_write", N, 256, &ra, sizeof(ra), stream);
+        if (log_states) {
+            log_fill_states(log_rows, ra.total, log_ub);
+        }
+    }
     const double *rec = nullptr;
     std::size_t rec_size = 0;
     if (ev_native) {
@@ -1643,12 +1769,18 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
             d_ev_counts.download(cnts.data(), cnts.size() * sizeof(unsigned long long), stream);
             d_ev_cursor.download(cur, sizeof(cur), stream);
             ev_systems += cur[2];
+            if (log_ub != 0u) {
+                log_rows += cur[3];
+            }
         } else {
             stream_synchronize(device, stream);
         }
         for (std::size_t e = 0; e < cnts.size(); ++e) {
             auto *ctr = e < tes.size() ? tes[e].native_counter : ntes[e - tes.size()].native_counter;
-            __atomic_fetch_add(ctr, static_cast<std::uint64_t>(cnts[e]), __ATOMIC_RELAXED);
+            // (A recording callback may come without a counter.)
+            if (ctr != nullptr) {
+                __atomic_fetch_add(ctr, static_cast<std::uint64_t>(cnts[e]), __ATOMIC_RELAXED);
+            }
         }
         lap("dout + post + records");
         host_newer = false;
@@ -1701,6 +1833,14 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
     upd_cd.clear();
     std::vector<double> upd_oc;
     const auto gen = time_gen;
+    // Row headers of the recording callbacks among the host callbacks: collected where the callback runs, i.e. in the
+    // order of the log.
+    std::vector<double> log_hdrs;
+    const auto log_header = [&](std::uint32_t lane, int cls, const detected_event &ev, const dfloat &new_time, double h) {
+        const auto tt = new_time - h + ev.root;
+        log_hdrs.insert(log_hdrs.end(), {static_cast<double>(lane), static_cast<double>(cls), static_cast<double>(ev.idx),
+                                         static_cast<double>(ev.d_sgn), tt.hi, tt.lo, ev.root, ev.abs_der});
+    };
     for (const auto &ref : refs) {
         {
             const auto *r = rec + ref.off;
@@ -1748,6 +1888,9 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
                 nt_cb_exception = true;
                 break;
             }
+            if (ntes[ev.idx].recorder) {
+                log_header(i, 1, ev, new_time, h);
+            }
         }
         if (nt_cb_exception || lr.tes.empty()) {
             continue;
@@ -1778,6 +1921,9 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
                 continue;
             }
         }
+        if (te.recorder) {
+            log_header(i, 0, ev, new_time, h);
+        }
         const auto ev_idx = static_cast<std::int64_t>(ev.idx);
         upd_oc.insert(upd_oc.end(), {static_cast<double>(i), static_cast<double>(te_cb_ret ? ev_idx : (-ev_idx - 1))});
     }
@@ -1797,6 +1943,22 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
         stream_synchronize(device, stream);
     }
     pending_cd.clear();
+    if (!log_hdrs.empty()) {
+        // Behind the existing rows: the headers (state columns zeroed), then the dense-output kernel of the device path.
+        const auto w = log_row_doubles();
+        const std::uint64_t n_new = log_hdrs.size() / event_log_header;
+        log_grow(log_rows + n_new);
+        std::vector<double> rows_h(static_cast<std::size_t>(n_new) * w, 0.);
+        for (std::uint64_t r = 0; r < n_new; ++r) {
+            std::copy_n(log_hdrs.data() + r * event_log_header, event_log_header, rows_h.data() + r * w);
+        }
+        device_copy(d_ev_log.as<double>() + log_rows * w, rows_h.data(), rows_h.size() * dsz, device, stream);
+        if (log_states) {
+            log_fill_states(log_rows, nullptr, n_new);
+        }
+        stream_synchronize(device, stream);
+        log_rows += n_new;
+    }
 
     if (!cb_eptrs.empty()) {
         throw_callback_exceptions(cb_eptrs);
@@ -2938,6 +3100,108 @@ void tab_core::pack_results(double *dst)
     cp(d.dim + 5u, d.d_maxh.get(), 1);
 }
 
+// ---- event log ----
+std::uint64_t tab_core::get_event_log_size() const
+{
+    return m_impl->log_rows;
+}
+
+std::uint32_t tab_core::get_event_log_row_size() const
+{
+    return m_impl->log_row_doubles();
+}
+
+std::uint64_t tab_core::get_event_log_capacity() const
+{
+    return m_impl->log_capacity();
+}
+
+void tab_core::get_event_log(std::uint64_t first, std::uint64_t count, double *out) const
+{
+    const auto &d = *m_impl;
+    if (first > d.log_rows || count > d.log_rows - first) {
+        throw std::out_of_range("Invalid range of rows requested from the event log: [" + std::to_string(first) + ", "
+                                + std::to_string(first) + " + " + std::to_string(count) + ") of " + std::to_string(d.log_rows));
+    }
+    if (count == 0u) {
+        return;
+    }
+    const auto w = d.log_row_doubles();
+    if (!d.log_stash.empty()) {
+        std::copy_n(d.log_stash.data() + first * w, count * w, out);
+        return;
+    }
+    device_copy(out, d.d_ev_log.as<double>() + first * w, static_cast<std::size_t>(count) * w * sizeof(double), d.device, d.stream);
+    stream_synchronize(d.device, d.stream);
+}
+
+std::vector<double> tab_core::get_event_log() const
+{
+    std::vector<double> ret(static_cast<std::size_t>(m_impl->log_rows) * m_impl->log_row_doubles());
+    get_event_log(0, m_impl->log_rows, ret.data());
+    return ret;
+}
+
+const double *tab_core::event_log_device() const
+{
+    const auto &d = *m_impl;
+    if (d.log_rows == 0u) {
+        return nullptr;
+    }
+    d.log_grow(d.log_rows);
+    stream_synchronize(d.device, d.stream);
+    return d.d_ev_log.as<double>();
+}
+
+void tab_core::clear_event_log()
+{
+    m_impl->log_rows = 0;
+    m_impl->log_stash.clear();
+}
+
+void tab_core::event_log_reserve(std::uint64_t rows)
+{
+    auto &d = *m_impl;
+    d.log_reserved = std::max(d.log_reserved, rows);
+    // (Nothing is allocated before the device is in use, nor for an integrator without recording callbacks.)
+    if (d.ev_has_rec && d.dmod) {
+        d.log_grow(rows);
+    }
+}
+
+void tab_core::set_event_log_states(bool on)
+{
+    auto &d = *m_impl;
+    if (on == d.log_states) {
+        return;
+    }
+    if (d.log_rows != 0u) {
+        throw std::invalid_argument("The state columns of the event log can be switched only while the log is empty: it holds "
+                                    + std::to_string(d.log_rows) + " row(s) - clear it first");
+    }
+    d.log_states = on;
+}
+
+bool tab_core::get_event_log_states() const
+{
+    return m_impl->log_states;
+}
+
+bool tab_core::has_event_recorders() const
+{
+    return m_impl->ev_has_rec;
+}
+
+const std::vector<char> &tab_core::event_log_code_object(int which) const
+{
+    const auto &d = *m_impl;
+    const auto &m = which == 0 ? d.evr_cmod : d.drow_cmod;
+    if (!m) {
+        throw std::invalid_argument("This integrator has no recording event callbacks: no event-log kernels were compiled");
+    }
+    return m->code;
+}
+
 void tab_core::set_event_timing(bool on)
 {
     m_impl->ev_timing = on;
@@ -3011,6 +3275,17 @@ void tab_core::set_device(int device)
     d.ed_mod.reset();
     d.grid_mod.reset();
     d.evj_mod.reset();
+    if (d.log_rows != 0u && d.log_stash.empty()) {
+        d.log_stash.resize(static_cast<std::size_t>(d.log_rows) * d.log_row_doubles());
+        device_copy(d.log_stash.data(), d.d_ev_log.get(), d.log_stash.size() * sizeof(double), d.device, d.stream);
+        stream_synchronize(d.device, d.stream);
+    }
+    d.evr_mod.reset();
+    d.drow_mod.reset();
+    d.d_ev_log = {};
+    d.d_evr_isrec = {};
+    d.d_evr_lane = {};
+    d.d_evr_blk = {};
     d.tc_expand_pending = false;
     d.tc_partial = false;
     d.evs_state = {};

@@ -247,6 +247,24 @@ public:
     // systems which reported events}. The phase times are taken only with the timing on (a synchronisation per phase).
     void set_event_timing(bool on);
     [[nodiscard]] std::array<double, 8> get_event_stats() const;
+    // Event log of the recording callbacks (core_*_event::recorder, layout in event_detection.hpp): rows of
+    // get_event_log_row_size() doubles, in the order in which the callbacks would have been invoked. The log persists
+    // across steps and propagations, a copy of the integrator starts with an empty one. event_log_device(): the rows in
+    // device memory (nullptr if empty), valid until the next call which steps or clears. The state columns can be
+    // switched only while the log is empty. event_log_code_object(): 0 the module of the row-header kernels, 1 the
+    // dense-output kernel over the rows.
+    [[nodiscard]] std::uint64_t get_event_log_size() const;
+    [[nodiscard]] std::uint32_t get_event_log_row_size() const;
+    [[nodiscard]] std::uint64_t get_event_log_capacity() const; // rows the device buffer holds without growing
+    void get_event_log(std::uint64_t first, std::uint64_t count, double *out) const;
+    [[nodiscard]] std::vector<double> get_event_log() const;
+    [[nodiscard]] const double *event_log_device() const;
+    void clear_event_log();
+    void event_log_reserve(std::uint64_t rows);
+    void set_event_log_states(bool on);
+    [[nodiscard]] bool get_event_log_states() const;
+    [[nodiscard]] bool has_event_recorders() const;
+    [[nodiscard]] const std::vector<char> &event_log_code_object(int which) const;
     // Mark the device copies as modified by the caller (e.g. initial conditions written by a kernel).
     void mark_device_modified();
     void set_stream(void *hip_stream);
@@ -287,6 +305,12 @@ std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool high_a
 // include/heyoka/events.hpp:52-325). Callback signatures as in the reference:
 //   non-terminal: void(taylor_adaptive_batch<T> &, T time, int d_sgn, std::uint32_t batch_idx)
 //   terminal:     bool(taylor_adaptive_batch<T> &, int d_sgn, std::uint32_t batch_idx) (false -> stop).
+// Tag accepted in place of a callback: the event is recorded in the integrator's event log (get_event_log()) instead of
+// running code of the caller's - on the device when every event of the integrator is recorded. As a terminal callback
+// it lets the integration continue.
+struct event_recorder {
+};
+
 template <typename T>
 class nt_event_batch
 {
@@ -297,6 +321,7 @@ private:
     expression m_eq;
     callback_t m_cb;
     event_direction m_dir = event_direction::any;
+    bool m_recorder = false;
 
 public:
     // Default construction: the event equation 0 with a callback which does nothing
@@ -313,6 +338,12 @@ public:
         }
         check_dir();
     }
+    template <typename... KwArgs>
+    explicit nt_event_batch(expression e, event_recorder, const KwArgs &...kw_args)
+        : nt_event_batch(std::move(e), callback_t([](taylor_adaptive_batch<T> &, T, int, std::uint32_t) {}), kw_args...)
+    {
+        m_recorder = true;
+    }
     [[nodiscard]] const expression &get_expression() const
     {
         return m_eq;
@@ -324,6 +355,10 @@ public:
     [[nodiscard]] event_direction get_direction() const
     {
         return m_dir;
+    }
+    [[nodiscard]] bool is_recorder() const
+    {
+        return m_recorder;
     }
 
 private:
@@ -346,6 +381,7 @@ private:
     callback_t m_cb;
     event_direction m_dir = event_direction::any;
     T m_cooldown = -1;
+    bool m_recorder = false;
 
 public:
     // Default construction: the event equation 0, no callback, any direction, automatic cooldown
@@ -359,7 +395,12 @@ public:
     {
         static_assert(kw::all_named_v<KwArgs...>);
         if constexpr (kw::has_v<kw::callback_tag, KwArgs...>) {
-            m_cb = kw::get(kw::callback, 0, kw_args...);
+            if constexpr (std::is_same_v<std::decay_t<decltype(kw::get(kw::callback, 0, kw_args...))>, event_recorder>) {
+                m_cb = [](taylor_adaptive_batch<T> &, int, std::uint32_t) { return true; };
+                m_recorder = true;
+            } else {
+                m_cb = kw::get(kw::callback, 0, kw_args...);
+            }
         }
         if (m_dir != event_direction::any && m_dir != event_direction::positive && m_dir != event_direction::negative) {
             throw std::invalid_argument("Invalid value selected for the direction of a terminal event");
@@ -383,6 +424,10 @@ public:
     [[nodiscard]] T get_cooldown() const
     {
         return m_cooldown;
+    }
+    [[nodiscard]] bool is_recorder() const
+    {
+        return m_recorder;
     }
 };
 
@@ -478,6 +523,7 @@ class taylor_adaptive_batch<double>
                 ce.eq = ev.get_expression();
                 ce.dir = ev.get_direction();
                 ce.cooldown = ev.get_cooldown();
+                ce.recorder = ev.is_recorder();
                 if (const auto &cb = ev.get_callback()) {
                     ce.callback = [cb](void *ctx, int d_sgn, std::uint32_t idx) {
                         return cb(*static_cast<self_t *>(ctx), d_sgn, idx);
@@ -491,6 +537,7 @@ class taylor_adaptive_batch<double>
                 detail::core_nt_event ce;
                 ce.eq = ev.get_expression();
                 ce.dir = ev.get_direction();
+                ce.recorder = ev.is_recorder();
                 const auto &cb = ev.get_callback();
                 ce.callback = [cb](void *ctx, double tm, int d_sgn, std::uint32_t idx) {
                     cb(*static_cast<self_t *>(ctx), tm, d_sgn, idx);
@@ -650,6 +697,24 @@ public:
     void reset_cooldowns(std::uint32_t i)
     {
         m_core.reset_cooldowns(i);
+    }
+    // Event log of the events constructed with event_recorder: rows of get_event_log_row_size() = 8 + dim doubles
+    // (system, class, index, d_sgn, trigger time hi / lo, root, |d eq/dt|, state at the trigger time), in callback order.
+    [[nodiscard]] std::vector<double> get_event_log() const
+    {
+        return m_core.get_event_log();
+    }
+    [[nodiscard]] std::uint64_t get_event_log_size() const
+    {
+        return m_core.get_event_log_size();
+    }
+    [[nodiscard]] std::uint32_t get_event_log_row_size() const
+    {
+        return m_core.get_event_log_row_size();
+    }
+    void clear_event_log()
+    {
+        m_core.clear_event_log();
     }
     [[nodiscard]] const std::vector<std::vector<std::optional<std::pair<double, double>>>> &get_te_cooldowns() const
     {

@@ -278,6 +278,45 @@ int hy_tab_get_event_stats(hy_tab, double *out8);
  * src/taylor_adaptive_batch.cpp:837-1030 does) and adds the counts to the counters once per step: no per-event host work. */
 void hy_event_counter_nt(hy_tab, double time, int d_sgn, uint32_t batch_idx, void *user);
 int hy_event_counter_t(hy_tab, int d_sgn, uint32_t batch_idx, void *user);
+/* Ready-made callbacks which RECORD: every invocation appends a row to the integrator's event log and lets the integration
+ * continue. `user` may be NULL or point to a uint64_t which is incremented like a counter's. Events with a counter or a
+ * callback of the caller's produce no rows. When every event of an integrator has a counting or a recording callback the
+ * rows are written on the device (no per-event host work); mixed with other callbacks they are collected by the host loop -
+ * the same rows in the same order.
+ * A row is 8 + dim doubles (8 with the states switched off), integers stored as doubles:
+ *   0 system (batch index), 1 class (0 terminal, 1 non-terminal), 2 event index within its class, 3 d_sgn,
+ *   4, 5 trigger time (hi, lo) = new time - h + root in double-length arithmetic (hi is the time a host callback receives),
+ *   6 root (offset from the beginning of the step), 7 |d eq/dt| at the root,
+ *   8 ... the state at the trigger time (non-terminal: dense output of the step's Taylor coefficients at the root;
+ *         terminal: the state after the step, which was truncated at the event).
+ * Order: the order in which the host loop would have invoked the callbacks - steps in order; within a step by batch index;
+ * within a lane the non-terminal events triggering before the lane's first terminal event by ascending |root| (stable in
+ * detection order), then that terminal event. Lanes which went non-finite produce no rows.
+ * Recorders next to callbacks of the caller's (host-loop path): the state columns are filled when all the callbacks of the
+ * step have run - a callback which changes the state or asks for other Taylor coefficients through the integrator is
+ * visible in the rows of that step.
+ * The log belongs to the integrator and persists across step / propagate calls; hy_tab_copy() gives the copy an empty log;
+ * an integrator without recording callbacks has a log of size 0 and allocates nothing. */
+void hy_event_recorder_nt(hy_tab, double time, int d_sgn, uint32_t batch_idx, void *user);
+int hy_event_recorder_t(hy_tab, int d_sgn, uint32_t batch_idx, void *user);
+uint64_t hy_tab_event_log_size(hy_tab);            /* rows */
+uint32_t hy_tab_event_log_row_doubles(hy_tab);     /* doubles per row */
+uint64_t hy_tab_event_log_capacity(hy_tab);        /* rows the device buffer holds before it grows (geometrically) */
+int hy_tab_get_event_log(hy_tab, uint64_t first, uint64_t count, double *out);
+/* Zero-copy: device pointer to the rows (NULL if the log is empty), valid until the next call which steps or clears. */
+int hy_tab_event_log_device(hy_tab, const double **rows, uint64_t *n_rows, uint32_t *row_doubles);
+int hy_tab_clear_event_log(hy_tab);
+int hy_tab_event_log_reserve(hy_tab, uint64_t rows);
+/* State columns on (default) / off: rows of 8 doubles, no dense output. Only while the log is empty (error otherwise). */
+int hy_tab_set_event_log_states(hy_tab, int on);
+int hy_tab_get_event_log_states(hy_tab);
+/* Introspection hooks (used by the test suite; not needed to use the log): capacity of the device buffer above, and
+ * the two functions below.
+ * Code objects (gfx950) of the event-log kernels of an integrator with recording callbacks: which = 0 row headers
+ * (hy_evr_count / hy_evr_scan / hy_evr_write), 1 dense output over the rows (hy_dout_rows). Owned by the integrator. */
+int hy_tab_event_log_code_object(hy_tab, int which, const char **data, size_t *size);
+/* HIP source of the event-detection module for (order, number of terminal / non-terminal events); hy_free_str(). */
+char *hy_event_detection_source(uint32_t order, uint32_t n_t_events, uint32_t n_nt_events);
 /* reset_cooldowns(): batch_idx < 0 -> all the lanes. */
 int hy_tab_reset_cooldowns(hy_tab, int64_t batch_idx);
 /* get_te_cooldowns(): [batch_size * n_t_events] arrays indexed [lane * n_t_events + event]; active != 0 where a
