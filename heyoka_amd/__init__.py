@@ -61,6 +61,7 @@ __all__ = [
     "native_event_counter",
     "native_event_recorder",
     "event_log",
+    "callback",
 ]
 
 _builtin_sum = sum
@@ -878,6 +879,54 @@ class native_event_recorder(native_event_counter):
     of invocations; as a terminal callback it always continues."""
 
 
+class _angle_reducer:
+    """callback::angle_reducer (include/heyoka/callback/angle_reducer.hpp): the step callback which keeps the given state
+    variables in [0, 2 pi) - ``x -= 2 pi floor(x / 2 pi)`` after every step. It lives in the library: passed as
+    ``callback=`` (alone or in a list) the reduction runs on the device, and when it is the only callback of
+    propagate_until() / propagate_for() (no continuous output, no events) inside the propagate kernel itself
+    (``ta.last_callback_path``). ``angle_reducer()`` without arguments is the default-constructed object, which every use
+    rejects. Calling it with an integrator reduces that integrator's state once."""
+
+    def __init__(self, vars=None, _handle=None):  # noqa: A002 - the reference's argument name
+        if _handle is not None:
+            self._h = _handle
+        elif vars is None:
+            self._h = check_handle(lib.hy_angle_reducer_new_default())
+        else:
+            exs, arr = _handle_array(list(vars))
+            self._h = check_handle(lib.hy_angle_reducer_new(arr, len(exs)))
+
+    def __del__(self, _free=lib.hy_angle_reducer_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def __copy__(self):
+        return _angle_reducer(_handle=check_handle(lib.hy_angle_reducer_clone(self._h)))
+
+    def __deepcopy__(self, memo):
+        return self.__copy__()
+
+    def __repr__(self):
+        return take_str(lib.hy_angle_reducer_str(self._h))
+
+    def pre_hook(self, ta):
+        if lib.hy_angle_reducer_pre_hook(ta._h, self._h) != 0:
+            raise_for(lib.hy_last_error_code() or 4)
+
+    def __call__(self, ta):
+        if lib.hy_angle_reducer_call(ta._h, self._h) < 0:
+            raise_for(lib.hy_last_error_code() or 4)
+        return True
+
+
+class callback:  # noqa: N801 - namespace heyoka::callback
+    """Step callbacks which the library ships (namespace heyoka::callback)."""
+
+    angle_reducer = _angle_reducer
+
+
 class event_log:
     """The rows of an integrator's event log as arrays, in the order in which the callbacks would have been invoked:
     ``system``, ``terminal`` (bool), ``idx`` (event index within its class), ``d_sgn``, ``time`` / ``time_lo`` (trigger
@@ -1232,6 +1281,28 @@ class taylor_adaptive_batch:
         return take_str(lib.hy_tab_get_codegen_info(self._h))
 
     @property
+    def last_callback_path(self):
+        """How the step callback of the last propagate_*() ran: 0 no callback, 1 host callback after every sweep of the
+        lock-step loop, 2 ``callback.angle_reducer`` on the device after every sweep (kernel hy_angle_reduce), 3 the reduction
+        fused into the propagate kernel (one launch)."""
+        return int(lib.hy_tab_last_callback_path(self._h))
+
+    @property
+    def angle_reduce_compile_seconds(self):
+        """One-off hiprtc compilation time of the last stepper variant with a fused angle reduction (0.0: none yet)."""
+        return float(lib.hy_tab_angle_reduce_compile_seconds(self._h))
+
+    def angle_reduce_variant_source(self, indices):
+        """(HIP source of the stepper variant which reduces the state variables ``indices`` after every state update, reason):
+        the source is "" and the reason says why when the code generator of this integrator has no such variant."""
+        idx = np.ascontiguousarray(sorted(int(i) for i in indices), dtype=np.uint32)
+        why = ctypes.c_void_p()
+        p = lib.hy_tab_angle_reduce_variant_source(self._h, idx.ctypes.data, idx.size, ctypes.byref(why))
+        if not p:
+            raise_for(lib.hy_last_error_code() or 4)
+        return take_str(p), (take_str(why.value) if why.value else "")
+
+    @property
     def decomposition(self):
         return take_str(lib.hy_tab_get_decomposition_str(self._h)).rstrip("\n").split("\n")
 
@@ -1359,6 +1430,9 @@ class taylor_adaptive_batch:
                                  if len(cbs) > 1 or isinstance(callback, (list, tuple)) else "the step callback must be callable")
         arr = (_lib.StepCallbackDesc * len(cbs))()
         keep = []
+        # (The library's own angle_reducer: its native descriptor instead of a ctypes thunk - recognised by address.)
+        native_call = ctypes.cast(lib.hy_angle_reducer_call, _lib.STEP_CALLBACK)
+        native_pre = ctypes.cast(lib.hy_angle_reducer_pre_hook, _lib.STEP_PRE_HOOK)
 
         def make(c):
             def call(_tab, _data):
@@ -1382,6 +1456,10 @@ class taylor_adaptive_batch:
             return f_call, f_pre
 
         for i, c in enumerate(cbs):
+            if isinstance(c, _angle_reducer):
+                arr[i].call, arr[i].pre_hook, arr[i].user_data = native_call, native_pre, c._h
+                keep.append(c)
+                continue
             arr[i].call, arr[i].pre_hook = make(c)
             arr[i].user_data = None
         return arr, len(cbs), keep

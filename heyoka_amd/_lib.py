@@ -292,6 +292,18 @@ SIGNATURES = [
     ("hy_cfunc_set_stream", c_int, [c_void_p, c_void_p]),
     ("hy_cfunc_eval", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     ("hy_cfunc_eval_device", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
+    ("hy_angle_reducer_new", c_void_p, [c_void_p, c_size_t]),
+    ("hy_angle_reducer_new_default", c_void_p, []),
+    ("hy_angle_reducer_clone", c_void_p, [c_void_p]),
+    ("hy_angle_reducer_free", None, [c_void_p]),
+    ("hy_angle_reducer_str", c_void_p, [c_void_p]),
+    ("hy_angle_reducer_call", c_int, [c_void_p, c_void_p]),
+    ("hy_angle_reducer_pre_hook", c_int, [c_void_p, c_void_p]),
+    ("hy_tab_last_callback_path", c_int, [c_void_p]),
+    ("hy_tab_angle_reduce_variant_source", c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("hy_tab_angle_reduce_compile_seconds", c_double, [c_void_p]),
+    ("hy_angle_reduce_source", c_void_p, []),
+    ("hy_angle_reduce_host", c_double, [c_double]),
     ("hy_tab_take_c_output", c_int, [c_void_p, c_void_p]),
     ("hy_cout_free", None, [c_void_p]),
     ("hy_cout_clone", c_void_p, [c_void_p]),

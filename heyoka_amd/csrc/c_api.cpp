@@ -3,22 +3,27 @@
 #include "_build/build_id.h"
 #include "../../include/heyoka_amd.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <limits>
+#include <set>
 #include <sstream>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
 #include <hip/hiprtc.h>
 
+#include "angle_reducer.hpp"
 #include "cfunc.hpp"
 #include "decompose.hpp"
 #include "ensemble.hpp"
 #include "expression.hpp"
 #include "hip_backend.hpp"
+#include "hip_emit.hpp"
 #include "model.hpp"
 #include "node_rule.hpp"
 #include "taylor_adaptive_batch.hpp"
@@ -35,6 +40,10 @@ struct hy_sys_s {
 
 struct hy_tab_s {
     detail::tab_core core;
+};
+
+struct hy_angle_reducer_s {
+    callback::angle_reducer ar;
 };
 
 struct hy_cout_s {
@@ -154,8 +163,12 @@ detail::tab_core::cb_t wrap_cb(hy_tab tab, hy_step_callback cb, void *cb_data)
 }
 
 // A set of C step callbacks with optional pre-hooks (hy_step_callback_desc): every member runs at every step, the
-// results are and-ed (src/step_callback.cpp:108-127). Returns the pair (call, pre_hook) for the core.
-std::pair<detail::tab_core::cb_t, detail::tab_core::pre_t> wrap_cbs(hy_tab tab, const hy_step_callback_desc *cbs, size_t n_cbs)
+// results are and-ed (src/step_callback.cpp:108-127). Returns (call, pre_hook, reducer indices) for the core.
+// Members whose `call` is the library's hy_angle_reducer_call are recognised by address (like hy_event_counter_nt among the
+// event callbacks): the C++ object behind the handle is used directly - its exceptions reach the caller with their
+// messages -, and when every member is one the core learns the indices they reduce (tab_core::red_t).
+std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::red_t> wrap_cbs(hy_tab tab, const hy_step_callback_desc *cbs,
+                                                                                             size_t n_cbs)
 {
     if (n_cbs == 0u || (n_cbs == 1u && cbs[0].call == nullptr)) {
         return {};
@@ -166,9 +179,17 @@ std::pair<detail::tab_core::cb_t, detail::tab_core::pre_t> wrap_cbs(hy_tab tab, 
             throw std::invalid_argument("Cannot construct a callback set containing one or more empty callbacks");
         }
     }
-    detail::tab_core::cb_t call = [tab, v]() {
+    const auto reducer_of = [](const hy_step_callback_desc &c) -> callback::angle_reducer * {
+        return (c.call == &hy_angle_reducer_call && c.user_data != nullptr) ? &static_cast<hy_angle_reducer>(c.user_data)->ar
+                                                                            : nullptr;
+    };
+    detail::tab_core::cb_t call = [tab, v, reducer_of]() {
         bool ret = true;
         for (const auto &c : v) {
+            if (auto *ar = reducer_of(c)) {
+                (*ar)(tab->core);
+                continue;
+            }
             const auto rc = c.call(tab, c.user_data);
             if (rc < 0) {
                 // An error inside the callback (e.g. a Python exception recorded by the binding): the other members of the
@@ -179,14 +200,30 @@ std::pair<detail::tab_core::cb_t, detail::tab_core::pre_t> wrap_cbs(hy_tab tab, 
         }
         return ret;
     };
-    detail::tab_core::pre_t pre = [tab, v]() {
+    detail::tab_core::pre_t pre = [tab, v, reducer_of]() {
         for (const auto &c : v) {
+            if (auto *ar = reducer_of(c)) {
+                ar->pre_hook(tab->core);
+                continue;
+            }
             if (c.pre_hook != nullptr && c.pre_hook(tab, c.user_data) != 0) {
                 throw std::runtime_error("The pre_hook() of a step callback failed: the propagation was not started");
             }
         }
     };
-    return {std::move(call), std::move(pre)};
+    detail::tab_core::red_t red;
+    if (std::all_of(v.begin(), v.end(), [&](const auto &c) { return reducer_of(c) != nullptr; })) {
+        red = [v, reducer_of]() {
+            std::set<std::uint32_t> u;
+            for (const auto &c : v) {
+                for (const auto i : reducer_of(c)->get_indices()) {
+                    u.insert(static_cast<std::uint32_t>(i));
+                }
+            }
+            return std::vector<std::uint32_t>(u.begin(), u.end());
+        };
+    }
+    return {std::move(call), std::move(pre), std::move(red)};
 }
 
 } // namespace
@@ -1223,18 +1260,18 @@ int hy_tab_propagate_until_cbs(hy_tab t, const double *ts, size_t n_ts, uint64_t
                                const hy_step_callback_desc *cbs, size_t n_cbs, int wtc, int c_out)
 {
     return guarded([&] {
-        auto [call, pre] = wrap_cbs(t, cbs, n_cbs);
+        auto [call, pre, red] = wrap_cbs(t, cbs, n_cbs);
         t->core.propagate_until(vec_from(ts, n_ts), static_cast<std::size_t>(max_steps),
-                                expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre);
+                                expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red);
     });
 }
 int hy_tab_propagate_for_cbs(hy_tab t, const double *dts, size_t n_dts, uint64_t max_steps, const double *mdts, size_t n_mdt,
                              const hy_step_callback_desc *cbs, size_t n_cbs, int wtc, int c_out)
 {
     return guarded([&] {
-        auto [call, pre] = wrap_cbs(t, cbs, n_cbs);
+        auto [call, pre, red] = wrap_cbs(t, cbs, n_cbs);
         t->core.propagate_for(vec_from(dts, n_dts), static_cast<std::size_t>(max_steps),
-                              expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre);
+                              expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red);
     });
 }
 int hy_tab_propagate_grid_cbs(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
@@ -1242,12 +1279,109 @@ int hy_tab_propagate_grid_cbs(hy_tab t, const double *grid, size_t n_grid, uint6
 {
     return guarded([&] {
         const auto bs = t->core.get_batch_size();
-        auto [call, pre] = wrap_cbs(t, cbs, n_cbs);
+        auto [call, pre, red] = wrap_cbs(t, cbs, n_cbs);
         auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
-                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre);
+                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red);
         std::memcpy(out, ret.data(), ret.size() * sizeof(double));
     });
 }
+// ---- callback::angle_reducer ----
+hy_angle_reducer hy_angle_reducer_new(const hy_expr *vars, size_t n)
+{
+    try {
+        std::vector<expression> v;
+        for (size_t i = 0; i < n; ++i) {
+            v.push_back(vars[i]->ex);
+        }
+        return new hy_angle_reducer_s{callback::angle_reducer(v)};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+hy_angle_reducer hy_angle_reducer_new_default(void)
+{
+    try {
+        return new hy_angle_reducer_s{};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+hy_angle_reducer hy_angle_reducer_clone(hy_angle_reducer r)
+{
+    try {
+        return new hy_angle_reducer_s{r->ar};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+void hy_angle_reducer_free(hy_angle_reducer r)
+{
+    delete r;
+}
+char *hy_angle_reducer_str(hy_angle_reducer r)
+{
+    try {
+        std::ostringstream oss;
+        oss << r->ar;
+        return dup_str(oss.str());
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+int hy_angle_reducer_call(hy_tab t, void *user)
+{
+    try {
+        return (static_cast<hy_angle_reducer>(user)->ar)(t->core) ? 1 : 0;
+    } catch (...) {
+        handle_exception();
+        return -1;
+    }
+}
+int hy_angle_reducer_pre_hook(hy_tab t, void *user)
+{
+    try {
+        static_cast<hy_angle_reducer>(user)->ar.pre_hook(t->core);
+        return 0;
+    } catch (...) {
+        handle_exception();
+        return 1;
+    }
+}
+int hy_tab_last_callback_path(hy_tab t)
+{
+    return t->core.get_last_callback_path();
+}
+double hy_tab_angle_reduce_compile_seconds(hy_tab t)
+{
+    return t->core.get_angle_reduce_compile_seconds();
+}
+char *hy_tab_angle_reduce_variant_source(hy_tab t, const uint32_t *idx, size_t n, char **why_not)
+{
+    try {
+        std::string why;
+        const auto src = t->core.get_angle_reduce_variant_source(std::vector<std::uint32_t>(idx, idx + n), why);
+        if (why_not != nullptr) {
+            *why_not = dup_str(why);
+        }
+        return dup_str(src);
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+char *hy_angle_reduce_source(void)
+{
+    return dup_str(make_angle_reduce_source());
+}
+double hy_angle_reduce_host(double x)
+{
+    return angle_reduce_host(x);
+}
+
 int hy_tab_take_c_output(hy_tab t, hy_cout *out)
 {
     return guarded([&] {

@@ -38,6 +38,75 @@ std::string fp_literal(double x)
     return s;
 }
 
+// NOTE: the modules are compiled with -ffp-contract=fast, under which the backend fuses a product into a following
+// difference whatever the pragmas say: the product goes through an empty asm operand, which is opaque to it (like
+// hy_mul_nc() of the event-jet module). The quotient is a correctly rounded division (no reciprocal-math flag is ever set).
+const char *const angle_reduce_helper_source = R"HIP(
+// callback::angle_reducer: x - 2 pi floor(x / 2 pi) with a rounded quotient, product and difference (no contraction);
+// non-finite values pass through, so that the non-finite detection of the steppers still sees them.
+__device__ __forceinline__ double hy_angle_red(double x)
+{
+    const double twopi = 0x1.921fb54442d18p+2;
+    double q = x / twopi;
+    asm("" : "+v"(q));
+    double t = twopi * floor(q);
+    asm("" : "+v"(t));
+    const double r = x - t;
+    return (fabs(x) < __builtin_inf()) ? r : x;
+}
+)HIP";
+
+std::string make_angle_reduce_source()
+{
+    std::string src = angle_reduce_helper_source;
+    src += R"HIP(
+struct hy_ar_kargs {
+    double *state;            // [n_eq * N]
+    const unsigned *idx;      // [n_idx] state variables to reduce
+    unsigned long long N;     // number of systems
+    unsigned n_idx;
+};
+
+extern "C" __global__ void __launch_bounds__(256) hy_angle_reduce(const hy_ar_kargs a)
+{
+    const unsigned long long t = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (t >= a.N * a.n_idx) return;
+    const unsigned long long j = t / a.N, s = t - j * a.N;
+    double *p = a.state + (unsigned long long)a.idx[j] * a.N + s;
+    *p = hy_angle_red(*p);
+}
+)HIP";
+    return src;
+}
+
+// Host counterpart of hy_angle_red(): the same three operations, kept apart by volatile temporaries so that no
+// compiler setting can contract the product into the difference.
+double angle_reduce_host(double x) noexcept
+{
+    const double twopi = 0x1.921fb54442d18p+2;
+    if (!std::isfinite(x)) {
+        return x;
+    }
+    volatile double q = x / twopi;
+    volatile double t = twopi * std::floor(q);
+    return x - t;
+}
+
+emitted_module emit_angle_reduce_variant(const taylor_program &prog, const emit_options &opts, std::string &why_not)
+{
+    if (opts.angle_reduce.empty() || !std::is_sorted(opts.angle_reduce.begin(), opts.angle_reduce.end())
+        || opts.angle_reduce.back() >= prog.n_eq) {
+        throw std::invalid_argument("Invalid list of state variables for the fused angle reduction");
+    }
+    auto m = emit_hip_module(prog, opts);
+    if (!m.angle_reduce_fused) {
+        why_not = "the generator of this stepper has no fused angle reduction (" + m.notes.substr(0, m.notes.find_first_of(":,;("))
+                  + ")";
+        return {};
+    }
+    return m;
+}
+
 namespace emit_detail
 {
 
@@ -471,6 +540,11 @@ std::string emit_unrolled_kernel(const taylor_program &p, const emit_options &op
 
     ssa_emitter e(p, order);
     auto &os = e.os;
+    // Fused callback::angle_reducer (emit_options::angle_reduce): the updated value of a flagged state variable goes
+    // through hy_angle_red() before it is checked, stored or reused.
+    const auto reduced = [&](std::uint32_t i, const std::string &v) {
+        return std::binary_search(opts.angle_reduce.begin(), opts.angle_reduce.end(), i) ? ("hy_angle_red(" + v + ")") : v;
+    };
     e.enable_pow_rcp(!opts.exact_division);
     e.running_sums = opts.sum_order != 1;
     // Divisions by the (constant) order: one multiplication by RN(1 / k), within 1 ulp of the quotient (like the pair
@@ -797,7 +871,7 @@ if (a.mode == 1) {
             }
         }
         for (std::uint32_t i = 0; i < n_eq; ++i) {
-            os << "x" << i << " = x" << i << "n;\n";
+            os << "x" << i << " = " << reduced(i, "x" + std::to_string(i) + "n") << ";\n";
         }
         if (n_derived != nullptr) {
             *n_derived = static_cast<std::uint32_t>(
@@ -818,7 +892,7 @@ if (a.mode == 1) {
                 os << "const double tmp = c[(u64)k * hy_Ns] * cur_h;\nconst double y = tmp - comp;\nconst double t = res + "
                       "y;\n";
                 os << "comp = (t - res) - y;\nres = t;\ncur_h = cur_h * h;\n}\n";
-                os << "x" << i << " = res;\n}\n";
+                os << "x" << i << " = " << reduced(i, "res") << ";\n}\n";
             }
         } else {
             // Horner (reference: taylor_run_multihorner(), src/taylor_00.cpp:279-351).
@@ -828,7 +902,7 @@ if (a.mode == 1) {
                 os << "double res = c[(u64)" << order << "u * hy_Ns];\n";
                 os << "#pragma unroll\nfor (unsigned k = 1; k <= " << order << "u; ++k) {\n";
                 os << "res = c[(u64)(" << order << "u - k) * hy_Ns] + res * h;\n}\n";
-                os << "x" << i << " = res;\n}\n";
+                os << "x" << i << " = " << reduced(i, "res") << ";\n}\n";
             }
         }
 
@@ -900,10 +974,11 @@ std::uint64_t reg_jet_estimate(const taylor_program &p, std::uint32_t order, boo
 emitted_module emit_unrolled(const taylor_program &p, const emit_options &opts)
 {
     std::ostringstream src;
-    src << prelude << rules_source(p);
+    src << prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << rules_source(p);
     emit_dout(src, p, opts);
 
     emitted_module ret;
+    ret.angle_reduce_fused = !opts.angle_reduce.empty();
     // Register-resident jets when they fit comfortably in the 512 VGPR+AGPR of a lane.
     // NOTE: the stepper with events needs the Taylor coefficients in memory (event detection, dense output).
     // (Round 6: the estimate counts what the generator really keeps when it folds scaled copies and u + number into their
@@ -1763,6 +1838,7 @@ dev_switches dev_switches::from_env()
     d.multi_class = !(std::getenv("HEYOKA_AMD_MULTI_CLASS") != nullptr && std::string(std::getenv("HEYOKA_AMD_MULTI_CLASS")) == "0");
     d.linearise = !set("HEYOKA_AMD_NO_LINEARISED_SUMS");
     d.table_lds = num("HEYOKA_AMD_TABLE_LDS", -1);
+    d.staged_wps = num("HEYOKA_AMD_STAGED_WPS", 0);
     d.ev_inline_max_nonlinear = num("HEYOKA_AMD_EV_INLINE_MAX_NONLINEAR", -1);
     d.v5_prio = num("HEYOKA_AMD_V5_PRIO", 2);
     d.unrolled_waves = num("HEYOKA_AMD_UNROLLED_WAVES", 0);

@@ -78,6 +78,7 @@ enum class emit_mode { unrolled, cluster, table, block };
 //   HEYOKA_AMD_CLUSTER_V1             first-generation cluster generator
 //   HEYOKA_AMD_MULTI_CLASS=0          planner: no multi-class plans (clusters of several shapes / levels)
 //   HEYOKA_AMD_TABLE_LDS=0|1          table stepper: tape in HBM / in LDS (default: by size)
+//   HEYOKA_AMD_STAGED_WPS=1|2|4       staged table stepper: wavefronts per system (default: by the size of the tape)
 //   HEYOKA_AMD_EV_INLINE_MAX_NONLINEAR  budget of nonlinear nodes of the event equations inside the stepper
 //   HEYOKA_AMD_V5_PRIO, HEYOKA_AMD_V5_OPTS, HEYOKA_AMD_V5_PAD   one-lane-per-pair kernel: issue priorities, round-5 items
 //                                     switched off one by one (A/B harness), sensitivity padding (see hip_emit_cluster2.cpp)
@@ -87,7 +88,7 @@ enum class emit_mode { unrolled, cluster, table, block };
 struct dev_switches {
     bool v5_events = true, compact_tc = true, events_in_stepper = true, pair_events = true, refill = true, block_v2 = true,
          state_aliases = true, cluster_v1 = false, linearise = true, multi_class = true;
-    int table_lds = -1, ev_inline_max_nonlinear = -1, v5_prio = 2;
+    int table_lds = -1, ev_inline_max_nonlinear = -1, v5_prio = 2, staged_wps = 0;
     // HEYOKA_AMD_UNROLLED_WAVES=n: the straight-line stepper is compiled for n wavefronts per SIMD (amdgpu_waves_per_eu: the
     // register allocator gets 512 / n registers per lane and spills the rest - the two-wavefront experiment of round 5).
     int unrolled_waves = 0;
@@ -151,6 +152,11 @@ struct emit_options {
     // emit_event_jets(): only the kernels which serve the compact Taylor coefficients (hy_dout_c, hy_tc_expand) - the
     // stepper evaluates the event equations itself (emitted_module::events_in_stepper).
     bool ev_helpers_only = false;
+    // callback::angle_reducer fused into the propagate kernel: sorted indices of the state variables which
+    // are reduced to [0, 2 pi) right after every state update. Empty: no reduction, and not a byte of the source differs. Only
+    // the straight-line, the table (both tape placements) and the first-generation / multi-class wave-cluster generators
+    // implement it (emitted_module::angle_reduce_fused); the module is used for mode-1 launches only.
+    std::vector<std::uint32_t> angle_reduce;
 };
 
 struct emitted_module {
@@ -192,6 +198,8 @@ struct emitted_module {
     // decomposition strings, then the definitions of the state derivatives. Lets the tests run the oracle's interpreter
     // on the rewritten program and check that the rewrites do not change a single bit of the jets.
     std::string internal_program;
+    // The stepper reduces the state variables of emit_options::angle_reduce after every state update.
+    bool angle_reduce_fused = false;
 };
 
 // Textual form of a flattened program (see emitted_module::internal_program).
@@ -255,6 +263,18 @@ struct pair_distance_event {
     double sign = 1; // -1: the squares are subtracted, c - |r_i - r_j|^2
 };
 bool match_pair_distance_event(const taylor_program &prog, std::uint32_t u, pair_distance_event &out);
+
+// callback::angle_reducer on the device. angle_reduce_helper_source: the __device__ function hy_angle_red(x) =
+// x - twopi * floor(x / twopi), twopi = 0x1.921fb54442d18p+2, with a rounded quotient, a rounded product and a rounded
+// difference (no FMA contraction), non-finite x returned as it is - the ONE definition which the stand-alone kernel and the
+// fused steppers share. make_angle_reduce_source(): module of the stand-alone kernel hy_angle_reduce (one thread per
+// (flagged variable, system) over the device-resident state). emit_angle_reduce_variant(): the stepper of `prog` with the
+// reduction of opts.angle_reduce fused in, or a module with an empty source and the reason in why_not when the generator
+// which serves prog does not implement it. angle_reduce_host(): the same arithmetic on the host.
+extern const char *const angle_reduce_helper_source;
+std::string make_angle_reduce_source();
+emitted_module emit_angle_reduce_variant(const taylor_program &prog, const emit_options &opts, std::string &why_not);
+double angle_reduce_host(double x) noexcept;
 
 // Format a double as a C++17 hexadecimal floating-point literal (exact round trip).
 std::string fp_literal(double);

@@ -2115,7 +2115,7 @@ emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts
 
     // ===================== module text =====================
     std::ostringstream src;
-    src << prelude;
+    src << prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source);
     emit_detail::emit_dout(src, p, opts);
 
     src << emit_detail::wsync_macro;
@@ -2169,6 +2169,22 @@ emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts
         src << "const bool svalid" << r << " = (" << r * L << "u + l) < " << n_eq << "u;\n";
         src << "const unsigned svi" << r << " = svalid" << r << " ? (" << r * L << "u + l) : " << r * L << "u;\n";
     }
+    // Fused callback::angle_reducer (emit_options::angle_reduce): lane l of a system holds the state variables r * L + l;
+    // sred<r> says whether the one of round r is flagged (rounds without a flagged variable get no code at all).
+    std::vector<char> round_reduced(sv_rounds, 0);
+    for (std::uint32_t r = 0; r < sv_rounds; ++r) {
+        std::string cond;
+        for (const auto i : opts.angle_reduce) {
+            if (i / L == r) {
+                cond += (cond.empty() ? "" : " || ") + ("svi" + std::to_string(r) + " == " + std::to_string(i) + "u");
+            }
+        }
+        if (!cond.empty()) {
+            round_reduced[r] = 1;
+            src << "const bool sred" << r << " = svalid" << r << " && (" << cond << ");\n";
+        }
+    }
+    ret.angle_reduce_fused = !opts.angle_reduce.empty();
     src << R"HIP(
 for (;;) {
 // Pull the next group of systems from the device-side work queue.
@@ -2250,7 +2266,11 @@ if (a.mode == 1) {
             src << "for (unsigned k = 1; k <= " << order << "u; ++k) {\n";
             src << "res = c[(u64)(" << order << "u - k) * " << kstride << "u] + res * h;\n}\n";
         }
-        src << "xs" << r << " = res;\n}\n";
+        if (round_reduced[r] != 0) {
+            src << "xs" << r << " = sred" << r << " ? hy_angle_red(res) : res;\n}\n";
+        } else {
+            src << "xs" << r << " = res;\n}\n";
+        }
     }
     src << R"HIP(
 {

@@ -46,6 +46,7 @@ namespace table_detail
 {
 void emit_tables_and_rules(std::ostream &src, const taylor_program &p, const emit_options &opts, const std::string &pre_defs,
                            const char *stride);
+void expand_angle_reduce_marker(std::string &text, const emit_options &opts);
 }
 
 namespace
@@ -484,12 +485,9 @@ emitted_module emit_staged(const taylor_program &p, const emit_options &opts, st
     // a level then ends with a wave-level synchronisation (LDS operations of a wavefront complete in order: no s_barrier),
     // and the 5 ... 10 systems of a CU hide each other's latency. Four wavefronts only where ONE tape fills the LDS of a CU.
     std::uint32_t wps = per_cu >= 2u ? 1u : 4u;
-    if (const char *e = std::getenv("HEYOKA_AMD_STAGED_WPS")) {
-        // (Experiment switch: wavefronts per system.)
-        const auto w = static_cast<std::uint32_t>(std::atoi(e));
-        if (w == 1u || w == 2u || w == 4u) {
-            wps = w;
-        }
+    // (Experiment switch, read when the integrator is constructed - dev_switches::from_env(): wavefronts per system.)
+    if (opts.dev.staged_wps == 1 || opts.dev.staged_wps == 2 || opts.dev.staged_wps == 4) {
+        wps = static_cast<std::uint32_t>(opts.dev.staged_wps);
     }
     const std::uint32_t LANES = 64u * wps;
 
@@ -1052,7 +1050,7 @@ emitted_module emit_staged(const taylor_program &p, const emit_options &opts, st
 
     // ---- module text ----
     std::ostringstream src;
-    src << emit_detail::prelude << emit_detail::rules_source(p);
+    src << emit_detail::prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
     emit_detail::emit_dout(src, p, opts);
     src << emit_detail::wsync_macro;
     {
@@ -1285,6 +1283,7 @@ for (;;) {
             res = cf[HY_ORDER];
             for (unsigned k = 1; k <= HY_ORDER; ++k) res = cf[HY_ORDER - k] + res * h;
 #endif
+            HY_ANGLE_REDUCE(i, res)
             hy_sv(i, 0u) = res;
             nf = nf | !hy_finite(res);
         }
@@ -1335,6 +1334,8 @@ for (;;) {
     const auto pos = text.find("#define HY_STAGED 1\n");
     text.insert(pos, sync_def);
 
+    table_detail::expand_angle_reduce_marker(text, opts);
+    ret.angle_reduce_fused = !opts.angle_reduce.empty();
     ret.source = std::move(text);
     ret.kernel_name = "hy_taylor";
     ret.dout_name = "hy_dout";

@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
 #include <vector>
 
 namespace heyoka_amd
@@ -686,6 +687,7 @@ extern "C" __global__ void __launch_bounds__(256, 4) hy_taylor(const hy_kargs a)
                 res = hy_tp(c, HY_ORDER, i);
                 for (unsigned k = 1; k <= HY_ORDER; ++k) res = hy_tp(c, HY_ORDER - k, i) + res * h;
 #endif
+                HY_ANGLE_REDUCE(i, res)
                 hy_tp(c, 0, i) = res;
                 nf = nf | !hy_finite(res);
             }
@@ -930,6 +932,27 @@ void emit_tables_and_rules(std::ostream &src, const taylor_program &p, const emi
     src << "default: return 0.0;\n}\n}\n";
 }
 
+// Fused callback::angle_reducer (emit_options::angle_reduce) in the rolled state update of the table steppers. The kernel
+// templates carry the marker line HY_ANGLE_REDUCE(i, res) right in front of the statement which stores the updated value
+// `res` of state variable i; it is replaced by one guarded call of hy_angle_red() per flagged state variable - by nothing
+// when the list is empty, so that source is the one of a template without the marker. A template which lost its marker is
+// an error whatever the list: every construction of a table stepper notices, not the first fused propagation.
+void expand_angle_reduce_marker(std::string &text, const emit_options &opts)
+{
+    const std::string marker = "HY_ANGLE_REDUCE(i, res)\n";
+    const auto pos = text.find(marker);
+    if (pos == std::string::npos || text.find(marker, pos + 1u) != std::string::npos) {
+        throw std::logic_error("table stepper: the marker of the fused angle reduction must occur exactly once in the kernel");
+    }
+    const auto line = text.rfind('\n', pos) + 1u;
+    const auto indent = text.substr(line, pos - line);
+    std::string code;
+    for (const auto i : opts.angle_reduce) {
+        code += indent + "if (i == " + std::to_string(i) + "u) res = hy_angle_red(res);\n";
+    }
+    text.replace(line, pos + marker.size() - line, code);
+}
+
 } // namespace table_detail
 
 emitted_module emit_staged(const taylor_program &, const emit_options &, std::string &why_not);
@@ -948,13 +971,15 @@ emitted_module emit_table(const taylor_program &p, const emit_options &opts)
     }
 
     std::ostringstream src;
-    src << emit_detail::prelude << emit_detail::rules_source(p);
+    src << emit_detail::prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
     emit_detail::emit_dout(src, p, opts);
     table_detail::emit_tables_and_rules(src, p, opts, "", "64u");
     src << table_hbm_kernel_code;
 
     emitted_module ret;
     ret.source = src.str();
+    table_detail::expand_angle_reduce_marker(ret.source, opts);
+    ret.angle_reduce_fused = !opts.angle_reduce.empty();
     ret.kernel_name = "hy_taylor";
     ret.dout_name = "hy_dout";
     ret.mode = emit_mode::table;

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -179,6 +180,79 @@ struct tab_core::impl {
     mutable device_buffer snap_state, snap_thi, snap_tlo;
     mutable bool fix_step_limit = false;
     bool force_lockstep = false;
+    // ---- callback::angle_reducer ----
+    // Options the stepper was generated with, and the stepper variants with a fused reduction, keyed by the sorted list of
+    // reduced state variables: generated and compiled on first use (the compiled code objects live in the process-wide,
+    // reference-counted caches of hip_backend.cpp like every other module), or the reason why the generator declined.
+    emit_options eo;
+    struct ar_variant {
+        emitted_module em;
+        std::shared_ptr<const compiled_module> cm;
+        std::unique_ptr<device_module> dm;
+        std::string why_not;
+    };
+    std::map<std::vector<std::uint32_t>, ar_variant> ar_variants;
+    double ar_compile_seconds = 0;
+    // Stand-alone kernel hy_angle_reduce and the index list it last ran with.
+    mutable std::unique_ptr<aux_module> ar_mod;
+    device_buffer d_ar_idx;
+    std::vector<std::uint32_t> ar_idx_dev;
+    // The callback of the running propagate_*() is a pure angle_reducer (set); how the callback of the last one ran.
+    bool cb_is_reducer = false;
+    int last_cb_path = 0;
+    ar_variant &get_ar_variant(const std::vector<std::uint32_t> &idx)
+    {
+        auto it = ar_variants.find(idx);
+        if (it == ar_variants.end()) {
+            ar_variant v;
+            auto o = eo;
+            o.angle_reduce = idx;
+            v.em = emit_angle_reduce_variant(prog, o, v.why_not);
+            if (!v.em.source.empty()) {
+                const detail::stopwatch sw;
+                v.cm = hiprtc_compile(v.em);
+                ar_compile_seconds = v.cm->compile_seconds;
+                detail::log_message(log_level::trace, "angle_reducer: stepper variant compilation runtime: " + sw.str());
+            }
+            it = ar_variants.emplace(idx, std::move(v)).first;
+        }
+        return it->second;
+    }
+    // One propagate-mode (mode 1) launch of `mod` - the stepper, or a variant of it - over the device-resident state: every
+    // lane runs its own adaptive loop up to its final time or max_steps. scalar_tf: the final time of every lane, or nullptr
+    // when the per-lane final times are in d_tfhi / d_tflo already.
+    void launch_propagate(device_module &mod, const double *scalar_tf, const std::vector<double> &max_delta_ts,
+                          std::size_t max_steps, bool wtc)
+    {
+        d_counters.zero(stream);
+        auto a = base_args();
+        if (scalar_tf != nullptr) {
+            a.tfin_hi = nullptr;
+            a.tfin_lo = nullptr;
+            a.tfin_s_hi = *scalar_tf;
+            a.tfin_s_lo = 0.;
+        }
+        if (max_delta_ts.empty()) {
+            a.lim = nullptr;
+        } else {
+            d_lim.upload(max_delta_ts.data(), max_delta_ts.size() * sizeof(double), stream);
+            d_lim_src = nullptr;
+        }
+        if (wtc && is_cluster()) {
+            ensure_tc();
+            a.tc = d_tc.as<double>();
+        }
+        a.mode = 1;
+        a.max_steps = max_steps;
+        keep_written_tc(wtc);
+        if (batch_semantics == 0) {
+            snapshot_for_rollback();
+        }
+        mod.launch_taylor(a);
+        after_kernel(wtc);
+        prop_res_dev_newer = true;
+        step_res_dev_newer = false;
+    }
     void snapshot_for_rollback()
     {
         const auto sb = d_state.bytes(), tb = d_thi.bytes();
@@ -820,6 +894,7 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
             ed_max_detected(d.order, static_cast<std::uint32_t>(d.tes.size()), static_cast<std::uint32_t>(d.ntes.size()))));
     }
 
+    d.eo = eo;
     d.sys = std::move(sys);
     d.last_h.assign(d.N, 0.);
     d.d_out.assign(static_cast<std::size_t>(d.dim) * d.N, 0.);
@@ -868,6 +943,7 @@ tab_core::tab_core(const tab_core &o) : m_impl(o.m_impl ? std::make_unique<impl>
     d.dim = s.dim;
     d.device = s.device;
     d.emitted = s.emitted;
+    d.eo = s.eo;
     d.cmod = s.cmod;
     d.cluster_events = s.cluster_events;
     d.ev_emitted = s.ev_emitted;
@@ -2030,7 +2106,7 @@ void tab_core::step(const std::vector<double> &max_delta_ts, bool wtc)
 // lane - an error path - is rolled back to the snapshot taken before the launch and re-run through the lock-step loop,
 // which implements the reference's semantics iteration by iteration.
 void tab_core::finish_device_propagate(const std::vector<double> &ts, std::size_t max_steps,
-                                       const std::vector<double> &max_delta_ts, bool wtc)
+                                       const std::vector<double> &max_delta_ts, bool wtc, const cb_t &cb)
 {
     auto &d = *m_impl;
     if (d.batch_semantics != 0) {
@@ -2057,12 +2133,13 @@ void tab_core::finish_device_propagate(const std::vector<double> &ts, std::size_
             f = false;
         }
     } guard(d.force_lockstep);
-    propagate_until(ts, max_steps, max_delta_ts, {}, wtc, false);
+    // (cb: the fused angle reduction falls back to the callback after every sweep; its pre_hook() has run already.)
+    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, false);
 }
 
 void tab_core::propagate_for(const std::vector<double> &delta_ts, std::size_t max_steps,
                              const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                             const pre_t &pre)
+                             const pre_t &pre, const red_t &red)
 {
     auto &d = *m_impl;
     if (delta_ts.size() != 1u && delta_ts.size() != d.N) {
@@ -2092,16 +2169,21 @@ void tab_core::propagate_for(const std::vector<double> &delta_ts, std::size_t ma
             flag = false;
         }
     } guard(d.dl_times_ok);
-    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, c_out, pre);
+    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, c_out, pre, red);
 }
 
 // Reference: propagate_until_impl(), src/taylor_adaptive_batch.cpp:1137-1534.
 void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_steps,
                                const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                               const pre_t &pre)
+                               const pre_t &pre, const red_t &red)
 {
     auto &d = *m_impl;
     const auto N = d.N;
+    // (The re-run of a rolled-back fused propagation keeps the kind of its callback.)
+    if (!d.force_lockstep) {
+        d.cb_is_reducer = cb && red;
+    }
+    d.last_cb_path = 0;
 
     const auto check_mdts = [&]() {
         if (!max_delta_ts.empty() && max_delta_ts.size() != N) {
@@ -2136,32 +2218,7 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
         check_mdts();
         d.prop_res_override.reset();
     d.fix_step_limit = false;
-        d.d_counters.zero(d.stream);
-        auto a = d.base_args();
-        a.tfin_hi = nullptr;
-        a.tfin_lo = nullptr;
-        a.tfin_s_hi = ts_[0];
-        a.tfin_s_lo = 0.;
-        if (max_delta_ts.empty()) {
-            a.lim = nullptr;
-        } else {
-            d.d_lim.upload(max_delta_ts.data(), max_delta_ts.size() * sizeof(double), d.stream);
-            d.d_lim_src = nullptr;
-        }
-        if (wtc && d.is_cluster()) {
-            d.ensure_tc();
-            a.tc = d.d_tc.as<double>();
-        }
-        a.mode = 1;
-        a.max_steps = max_steps;
-        d.keep_written_tc(wtc);
-        if (d.batch_semantics == 0) {
-            d.snapshot_for_rollback();
-        }
-        d.dmod->launch_taylor(a);
-        d.after_kernel(wtc);
-        d.prop_res_dev_newer = true;
-        d.step_res_dev_newer = false;
+        d.launch_propagate(*d.dmod, &ts_[0], max_delta_ts, max_steps, wtc);
         finish_device_propagate(ts_, max_steps, max_delta_ts, wtc);
         return;
     }
@@ -2234,36 +2291,67 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
         d.before_kernel();
         d.d_tfhi.upload(tf_hi.data(), tf_hi.size() * sizeof(double), d.stream);
         d.d_tflo.upload(tf_lo.data(), tf_lo.size() * sizeof(double), d.stream);
-        d.d_counters.zero(d.stream);
-        auto a = d.base_args();
-        if (max_delta_ts.empty()) {
-            a.lim = nullptr;
-        } else {
-            d.d_lim.upload(max_delta_ts.data(), max_delta_ts.size() * sizeof(double), d.stream);
-            d.d_lim_src = nullptr;
-        }
-        if (wtc && d.is_cluster()) {
-            d.ensure_tc();
-            a.tc = d.d_tc.as<double>();
-        }
-        a.mode = 1;
-        a.max_steps = max_steps;
-        d.keep_written_tc(wtc);
-        if (d.batch_semantics == 0) {
-            d.snapshot_for_rollback();
-        }
-        d.dmod->launch_taylor(a);
-        d.after_kernel(wtc);
-        d.prop_res_dev_newer = true;
-        d.step_res_dev_newer = false;
+        d.launch_propagate(*d.dmod, nullptr, max_delta_ts, max_steps, wtc);
         finish_device_propagate(ts_, max_steps, max_delta_ts, wtc);
         return;
+    }
+
+    // callback::angle_reducer alone, no continuous output, no events: the persistent kernel of the stepper variant which
+    // reduces the flagged state variables of a system right after each of its state updates. Every system
+    // takes at least one - possibly zero-length - step in the kernel, like in the reference's loop, hence every system is
+    // reduced at least once. Step limits, outcomes, counters and the safety net of the default semantics are those of the
+    // propagation without a callback; the re-run after a rollback goes through the lock-step loop with the callback.
+    bool pre_done = false;
+    if (cb && red && !c_out && !d.has_events() && !ref_semantics) {
+        if (pre) {
+            const auto gen = d.time_gen;
+            pre();
+            if (d.time_gen != gen) {
+                throw std::runtime_error("The invocation of the callback passed to propagate_until() resulted in the "
+                                         "alteration of the time coordinate of the integrator - this is not supported");
+            }
+        }
+        pre_done = true;
+        const auto idx = red();
+        // (The pre_hook() has just rebuilt the indices from the system of this integrator: they fit it.)
+        auto *var = idx.empty() ? nullptr : &d.get_ar_variant(idx);
+        if (var != nullptr && var->cm) {
+            detail::log_message(log_level::info, "propagate_until(): angle_reducer fused into the propagate kernel of the stepper ("
+                                                     + get_codegen_info() + ")");
+            d.before_kernel();
+            if (!var->dm) {
+                var->dm = std::make_unique<device_module>(var->cm, d.device);
+            }
+            var->dm->set_stream(d.stream);
+            // (One final time for every lane travels as a kernel argument, per-lane ones as two arrays.)
+            const bool scalar_tf = ts_.size() == 1u;
+            if (!scalar_tf) {
+                d.d_tfhi.upload(tf_hi.data(), tf_hi.size() * sizeof(double), d.stream);
+                d.d_tflo.upload(tf_lo.data(), tf_lo.size() * sizeof(double), d.stream);
+            }
+            d.launch_propagate(*var->dm, scalar_tf ? &ts_[0] : nullptr, max_delta_ts, max_steps, wtc);
+            d.last_cb_path = 3;
+            finish_device_propagate(ts_, max_steps, max_delta_ts, wtc, cb);
+            return;
+        }
+        detail::log_message(log_level::info,
+                            "propagate_until(): angle_reducer applied by hy_angle_reduce after every sweep of the lock-step loop: "
+                                + (var != nullptr ? var->why_not : std::string("no state variable of the system is reduced")));
     }
 
     // Lock-step propagation with a callback executed after every sweep and/or the recording of the
     // continuous output: the reference's loop, one single-step kernel launch per iteration.
     // The pre_hook() of the step callback, once, before the first step (src/taylor_adaptive_batch.cpp:1356-1365).
-    if (cb && pre) {
+    if (cb) {
+        d.last_cb_path = d.cb_is_reducer ? 2 : 1;
+        if (d.cb_is_reducer && !pre_done && !d.force_lockstep) {
+            detail::log_message(log_level::info,
+                                "propagate_until(): angle_reducer applied by hy_angle_reduce after every sweep of the lock-step loop ("
+                                    + std::string(c_out ? "continuous output" : (d.has_events() ? "events" : "lock-step semantics"))
+                                    + ")");
+        }
+    }
+    if (cb && pre && !pre_done) {
         const auto gen = d.time_gen;
         pre();
         if (d.time_gen != gen) {
@@ -2870,7 +2958,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
 // grid[point * N + lane]; return value ret[(point * dim + var) * N + lane], NaN where not reached.
 std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                              const std::vector<double> &max_delta_ts_, const cb_t &cb, double *d_out,
-                                             const pre_t &pre)
+                                             const pre_t &pre, const red_t &red)
 {
     auto &d = *m_impl;
     const auto N = d.N;
@@ -3009,8 +3097,73 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     // Device-resident lock-step loop: the step kernel and a post-step kernel (bookkeeping of the reference's loop, dense
     // output at the grid points covered by the step, next step limit) alternate without any per-lane host work; the host
     // reads three counters per sweep and runs the callback, if any.
+    // (A pure angle_reducer callback runs hy_angle_reduce after every sweep: no fused grid launches.)
+    d.last_cb_path = cb ? (red ? 2 : 1) : 0;
     propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb);
     return retval;
+}
+
+// ---- callback::angle_reducer ----
+void tab_core::angle_reduce(const std::vector<std::uint32_t> &idx)
+{
+    auto &d = *m_impl;
+    if (idx.empty()) {
+        return;
+    }
+    if (!std::is_sorted(idx.begin(), idx.end()) || idx.back() >= d.dim) {
+        throw std::invalid_argument("Invalid list of state variables passed to the angle reduction of an adaptive Taylor "
+                                    "integrator in batch mode");
+    }
+    if (d.sticky_host_ptr || d.host_newer || !d.dmod) {
+        // The host mirror is the newer copy (or a mutable pointer to it is out, and it is refreshed after every launch and
+        // uploaded before the next one anyway): reduce it in place.
+        d.to_host();
+        for (const auto i : idx) {
+            auto *row = d.state.data() + static_cast<std::size_t>(i) * d.N;
+            for (std::uint32_t s = 0; s < d.N; ++s) {
+                row[s] = angle_reduce_host(row[s]);
+            }
+        }
+        d.host_newer = true;
+        return;
+    }
+    if (!d.ar_mod) {
+        d.ar_mod = std::make_unique<aux_module>(hiprtc_compile_source(make_angle_reduce_source()), d.device);
+    }
+    if (idx != d.ar_idx_dev) {
+        d.d_ar_idx = device_buffer(idx.size() * sizeof(std::uint32_t), d.device);
+        d.ar_idx_dev = idx;
+        d.d_ar_idx.upload(d.ar_idx_dev.data(), d.ar_idx_dev.size() * sizeof(std::uint32_t), d.stream);
+    }
+    const struct {
+        double *state;
+        const unsigned *idx;
+        unsigned long long N;
+        unsigned n_idx;
+    } a{d.d_state.as<double>(), d.d_ar_idx.as<unsigned>(), d.N, static_cast<unsigned>(idx.size())};
+    d.ar_mod->launch("hy_angle_reduce", static_cast<std::uint64_t>(d.N) * idx.size(), 256, &a, sizeof(a), d.stream);
+    // The device copy of the state is the newer one; callers who hold references to the host mirror see it refreshed.
+    d.dev_newer = true;
+    if (d.sticky_const_refs) {
+        d.to_host();
+    }
+}
+
+int tab_core::get_last_callback_path() const
+{
+    return m_impl->last_cb_path;
+}
+
+std::string tab_core::get_angle_reduce_variant_source(const std::vector<std::uint32_t> &idx, std::string &why_not) const
+{
+    auto o = m_impl->eo;
+    o.angle_reduce = idx;
+    return emit_angle_reduce_variant(m_impl->prog, o, why_not).source;
+}
+
+double tab_core::get_angle_reduce_compile_seconds() const
+{
+    return m_impl->ar_compile_seconds;
 }
 
 double *tab_core::device_state()
@@ -3275,6 +3428,13 @@ void tab_core::set_device(int device)
     d.ed_mod.reset();
     d.grid_mod.reset();
     d.evj_mod.reset();
+    d.ar_mod.reset();
+    d.d_ar_idx = {};
+    d.ar_idx_dev.clear();
+    for (auto &[k, v] : d.ar_variants) {
+        (void)k;
+        v.dm.reset();
+    }
     if (d.log_rows != 0u && d.log_stash.empty()) {
         d.log_stash.resize(static_cast<std::size_t>(d.log_rows) * d.log_row_doubles());
         device_copy(d.log_stash.data(), d.d_ev_log.get(), d.log_stash.size() * sizeof(double), d.device, d.stream);

@@ -195,19 +195,36 @@ public:
     using cb_t = std::function<bool()>;
     // ts: final times (size 1 = scalar splat, else batch_size); max_delta_ts: empty or batch_size.
     void finish_device_propagate(const std::vector<double> &ts, std::size_t max_steps, const std::vector<double> &max_delta_ts,
-                                 bool wtc);
+                                 bool wtc, const cb_t &cb = {});
     // pre: the pre_hook() of the step callback (include/heyoka/step_callback.hpp:46-62), run once after the validation of
     // the arguments and before the first step (src/taylor_adaptive_batch.cpp:1356-1365, :1782-1791); it must not move the
     // time coordinate.
     using pre_t = std::function<void()>;
+    // red: set when the step callback is a callback::angle_reducer, or a set whose members all are (angle_reducer.hpp):
+    // called after pre, it returns the sorted union of the indices of the state variables they reduce. propagate_until() /
+    // propagate_for() then run the persistent kernel of a stepper variant which reduces those variables after every state
+    // update - one launch, cb is not invoked - whenever there is no continuous output, there are no events and the generator
+    // of the stepper implements the variant; otherwise cb runs after every sweep of the lock-step loop as usual.
+    using red_t = std::function<std::vector<std::uint32_t>()>;
     void propagate_until(const std::vector<double> &ts, std::size_t max_steps, const std::vector<double> &max_delta_ts,
-                         const cb_t &cb, bool wtc, bool c_out, const pre_t &pre = {});
+                         const cb_t &cb, bool wtc, bool c_out, const pre_t &pre = {}, const red_t &red = {});
     void propagate_for(const std::vector<double> &delta_ts, std::size_t max_steps,
                        const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                       const pre_t &pre = {});
+                       const pre_t &pre = {}, const red_t &red = {});
     std::vector<double> propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                        const std::vector<double> &max_delta_ts, const cb_t &cb,
-                                       double *d_out = nullptr, const pre_t &pre = {});
+                                       double *d_out = nullptr, const pre_t &pre = {}, const red_t &red = {});
+    // x -= 2 pi floor(x / 2 pi) on the state variables idx (sorted, < get_dim()) of every system - what the call operator
+    // of callback::angle_reducer does: kernel hy_angle_reduce on the integrator's stream over the device-resident state
+    // (no download, no switch to eager synchronisation), or on the host mirror when that is the newer copy.
+    void angle_reduce(const std::vector<std::uint32_t> &idx);
+    // How the step callback of the last propagate_*() ran: 0 no callback, 1 host callback after every sweep, 2 a pure
+    // angle_reducer callback after every sweep (hy_angle_reduce), 3 fused into the propagate kernel.
+    [[nodiscard]] int get_last_callback_path() const;
+    // HIP source of the stepper variant with the reduction of idx fused in (empty + the reason if the generator declines),
+    // and the seconds its last compilation took (0: never compiled / cached).
+    [[nodiscard]] std::string get_angle_reduce_variant_source(const std::vector<std::uint32_t> &idx, std::string &why_not) const;
+    [[nodiscard]] double get_angle_reduce_compile_seconds() const;
     // Device-resident loop of propagate_grid(): see taylor_adaptive_batch.cpp.
     void propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                     const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
@@ -294,6 +311,11 @@ private:
 };
 
 std::vector<double> make_vector_from(double x);
+
+// If cb holds a callback::angle_reducer, or a callback set whose members all are angle_reducers (angle_reducer.hpp): the
+// function which returns the sorted union of their indices (tab_core::red_t, to be called after the pre_hook());
+// empty otherwise. Defined in angle_reducer.cpp.
+tab_core::red_t angle_reducer_indices_of(step_cb_wrap<taylor_adaptive_batch<double>> &cb);
 
 // HIP source of the post-step kernel of the device-resident propagate_grid() loop (exposed for the build-time
 // compilation check).
@@ -585,13 +607,17 @@ class taylor_adaptive_batch<double>
         }
         detail::tab_core::cb_t cb;
         detail::tab_core::pre_t pre;
+        detail::tab_core::red_t red;
         if (*user_cb) {
             cb = [this, user_cb]() { return (*user_cb)(*this); };
             pre = [this, user_cb]() { user_cb->pre_hook(*this); };
+            // (The library's own angle_reducer is recognised by type: the core may apply it inside the propagate kernel.)
+            red = detail::angle_reducer_indices_of(*user_cb);
         }
         const auto wtc = static_cast<bool>(kw::get(kw::write_tc, false, kw_args...));
         const auto c_out = static_cast<bool>(kw::get(kw::c_output, false, kw_args...));
-        return std::tuple{max_steps, std::move(max_delta_ts), std::move(cb), std::move(user_cb), wtc, c_out, std::move(pre)};
+        return std::tuple{max_steps, std::move(max_delta_ts), std::move(cb), std::move(user_cb), wtc, c_out, std::move(pre),
+                          std::move(red)};
     }
 
 public:
@@ -863,43 +889,43 @@ public:
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_until(const std::vector<double> &ts,
                                                                            KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_until(ts, max_steps, mdts, cb, wtc, c_out, pre);
+        m_core.propagate_until(ts, max_steps, mdts, cb, wtc, c_out, pre, red);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_until(double t, KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_until(std::vector<double>{t}, max_steps, mdts, cb, wtc, c_out, pre);
+        m_core.propagate_until(std::vector<double>{t}, max_steps, mdts, cb, wtc, c_out, pre, red);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_for(const std::vector<double> &dts,
                                                                          KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_for(dts, max_steps, mdts, cb, wtc, c_out, pre);
+        m_core.propagate_for(dts, max_steps, mdts, cb, wtc, c_out, pre, red);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_for(double dt, KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_for(std::vector<double>{dt}, max_steps, mdts, cb, wtc, c_out, pre);
+        m_core.propagate_for(std::vector<double>{dt}, max_steps, mdts, cb, wtc, c_out, pre, red);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<step_callback_batch<double>, std::vector<double>> propagate_grid(std::vector<double> grid,
                                                                                KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre);
+        auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red);
         return {std::move(*user_cb), std::move(ret)};
     }
 

@@ -7,6 +7,7 @@
 #include "../../heyoka_amd/csrc/model.hpp"
 #include "../../heyoka_amd/csrc/cfunc.hpp"
 #include "../../heyoka_amd/csrc/logging.hpp"
+#include "../../heyoka_amd/csrc/angle_reducer.hpp"
 #include "math/constants.hpp"
 #include "math/kepDE.hpp"
 #include "math/kepF.hpp"

@@ -424,6 +424,37 @@ int hy_tab_propagate_for_cbs(hy_tab, const double *dts, size_t n_dts, uint64_t m
                              size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, int write_tc, int c_output);
 int hy_tab_propagate_grid_cbs(hy_tab, const double *grid, size_t n_grid, uint64_t max_steps, const double *max_delta_ts,
                               size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, double *out);
+/* callback::angle_reducer (include/heyoka/callback/angle_reducer.hpp, src/callback/angle_reducer.cpp): the step callback which
+ * keeps the named state variables in [0, 2 pi), x -= twopi * floor(x / twopi) with twopi = 0x1.921fb54442d18p+2 and every
+ * operation rounded (no FMA); non-finite values are left alone. hy_angle_reducer_new() fails (NULL, hy_last_error()) on an
+ * empty list or a non-variable; hy_angle_reducer_new_default() gives the default-constructed object, which every use rejects.
+ * hy_angle_reducer_call / hy_angle_reducer_pre_hook are ready-made members for a hy_step_callback_desc with the handle as
+ * user_data. The library recognises them by address: the reduction runs on the device over the device-resident state
+ * (kernel hy_angle_reduce after every sweep), and when every member of the callback set is one, propagate_until() /
+ * propagate_for() without continuous output on an integrator without events run ONE launch of a stepper variant which
+ * reduces inside the propagate kernel (generators: straight-line, table, first-generation / multi-class wave-cluster). */
+typedef struct hy_angle_reducer_s *hy_angle_reducer;
+hy_angle_reducer hy_angle_reducer_new(const hy_expr *vars, size_t n);
+hy_angle_reducer hy_angle_reducer_new_default(void);
+hy_angle_reducer hy_angle_reducer_clone(hy_angle_reducer);
+void hy_angle_reducer_free(hy_angle_reducer);
+/* "Angle reducer: {x, y}" / "Angle reducer (default constructed)". Caller frees. */
+char *hy_angle_reducer_str(hy_angle_reducer);
+int hy_angle_reducer_call(hy_tab, void *user);     /* 1, or -1 on error (hy_last_error()) */
+int hy_angle_reducer_pre_hook(hy_tab, void *user); /* 0, or 1 on error */
+/* How the step callback of the last propagate_*() ran: 0 none, 1 host callback after every sweep, 2 angle reduction on the
+ * device after every sweep, 3 angle reduction fused into the propagate kernel. */
+int hy_tab_last_callback_path(hy_tab);
+/* Beyond the constructor, the destructor and the two ready-made members: hy_angle_reducer_new_default / _clone / _str serve
+ * the language bindings (default construction, copy, repr). The four entry points below are INTERNAL hooks of the test suite and
+ * of the build-time compilation check, not part of the supported interface. */
+/* Source of the stepper variant with the reduction of the state variables idx[0..n) (sorted) fused in; "" and the reason in
+ * *why_not (may be NULL) when the generator of this integrator declines. Seconds of its last compilation. Caller frees. */
+char *hy_tab_angle_reduce_variant_source(hy_tab, const uint32_t *idx, size_t n, char **why_not);
+double hy_tab_angle_reduce_compile_seconds(hy_tab);
+/* Source of the module of the stand-alone kernel hy_angle_reduce, and the same arithmetic on the host. Caller frees. */
+char *hy_angle_reduce_source(void);
+double hy_angle_reduce_host(double x);
 /* ------------------------------------------------------------------------------------------------
  * continuous_output_batch<double> (include/heyoka/continuous_output.hpp:151-204,
  * src/continuous_output.cpp:602-1236): the optional<continuous_output_batch> slot of the tuple returned
