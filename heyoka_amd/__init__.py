@@ -993,7 +993,7 @@ class taylor_adaptive_batch:
                  _events=None, **ignored_llvm_kwargs):
         # MI355X extensions (hy_tab_config, include/heyoka_amd.h): emitter in (None, "unrolled", "cluster", "table",
         # "block"); cluster_kernel in (None, "v5", "v3", "v2", "v1"); exact_division; events_on_cluster (None / False);
-        # batch_semantics in (None = "reference", "lockstep", "per_lane").
+        # batch_semantics in (None = "reference", "lockstep", "per_lane", "independent").
         # LLVM-only keyword arguments of the reference (opt_level, fast_math, force_avx512,
         # slp_vectorize, code_model, parjit) are accepted and ignored.
         for k in ignored_llvm_kwargs:
@@ -1041,7 +1041,7 @@ class taylor_adaptive_batch:
         cfg.events_on_cluster = 1 if events_on_cluster is False else 0
         cfg.sum_order = _enum_arg("sum_order", sum_order, {None: 0, "auto": 0, "pairwise": 1, "running": 2})
         cfg.batch_semantics = _enum_arg("batch_semantics", batch_semantics,
-                                        {None: 0, "reference": 0, "lockstep": 1, "per_lane": 2})
+                                        {None: 0, "reference": 0, "lockstep": 1, "per_lane": 2, "independent": 3})
         if tol is not None and float(tol) == 0.0:
             cfg.tol = 0.0
         t_events, nt_events = list(t_events), list(nt_events)
@@ -1126,7 +1126,16 @@ class taylor_adaptive_batch:
         raise_for(lib.hy_tab_get_event_stats(self._h, out.ctypes.data))
         keys = ("steps", "ms_upload", "ms_stepper", "ms_detection", "ms_bookkeeping_flags", "ms_update_records",
                 "tc_regeneration_launches", "systems_with_events")
-        return dict(zip(keys, [float(x) for x in out]))
+        ret = dict(zip(keys, [float(x) for x in out]))
+        # (Whether the events are applied on the device - no records, no per-event host work; known without a GPU.)
+        ret["events_on_device"] = bool(lib.hy_tab_events_on_device(self._h))
+        return ret
+
+    @property
+    def n_retired(self):
+        """batch_semantics="independent": systems retired (stopping terminal event or non-finite state) by the last
+        propagate_until() / propagate_for() / propagate_grid() which went through the sweep loop."""
+        return int(lib.hy_tab_get_n_retired(self._h))
 
     # ---- event log (native_event_recorder) ----
     @property

@@ -193,6 +193,8 @@ SIGNATURES = [
     ("hy_event_detection_source", c_void_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("hy_tab_set_event_timing", c_int, [c_void_p, c_int]),
     ("hy_tab_get_event_stats", c_int, [c_void_p, c_void_p]),
+    ("hy_tab_get_n_retired", ctypes.c_uint64, [c_void_p]),
+    ("hy_tab_events_on_device", c_int, [c_void_p]),
     ("hy_tab_reset_cooldowns", c_int, [c_void_p, ctypes.c_int64]),
     ("hy_tab_get_te_cooldowns", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     ("hy_tab_copy", c_void_p, [c_void_p]),

@@ -884,6 +884,15 @@ int hy_tab_get_event_stats(hy_tab t, double *out8)
     }
 }
 
+uint64_t hy_tab_get_n_retired(hy_tab t)
+{
+    return t->core.get_n_retired();
+}
+int hy_tab_events_on_device(hy_tab t)
+{
+    return t->core.events_on_device() ? 1 : 0;
+}
+
 // Native callbacks which count their invocations in the 64-bit integer behind `user` (the callbacks of an integrator run
 // serially on the host).
 // (Copies of an integrator made by ensemble_propagate_*() share `user` and run on one host thread per device: atomic.)

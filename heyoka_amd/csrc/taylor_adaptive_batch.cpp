@@ -71,6 +71,16 @@ struct grid_kargs {
     const unsigned *launch_nf;
     // (The grid index of every lane before this sweep's samples: hy_grid_unsample takes them back. Null: not kept.)
     unsigned *gidx_prev;
+    // Independent semantics (config::batch_semantics == 3), null / 0 otherwise. retired[N]: the sticky outcome of a system
+    // retired in this call (0: not retired); outcome_w: the outcome array, writable - the sticky outcome is put back after
+    // every zero-length step; counters[4] / [5] count the systems retired by events / as non-finite. override_oc:
+    // hy_indep_override only - the outcome (step_limit, cb_stop) of the systems which are neither done nor retired.
+    long long *retired;
+    long long *outcome_w;
+    long long override_oc;
+    // (... and the cooldown flags / durations of the terminal events, [n_te * N]: see hy_indep_retired(). Null: none.)
+    int *cd_active;
+    const double *cd_second;
 };
 
 // Code generator from the configuration field (0 automatic: the wave-cluster generator is tried first and falls back
@@ -335,6 +345,58 @@ struct tab_core::impl {
     mutable device_buffer d_ev_cursor, d_ev_rec, d_ev_upd, d_ev_counts, d_te_cd;
     // Every event callback is the library's counting callback: hy_ev_post applies the events itself (ep_kargs::native).
     mutable bool ev_native = false;
+    // ---- independent semantics (config::batch_semantics == 3) ----
+    // Library-side events: counting and recording callbacks; under the independent semantics also the terminal events
+    // WITHOUT a callback (plain stops: hy_ev_stop writes the stopping outcome behind hy_ev_native, d_te_stop holds the flags).
+    [[nodiscard]] bool event_is_native(const core_t_event &ev) const
+    {
+        return ev.native_counter != nullptr || ev.recorder || (batch_semantics == 3 && !ev.callback);
+    }
+    [[nodiscard]] bool all_events_native() const
+    {
+        return std::all_of(tes.begin(), tes.end(), [this](const auto &ev) { return event_is_native(ev); })
+               && std::all_of(ntes.begin(), ntes.end(), [](const auto &ev) { return ev.native_counter != nullptr || ev.recorder; });
+    }
+    mutable device_buffer d_te_stop;
+    // Sticky outcomes of the systems retired in the running call (0: not retired); the pointer is set while a sweep loop
+    // runs, null otherwise. n_retired / n_retired_nf: of the last sweep loop.
+    device_buffer d_retired;
+    const long long *retired_ptr = nullptr;
+    void ensure_grid_mod() const;
+    std::uint64_t n_retired = 0, n_retired_nf = 0;
+    struct retirement_guard {
+        const long long *&p;
+        ~retirement_guard()
+        {
+            p = nullptr;
+        }
+    };
+    void log_sweep_loop(const char *what, std::size_t sweeps) const
+    {
+        if (detail::log_enabled(log_level::debug)) {
+            static const char *const names[] = {"reference", "lockstep", "per_lane", "independent"};
+            detail::log_message(log_level::debug,
+                                std::string(what) + " sweep loop: batch_semantics " + std::to_string(batch_semantics) + " ("
+                                    + names[batch_semantics] + "), " + std::to_string(sweeps) + " sweeps, "
+                                    + std::to_string(n_retired - n_retired_nf) + " systems retired by events, "
+                                    + std::to_string(n_retired_nf) + " retired as non-finite, events applied on the device: "
+                                    + ((has_events() && all_events_native()) ? "yes" : "no"));
+        }
+    }
+    long long *start_retirement()
+    {
+        n_retired = 0;
+        n_retired_nf = 0;
+        if (batch_semantics != 3) {
+            return nullptr;
+        }
+        if (d_retired.bytes() != N * sizeof(long long)) {
+            d_retired = device_buffer(N * sizeof(long long), device);
+        }
+        d_retired.zero(stream);
+        retired_ptr = d_retired.as<long long>();
+        return d_retired.as<long long>();
+    }
     // (Page-locked landing area of the event records of a step: see pinned_buffer.)
     mutable pinned_buffer h_ev_rec;
     // ---- event log (core_*_event::recorder, see event_detection.hpp) ----
@@ -661,9 +723,9 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
         throw std::invalid_argument("Invalid wave-cluster generator selected in an adaptive Taylor integrator in batch mode: "
                                     + std::to_string(d.cluster_kernel) + " (0 automatic, or 5, 3, 2, 1)");
     }
-    if (d.batch_semantics < 0 || d.batch_semantics > 2) {
+    if (d.batch_semantics < 0 || d.batch_semantics > 3) {
         throw std::invalid_argument("Invalid batch semantics selected in an adaptive Taylor integrator in batch mode: "
-                                    + std::to_string(d.batch_semantics) + " (0 reference, 1 lock-step loop, 2 per lane)");
+                                    + std::to_string(d.batch_semantics) + " (0 reference, 1 lock-step loop, 2 per lane, 3 independent)");
     }
     // Developer overrides from the environment (experiments and the test matrix): they map onto the same fields.
     if (const char *m = std::getenv("HEYOKA_AMD_EMIT_MODE")) {
@@ -1483,16 +1545,16 @@ void tab_core::impl::ensure_event_buffers()
         d_ev_cursor = device_buffer(4u * sizeof(unsigned long long), device);
         // Library-side callbacks only - counting (core_*_event::native_counter) or recording (core_*_event::recorder): the
         // events are applied on the device.
-        ev_native = true;
+        // (Independent semantics: terminal events without a callback count as library-side, see event_is_native().)
+        ev_native = all_events_native();
         std::vector<double> te_cd;
-        std::vector<int> is_rec;
+        std::vector<int> is_rec, te_stop;
         for (const auto &ev : tes) {
-            ev_native = ev_native && (ev.native_counter != nullptr || ev.recorder);
             te_cd.push_back(ev.cooldown);
             is_rec.push_back(ev.recorder ? 1 : 0);
+            te_stop.push_back((batch_semantics == 3 && !ev.callback) ? 1 : 0);
         }
         for (const auto &ev : ntes) {
-            ev_native = ev_native && (ev.native_counter != nullptr || ev.recorder);
             is_rec.push_back(ev.recorder ? 1 : 0);
         }
         if (ev_has_rec) {
@@ -1510,6 +1572,10 @@ void tab_core::impl::ensure_event_buffers()
             d_te_cd = device_buffer(std::max<std::size_t>(te_cd.size(), 1u) * sizeof(double), device);
             if (!te_cd.empty()) {
                 d_te_cd.upload(te_cd.data(), te_cd.size() * sizeof(double), stream);
+            }
+            if (std::any_of(te_stop.begin(), te_stop.end(), [](int f) { return f != 0; })) {
+                d_te_stop = device_buffer(te_stop.size() * sizeof(int), device);
+                d_te_stop.upload(te_stop.data(), te_stop.size() * sizeof(int), stream);
             }
         }
         std::vector<int> dirs;
@@ -1805,6 +1871,19 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
     ed_mod->launch("hy_ev_post", N, 256, &pa, sizeof(pa), stream);
     if (ev_native && cur[0] != 0u) {
         ed_mod->launch("hy_ev_native", N, 256, &pa, sizeof(pa), stream);
+        if (d_te_stop.bytes() != 0u) {
+            // Independent semantics: terminal events without a callback are applied on the device as well. hy_ev_native has
+            // given them their cooldown and the continuing outcome `index`; hy_ev_stop (post-step module: the text of the
+            // event-detection module is pinned) turns it into the stopping outcome -index - 1 where the flag is set.
+            const struct {
+                long long *outcome;
+                const int *te_stop;
+                unsigned long long N;
+                unsigned n_te, pad;
+            } sa{d_outcome.as<long long>(), d_te_stop.as<int>(), N, n_te, 0u};
+            ensure_grid_mod();
+            grid_mod->launch("hy_ev_stop", N, 256, &sa, sizeof(sa), stream);
+        }
     }
     if (log_ub != 0u) {
         // Rows of the log from the events of this step (event_detection.hpp): rows per lane and per workgroup, exclusive
@@ -2179,6 +2258,8 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
 {
     auto &d = *m_impl;
     const auto N = d.N;
+    d.n_retired = 0;
+    d.n_retired_nf = 0;
     // (The re-run of a rolled-back fused propagation keeps the kind of its callback.)
     if (!d.force_lockstep) {
         d.cb_is_reducer = cb && red;
@@ -2382,13 +2463,10 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
         // sweep, runs the callback and (for the continuous output) appends the coefficients device-to-device.
         d.ensure_device();
         d.ensure_tc();
-        if (!d.grid_mod) {
-            d.grid_mod = std::make_unique<aux_module>(
-                hiprtc_compile_source(make_grid_source(d.order, d.dim, d.high_accuracy)), d.device);
-        }
+        d.ensure_grid_mod();
         const auto dsz = sizeof(double);
         device_buffer b_rem_hi(N * dsz, d.device), b_rem_lo(N * dsz, d.device), b_mdt(N * dsz, d.device);
-        device_buffer b_tdir(N * sizeof(int), d.device), b_cnt(4u * sizeof(unsigned), d.device);
+        device_buffer b_tdir(N * sizeof(int), d.device), b_cnt(6u * sizeof(unsigned), d.device);
         std::vector<double> rhi(N), rlo(N), mdts(N);
         const std::vector<unsigned long long> ns0(N, 0u);
         for (std::uint32_t i = 0; i < N; ++i) {
@@ -2428,6 +2506,25 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
                 flag = old;
             }
         } tc_guard(d.ev_all_tc, static_cast<bool>(cob));
+        // Independent semantics (config::batch_semantics == 3): a stopping terminal event or a non-finite state
+        // retires ONE system (sticky outcome in d_retired, zero-length steps from then on); the loop ends when every system
+        // is done or retired, and a loop ended by max_steps / the callback overrides the outcomes of the others only.
+        auto *const retired = d.start_retirement();
+        const bool indep = retired != nullptr;
+        const impl::retirement_guard ret_guard{d.retired_ptr};
+        const auto finish = [&](const grid_kargs &a, std::optional<taylor_outcome> oc) {
+            if (oc) {
+                if (indep) {
+                    auto b = a;
+                    b.override_oc = static_cast<long long>(*oc);
+                    d.grid_mod->launch("hy_indep_override", N, 256, &b, sizeof(b), d.stream);
+                } else {
+                    d.prop_res_override = *oc;
+                }
+            }
+            d.log_sweep_loop("propagate_until()", iter_counter);
+            make_c_out();
+        };
         while (true) {
             if (d.has_events()) {
                 // (Callbacks of the events run inside: state, times, outcomes and cooldowns stay on the device.)
@@ -2441,15 +2538,19 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
                                b_rem_hi.as<double>(), b_rem_lo.as<double>(), b_mdt.as<double>(), b_tdir.as<int>(),
                                d.d_lim.as<double>(), nullptr, d.d_minh.as<double>(), d.d_maxh.as<double>(),
                                d.d_nsteps.as<unsigned long long>(), b_cnt.as<unsigned>(), N, 0u, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, nullptr};
+                               nullptr, nullptr, retired, indep ? d.d_outcome.as<long long>() : nullptr, 0,
+                               (indep && !d.tes.empty()) ? d.d_cd_active.as<int>() : nullptr,
+                               (indep && !d.tes.empty()) ? d.d_cd_second.as<double>() : nullptr};
             d.grid_mod->launch("hy_until_post", N, 256, &a, sizeof(a), d.stream);
-            unsigned cnt[3] = {0, 0, 0};
-            b_cnt.download(cnt, sizeof(cnt), d.stream);
+            unsigned cnt[6] = {0, 0, 0, 0, 0, 0};
+            b_cnt.download(cnt, (indep ? 6u : 3u) * sizeof(unsigned), d.stream);
+            d.n_retired = static_cast<std::uint64_t>(cnt[4]) + cnt[5];
+            d.n_retired_nf = cnt[5];
             // Outcomes of the last sweep + accumulated statistics: on the device.
             d.prop_res_dev_newer = true;
             d.step_res_dev_newer = true;
             if (cnt[1] != 0u) {
-                make_c_out();
+                finish(a, {});
                 return;
             }
             if (cob) {
@@ -2467,24 +2568,30 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
                                              "supported");
                 }
                 if (!ret_cb) {
-                    d.prop_res_override = taylor_outcome::cb_stop;
-                    make_c_out();
+                    finish(a, taylor_outcome::cb_stop);
                     return;
                 }
             }
-            // (cnt[2]: lanes stopped by a terminal event - the propagation of the whole batch ends, :1411, :1429.)
-            if (cnt[0] == N || cnt[2] != 0u) {
-                make_c_out();
+            // (cnt[2]: lanes stopped by a terminal event - the propagation of the whole batch ends, :1411, :1429. Independent
+            // semantics: they were retired, and counted in cnt[0].)
+            if (cnt[0] == N || (!indep && cnt[2] != 0u)) {
+                finish(a, {});
                 return;
             }
             if (iter_counter == max_steps) {
-                d.prop_res_override = taylor_outcome::step_limit;
-                make_c_out();
+                finish(a, taylor_outcome::step_limit);
                 return;
             }
         }
     }
 
+}
+
+void tab_core::impl::ensure_grid_mod() const
+{
+    if (!grid_mod) {
+        grid_mod = std::make_unique<aux_module>(hiprtc_compile_source(make_grid_source(order, dim, high_accuracy)), device);
+    }
 }
 
 std::optional<c_out_core> tab_core::take_c_output()
@@ -2537,6 +2644,11 @@ struct hy_grid_args {
     const double *grid_done;
     const unsigned *launch_nf;
     unsigned *gidx_prev;
+    i64 *retired;
+    i64 *outcome_w;
+    i64 override_oc;
+    int *cd_active;
+    const double *cd_second;
 };
 
 // Post-step kernel of the device-driven propagate_until() lock-step loop (callbacks / continuous output): the
@@ -2552,14 +2664,51 @@ __device__ __forceinline__ void hy_count(unsigned *p, bool pred)
     if (pred && (unsigned)__builtin_ctzll(m) == (threadIdx.x & 63u)) atomicAdd(p, (unsigned)__builtin_popcountll(m));
 }
 
+// Independent semantics (hy_grid_args::retired != nullptr; the branches below do not run otherwise). A system is retired by
+// the step which ends in a stopping terminal event (outcome -index - 1) or in a non-finite state: the outcome becomes sticky
+// in retired[i] (0: not retired) and the limit of its next steps is zero, so that it takes zero-length steps like a system
+// which has reached its final time - state, time, cooldowns, step count and min / max |h| stay those of that step. The
+// zero-length steps report time_limit: the sticky outcome is put back after each of them. counters[4] / [5]: systems
+// retired by events / as non-finite so far.
+// Returns true for a system retired in an EARLIER sweep: nothing else is to be done for it.
+__device__ __forceinline__ bool hy_indep_retired(const hy_grid_args &a, u64 i)
+{
+    const i64 so = a.retired[i];
+    if (so == 0) return false;
+    a.outcome_w[i] = so;
+    a.lim[i] = 0.0;
+    // (Frozen cooldowns: a zero-length step ages a cooldown by nothing, but it ends one of duration zero - the one the
+    // retiring event may have set.)
+    if (so != HY_OC_ERR_NF_STATE && a.cd_active != nullptr) {
+        const u64 p = (u64)(-so - 1) * a.N + i;
+        if (a.cd_second[p] == 0.0) a.cd_active[p] = 1;
+    }
+    hy_count(a.counters + 4, so != HY_OC_ERR_NF_STATE);
+    hy_count(a.counters + 5, so == HY_OC_ERR_NF_STATE);
+    return true;
+}
+
 extern "C" __global__ void __launch_bounds__(256) hy_until_post(const hy_grid_args a)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
     const u64 N = a.N;
     if (i >= N) return;
+    const bool indep = a.retired != nullptr;
+    if (indep && hy_indep_retired(a, i)) {
+        hy_count(a.counters, true);
+        return;
+    }
     const i64 oc = a.outcome[i];
     const double h = a.last_h[i];
     if (oc == HY_OC_ERR_NF_STATE) {
+        if (indep) {
+            // (Retired as non-finite: done as far as the loop is concerned, the other systems carry on.)
+            a.retired[i] = oc;
+            a.lim[i] = 0.0;
+            hy_count(a.counters, true);
+            hy_count(a.counters + 5, true);
+            return;
+        }
         hy_count(a.counters + 1, true);
         return;
     }
@@ -2570,9 +2719,17 @@ extern "C" __global__ void __launch_bounds__(256) hy_until_post(const hy_grid_ar
         a.max_h[i] = hy_max(a.max_h[i], ah);
     }
     // Stopping terminal event: outcome -index - 1 (src/taylor_adaptive_batch.cpp:1411).
-    hy_count(a.counters + 2, oc > HY_OC_SUCCESS && oc < 0);
+    const bool stopped = oc > HY_OC_SUCCESS && oc < 0;
+    hy_count(a.counters + 2, stopped);
     hy_df rem; rem.hi = a.rem_hi[i]; rem.lo = a.rem_lo[i];
-    hy_count(a.counters, h == rem.hi);
+    // (Independent semantics: the system retired by this step counts as done; the bookkeeping of the step is the one above
+    // and below - what the same step leaves behind when it ends the loop of the whole batch.)
+    const bool retire = indep && stopped;
+    if (retire) {
+        a.retired[i] = oc;
+        hy_count(a.counters + 4, true);
+    }
+    hy_count(a.counters, h == rem.hi || retire);
     if (h == rem.hi) {
         rem.hi = 0.0; rem.lo = 0.0;
     } else {
@@ -2585,7 +2742,35 @@ extern "C" __global__ void __launch_bounds__(256) hy_until_post(const hy_grid_ar
     double lim;
     if (a.t_dir[i] != 0) { m.hi = a.mdt[i]; lim = hy_df_lt(rem, m) ? rem.hi : m.hi; }
     else { m.hi = -a.mdt[i]; lim = hy_df_lt(m, rem) ? rem.hi : m.hi; }
-    a.lim[i] = lim;
+    a.lim[i] = retire ? 0.0 : lim;
+}
+
+// Independent semantics, events applied on the device: behind hy_ev_native, which has given the first terminal event of a
+// system its cooldown and the continuing outcome `index` - a terminal event WITHOUT a callback stops (te_stop[index] != 0:
+// the flag is data), outcome -index - 1.
+struct hy_ev_stop_args {
+    i64 *outcome;
+    const int *te_stop;
+    u64 N;
+    unsigned n_te, pad;
+};
+extern "C" __global__ void __launch_bounds__(256) hy_ev_stop(const hy_ev_stop_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.N) return;
+    const i64 oc = a.outcome[i];
+    if (oc >= 0 && oc < (i64)a.n_te && a.te_stop[oc] != 0) a.outcome[i] = -oc - 1;
+}
+
+// Independent semantics: the loop was ended by max_steps or by the step callback - the systems which are neither retired
+// nor done (remaining time zero) report override_oc (step_limit / cb_stop), the others keep their outcomes.
+extern "C" __global__ void __launch_bounds__(256) hy_indep_override(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.N) return;
+    if (a.retired[i] != 0) return;
+    const bool done = (a.gidx != nullptr) ? (a.gidx[i] >= a.n_grid) : (a.rem_hi[i] == 0.0 && a.rem_lo[i] == 0.0);
+    if (!done) a.outcome_w[i] = a.override_oc;
 }
 
 extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_args a)
@@ -2598,6 +2783,9 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         return;
     }
     if (a.gidx_prev != nullptr) a.gidx_prev[i] = a.gidx[i];
+    const bool indep = a.retired != nullptr;
+    // (A retired system is through its grid: it is not counted in counters[0].)
+    if (indep && hy_indep_retired(a, i)) return;
     const i64 oc = a.outcome[i];
     const double h = a.last_h[i];
     if (oc == HY_OC_ERR_NF_STATE) {
@@ -2606,6 +2794,15 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
             a.acc_n_steps[i] += a.n_steps[i];
             a.acc_min_h[i] = hy_min(a.acc_min_h[i], a.min_h[i]);
             a.acc_max_h[i] = hy_max(a.acc_max_h[i], a.max_h[i]);
+        }
+        if (indep) {
+            // (Retired as non-finite: no samples of this step, the remaining rows stay NaN, the other systems carry on.)
+            a.retired[i] = oc;
+            a.lim[i] = 0.0;
+            a.gidx[i] = a.n_grid;
+            if (a.next_tg != nullptr) a.next_tg[i] = (a.t_dir[i] != 0) ? __builtin_inf() : -__builtin_inf();
+            hy_count(a.counters + 5, true);
+            return;
         }
         hy_count(a.counters + 1, true);
         return;
@@ -2624,7 +2821,16 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         }
     }
     // Stopping terminal event: outcome -index - 1 (:1903-1908).
-    hy_count(a.counters + 2, oc > HY_OC_SUCCESS && oc < 0);
+    const bool stopped = oc > HY_OC_SUCCESS && oc < 0;
+    hy_count(a.counters + 2, stopped);
+    // (Independent semantics: the system is retired by this step. It takes the samples inside the truncated step below,
+    // like the step which ends the loop of the whole batch; then its grid index goes to the end - not through the
+    // done_lane branch, which would sample every remaining point.)
+    const bool retire = indep && stopped;
+    if (retire) {
+        a.retired[i] = oc;
+        hy_count(a.counters + 4, true);
+    }
     hy_df tcur; tcur.hi = a.thi[i]; tcur.lo = a.tlo[i];
     hy_df rem; rem.hi = a.rem_hi[i]; rem.lo = a.rem_lo[i];
     const unsigned ng = a.n_grid;
@@ -2672,6 +2878,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         }
         ++g;
     }
+    if (retire) g = ng;
     a.gidx[i] = g;
     // (The next grid time of the lane: the steps which do not reach it need not store their Taylor coefficients.)
     if (a.next_tg != nullptr) {
@@ -2682,7 +2889,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
     double lim;
     if (a.t_dir[i] != 0) { m.hi = a.mdt[i]; lim = hy_df_lt(rem, m) ? rem.hi : m.hi; }
     else { m.hi = -a.mdt[i]; lim = hy_df_lt(m, rem) ? rem.hi : m.hi; }
-    a.lim[i] = lim;
+    a.lim[i] = retire ? 0.0 : lim;
     hy_count(a.counters, g < ng);
 }
 
@@ -2719,16 +2926,13 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
 
     d.ensure_device();
     d.ensure_tc();
-    if (!d.grid_mod) {
-        d.grid_mod = std::make_unique<aux_module>(hiprtc_compile_source(make_grid_source(d.order, dim, d.high_accuracy)),
-                                                  d.device);
-    }
+    d.ensure_grid_mod();
 
     const auto out_doubles = grid.size() * dim;
     device_buffer b_grid(grid.size() * dsz, d.device), b_out(d_out != nullptr ? 0u : out_doubles * dsz, d.device);
     double *const out_ptr = d_out != nullptr ? d_out : b_out.as<double>();
     device_buffer b_rem_hi(N * dsz, d.device), b_rem_lo(N * dsz, d.device), b_mdt(N * dsz, d.device);
-    device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(4u * sizeof(unsigned), d.device),
+    device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(6u * sizeof(unsigned), d.device),
         b_gidx_prev(N * sizeof(unsigned), d.device);
     b_grid.upload(grid.data(), grid.size() * dsz, d.stream);
     std::vector<double> rhi(N), rlo(N), lim(N), mn(N, pinf), mx(N, 0.), tg(N);
@@ -2828,6 +3032,11 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         }
     } tc_reset{d.ev_all_tc};
     d.tc_stale = false;
+    // Independent semantics: see the loop of propagate_until(). A retired system keeps the samples of its last step, its
+    // remaining rows stay NaN and its grid index goes to the end (hy_grid_post).
+    auto *const retired = d.start_retirement();
+    const bool indep = retired != nullptr;
+    const impl::retirement_guard ret_guard{d.retired_ptr};
     while (n_grid > 1u) {
         // (The sweep after which max_steps ends the loop stores the coefficients of EVERY lane: the reference leaves the
         // Taylor coefficients of the last step behind, src/taylor_adaptive_batch.cpp:1546-2055.)
@@ -2868,10 +3077,24 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                            multi_step ? b_acc_ns.as<unsigned long long>() : nullptr, multi_step ? b_acc_min.as<double>() : nullptr,
                            multi_step ? b_acc_max.as<double>() : nullptr, multi_step ? b_grid_done.as<double>() : nullptr,
                            (multi_step && d.batch_semantics == 0) ? d.d_counters.as<unsigned>() : nullptr,
-                           b_gidx_prev.as<unsigned>()};
+                           b_gidx_prev.as<unsigned>(), retired, indep ? d.d_outcome.as<long long>() : nullptr, 0,
+                           (indep && !d.tes.empty()) ? d.d_cd_active.as<int>() : nullptr,
+                           (indep && !d.tes.empty()) ? d.d_cd_second.as<double>() : nullptr};
         d.grid_mod->launch("hy_grid_post", N, 256, &a, sizeof(a), d.stream);
-        unsigned cnt[4] = {0, 0, 0, 0};
-        b_cnt.download(cnt, sizeof(cnt), d.stream);
+        unsigned cnt[6] = {0, 0, 0, 0, 0, 0};
+        b_cnt.download(cnt, (indep ? 6u : 4u) * sizeof(unsigned), d.stream);
+        d.n_retired = static_cast<std::uint64_t>(cnt[4]) + cnt[5];
+        d.n_retired_nf = cnt[5];
+        // (The loop ended by the callback or by max_steps: the systems which are neither through their grid nor retired.)
+        const auto override_rest = [&](taylor_outcome oc) {
+            if (indep) {
+                auto b = a;
+                b.override_oc = static_cast<long long>(oc);
+                d.grid_mod->launch("hy_indep_override", N, 256, &b, sizeof(b), d.stream);
+            } else {
+                d.prop_res_override = oc;
+            }
+        };
         if (cnt[3] != 0u) {
             // A lane went non-finite inside a multi-step launch: back to the start of the grid, and all of it again in
             // single-step sweeps.
@@ -2907,19 +3130,21 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                                          "alteration of the time coordinate of the integrator - this is not supported");
             }
             if (!ret_cb) {
-                d.prop_res_override = taylor_outcome::cb_stop;
+                override_rest(taylor_outcome::cb_stop);
                 break;
             }
         }
-        // (cnt[2]: lanes stopped by a terminal event - they interrupt the propagation of the whole batch.)
-        if (cnt[0] == 0u || cnt[2] != 0u) {
+        // (cnt[2]: lanes stopped by a terminal event - they interrupt the propagation of the whole batch. Independent
+        // semantics: they were retired, their grid index is at the end.)
+        if (cnt[0] == 0u || (!indep && cnt[2] != 0u)) {
             break;
         }
         if (iter_counter == max_steps) {
-            d.prop_res_override = taylor_outcome::step_limit;
+            override_rest(taylor_outcome::step_limit);
             break;
         }
     }
+    d.log_sweep_loop("propagate_grid()", iter_counter);
     if (detail::log_enabled(log_level::debug)) {
         detail::log_message(
             log_level::debug,
@@ -3367,6 +3592,16 @@ std::array<double, 8> tab_core::get_event_stats() const
             static_cast<double>(d.tc_regens), static_cast<double>(d.ev_systems)};
 }
 
+std::uint64_t tab_core::get_n_retired() const
+{
+    return m_impl->n_retired;
+}
+
+bool tab_core::events_on_device() const
+{
+    return m_impl->has_events() && m_impl->all_events_native();
+}
+
 void tab_core::mark_device_modified()
 {
     m_impl->to_device();
@@ -3468,6 +3703,8 @@ void tab_core::set_device(int device)
     d.d_ed_counts = {};
     d.d_ed_flags = {};
     d.d_ed_wl = {};
+    d.d_te_stop = {};
+    d.d_retired = {};
     d.stream = nullptr;
     d.device = device;
     d.host_newer = true;

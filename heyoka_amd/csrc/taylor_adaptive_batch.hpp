@@ -122,7 +122,11 @@ public:
         //     obtained on the device-resident path: a step-limited batch reports step_limit in every lane, and a batch
         //     with a non-finite lane is rolled back and re-run through the lock-step loop;
         //   1 always the lock-step loop (one launch per iteration of the batch);
-        //   2 per-lane results of the device-resident path (every lane stops on its own), no snapshot, no host sync.
+        //   2 per-lane results of the device-resident path (every lane stops on its own), no snapshot, no host sync;
+        //   3 independent: as 2, and in the sweep loops (events, step callbacks, continuous output, propagate_grid) a system
+        //     whose step ends in a stopping terminal event or in a non-finite state is retired on its own for the rest of the
+        //     call (sticky outcome, zero-length steps), the other systems carry on; terminal events without a callback are
+        //     applied on the device.
         int batch_semantics = 0;
     };
 
@@ -264,6 +268,10 @@ public:
     // systems which reported events}. The phase times are taken only with the timing on (a synchronisation per phase).
     void set_event_timing(bool on);
     [[nodiscard]] std::array<double, 8> get_event_stats() const;
+    // config::batch_semantics == 3: systems retired by the last call which went through the sweep loop; whether every event
+    // is applied on the device (impl::ev_native, known without a device).
+    [[nodiscard]] std::uint64_t get_n_retired() const;
+    [[nodiscard]] bool events_on_device() const;
     // Event log of the recording callbacks (core_*_event::recorder, layout in event_detection.hpp): rows of
     // get_event_log_row_size() doubles, in the order in which the callbacks would have been invoked. The log persists
     // across steps and propagations, a copy of the integrator starts with an empty one. event_log_device(): the rows in
@@ -729,6 +737,14 @@ public:
     [[nodiscard]] std::vector<double> get_event_log() const
     {
         return m_core.get_event_log();
+    }
+    [[nodiscard]] std::uint64_t get_n_retired() const
+    {
+        return m_core.get_n_retired();
+    }
+    [[nodiscard]] bool events_on_device() const
+    {
+        return m_core.events_on_device();
     }
     [[nodiscard]] std::uint64_t get_event_log_size() const
     {

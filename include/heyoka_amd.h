@@ -233,7 +233,11 @@ typedef struct {
                             * default mode (products first, pairwise sum), 2 its compact mode (running sums: one FMA per term) */
     int batch_semantics;   /* propagate_for/until when a lane goes non-finite or max_steps is hit: 0 the reference's batch-wide
                             * outcomes (src/taylor_adaptive_batch.cpp:1404-1407, :1462-1467, :1516), 1 always the lock-step loop,
-                            * 2 per-lane outcomes of the device-resident path (no snapshot, fully asynchronous) */
+                            * 2 per-lane outcomes of the device-resident path (no snapshot, fully asynchronous),
+                            * 3 independent: as 2, and within one propagate_until / propagate_for / propagate_grid call a system
+                            * whose step ends in a stopping terminal event (outcome -index - 1) or in a non-finite state is retired
+                            * alone - it keeps the state, time and outcome of that step and takes zero-length steps from then on -
+                            * while every other system carries on to its final time (hy_tab_get_n_retired()) */
 } hy_tab_config;
 
 /* Constructor (taylor.hpp:905-941 -> finalise_ctor_impl(), src/taylor_adaptive_batch.cpp:78-427).
@@ -272,6 +276,12 @@ int hy_tab_with_events(hy_tab);
  * timing is on (hy_tab_set_event_timing(): one stream synchronisation per phase). */
 int hy_tab_set_event_timing(hy_tab, int on);
 int hy_tab_get_event_stats(hy_tab, double *out8);
+/* batch_semantics = 3: systems retired (stopping terminal event or non-finite state) by the last propagate_until / propagate_for /
+ * propagate_grid call which went through the sweep loop; 0 under the other semantics. */
+uint64_t hy_tab_get_n_retired(hy_tab);
+/* != 0: every event of the integrator is applied on the device (library-side counting / recording callbacks and, under
+ * batch_semantics = 3, terminal events without a callback): no records, no per-event host work. Needs no GPU. */
+int hy_tab_events_on_device(hy_tab);
 /* Ready-made callbacks which count their invocations in the uint64_t `user` points to (the terminal one continues).
  * When EVERY event of an integrator has one of them as its callback, the step applies the events on the device (counts per
  * event, cooldown and "continuing" outcome of the first terminal event of a lane: what the host loop of
