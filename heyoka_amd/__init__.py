@@ -60,6 +60,7 @@ __all__ = [
     "version",
     "native_event_counter",
     "native_event_recorder",
+    "event_action",
     "event_log",
     "callback",
 ]
@@ -879,6 +880,49 @@ class native_event_recorder(native_event_counter):
     of invocations; as a terminal callback it always continues."""
 
 
+class event_action:
+    """A terminal callback which lives in the library and is defined by assignments ``state variable <- expression``
+    instead of Python code: ``t_event(x, callback=event_action({v: -0.8 * v}))``. A dict, or a list of (variable,
+    expression) pairs, which keeps its order. The right-hand sides may read state variables, ``par[...]``, ``hy.time``
+    and numbers, and all of them read the state from before the action (``{x: v, v: x}`` swaps). The action runs where a
+    terminal callback would - the step truncated at the event, for the first terminal event of a system in a step - and
+    always continues. It is applied by a generated kernel: on the device when every event of the integrator is
+    library-side (``ta.event_stats["events_on_device"]``), at its place in the host loop otherwise, with the same bits -
+    those of ``cfunc(rhs, vars=state variables)``. Calling it, ``action(ta, d_sgn, batch_idx)``, applies it to one system
+    of an integrator it belongs to."""
+
+    def __init__(self, assignments=None, _handle=None):
+        if _handle is not None:
+            self._h = _handle
+            return
+        pairs = list(assignments.items()) if isinstance(assignments, dict) else [tuple(p) for p in (assignments or ())]
+        if any(len(p) != 2 for p in pairs):
+            raise ValueError("event_action takes a dict or a list of (state variable, expression) pairs")
+        lhs, larr = _handle_array([p[0] for p in pairs])
+        rhs, rarr = _handle_array([p[1] for p in pairs])
+        self._h = check_handle(lib.hy_event_action_new(larr, rarr, len(pairs)))
+
+    def __del__(self, _free=lib.hy_event_action_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def __copy__(self):
+        return event_action(_handle=check_handle(lib.hy_event_action_clone(self._h)))
+
+    def __deepcopy__(self, memo):
+        return self.__copy__()
+
+    def __repr__(self):
+        return take_str(lib.hy_event_action_str(self._h))
+
+    def __call__(self, ta, d_sgn, batch_idx):
+        if lib.hy_event_action_t(ta._h, int(d_sgn), int(batch_idx), self._h) == 0:
+            raise_for(lib.hy_last_error_code() or 4)
+        return True
+
+
 class _angle_reducer:
     """callback::angle_reducer (include/heyoka/callback/angle_reducer.hpp): the step callback which keeps the given state
     variables in [0, 2 pi) - ``x -= 2 pi floor(x / 2 pi)`` after every step. It lives in the library: passed as
@@ -1066,6 +1110,8 @@ class taylor_adaptive_batch:
             def make_t(ev):
                 if ev.callback is None:
                     return ctypes.cast(None, _lib.T_EVENT_CB)
+                if isinstance(ev.callback, event_action):
+                    return ctypes.cast(lib.hy_event_action_t, _lib.T_EVENT_CB)
                 if isinstance(ev.callback, native_event_recorder):
                     return ctypes.cast(lib.hy_event_recorder_t, _lib.T_EVENT_CB)
                 if isinstance(ev.callback, native_event_counter):
@@ -1088,6 +1134,8 @@ class taylor_adaptive_batch:
                 cb = make_t(ev)
                 cbs.append(cb)
                 user = ctypes.cast(ctypes.byref(ev.callback._c), ctypes.c_void_p) if isinstance(ev.callback, native_event_counter) else None
+                if isinstance(ev.callback, event_action):
+                    user = ctypes.c_void_p(ev.callback._h)
                 te_arr[k] = _lib.TEvent(ev.eq._h, cb, user, int(ev.direction), ev.cooldown)
             for k, ev in enumerate(nt_events):
                 cb = make_nt(ev)
@@ -1193,6 +1241,25 @@ class taylor_adaptive_batch:
         data, n = ctypes.c_void_p(), ctypes.c_size_t()
         raise_for(lib.hy_tab_event_log_code_object(self._h, int(which), ctypes.byref(data), ctypes.byref(n)))
         return ctypes.string_at(data.value, n.value)
+
+    @property
+    def n_event_actions(self):
+        return int(lib.hy_tab_n_event_actions(self._h))
+
+    @property
+    def event_action_kernel_ms(self):
+        """(sum of the durations of the hy_ev_action launches in ms, number of launches) taken from HIP events while the
+        event timing was on (``set_event_timing``)."""
+        ms, n = ctypes.c_double(0.0), ctypes.c_uint64(0)
+        raise_for(lib.hy_tab_event_action_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def event_action_module(self):
+        """(HIP source, gfx950 code object) of the action module (kernel hy_ev_action) of an integrator with event
+        actions."""
+        src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        raise_for(lib.hy_tab_event_action_module(self._h, ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
+        return take_str(src.value), ctypes.string_at(data.value, n.value)
 
     def reset_cooldowns(self, batch_idx=None):
         raise_for(lib.hy_tab_reset_cooldowns(self._h, -1 if batch_idx is None else int(batch_idx)))

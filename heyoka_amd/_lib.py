@@ -190,6 +190,14 @@ SIGNATURES = [
     ("hy_tab_set_event_log_states", c_int, [c_void_p, c_int]),
     ("hy_tab_get_event_log_states", c_int, [c_void_p]),
     ("hy_tab_event_log_code_object", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    ("hy_event_action_new", c_void_p, [c_void_p, c_void_p, c_size_t]),
+    ("hy_event_action_clone", c_void_p, [c_void_p]),
+    ("hy_event_action_free", None, [c_void_p]),
+    ("hy_event_action_str", c_void_p, [c_void_p]),
+    ("hy_event_action_t", c_int, [c_void_p, c_int, ctypes.c_uint32, c_void_p]),
+    ("hy_tab_event_action_module", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("hy_tab_n_event_actions", ctypes.c_uint32, [c_void_p]),
+    ("hy_tab_event_action_kernel_ms", c_int, [c_void_p, c_void_p, c_void_p]),
     ("hy_event_detection_source", c_void_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("hy_tab_set_event_timing", c_int, [c_void_p, c_int]),
     ("hy_tab_get_event_stats", c_int, [c_void_p, c_void_p]),

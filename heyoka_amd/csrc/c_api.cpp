@@ -46,6 +46,10 @@ struct hy_angle_reducer_s {
     callback::angle_reducer ar;
 };
 
+struct hy_event_action_s {
+    event_action act;
+};
+
 struct hy_cout_s {
     detail::c_out_core core;
 };
@@ -813,6 +817,14 @@ hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state
                     e.recorder = true;
                     e.native_counter = static_cast<std::uint64_t *>(user);
                 }
+                if (cb == &hy_event_action_t) {
+                    // (The integrator owns a copy of what is behind the handle; the callback itself is never invoked.)
+                    if (user == nullptr) {
+                        throw std::invalid_argument("hy_event_action_t needs a hy_event_action handle as its user pointer");
+                    }
+                    e.action = std::make_shared<const event_action>(static_cast<hy_event_action>(user)->act);
+                    e.callback = [](void *, int, std::uint32_t) { return true; };
+                }
             }
             c.t_events.push_back(std::move(e));
         }
@@ -967,6 +979,90 @@ int hy_tab_event_log_code_object(hy_tab t, int which, const char **data, size_t 
         const auto &co = t->core.event_log_code_object(which);
         *data = co.data();
         *size = co.size();
+    });
+}
+// Terminal-event actions (event_action.hpp).
+hy_event_action hy_event_action_new(const hy_expr *vars, const hy_expr *rhs, size_t n)
+{
+    try {
+        if (n == 0u) {
+            throw std::invalid_argument("Cannot construct an event action from an empty list of assignments");
+        }
+        std::vector<std::pair<expression, expression>> a;
+        for (size_t i = 0; i < n; ++i) {
+            if (!vars[i]->ex.is_variable()) {
+                throw std::invalid_argument("The left-hand side '" + vars[i]->ex.to_string()
+                                            + "' of an assignment of an event action is not a variable");
+            }
+            a.emplace_back(vars[i]->ex, rhs[i]->ex);
+        }
+        return new hy_event_action_s{event_action(std::move(a))};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+hy_event_action hy_event_action_clone(hy_event_action h)
+{
+    try {
+        return new hy_event_action_s{h->act};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+void hy_event_action_free(hy_event_action h)
+{
+    delete h;
+}
+char *hy_event_action_str(hy_event_action h)
+{
+    try {
+        return dup_str(h->act.to_string());
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+int hy_event_action_t(hy_tab t, int, uint32_t batch_idx, void *user)
+{
+    try {
+        if (user == nullptr) {
+            throw std::invalid_argument("hy_event_action_t needs a hy_event_action handle as its user pointer");
+        }
+        t->core.apply_event_action(static_cast<hy_event_action>(user)->act, batch_idx);
+        return 1;
+    } catch (...) {
+        handle_exception();
+        return 0;
+    }
+}
+int hy_tab_event_action_module(hy_tab t, char **source, const char **data, size_t *size)
+{
+    return guarded([&] {
+        const auto &src = t->core.event_action_source();
+        const auto &co = t->core.event_action_code_object();
+        if (source != nullptr) {
+            *source = dup_str(src);
+        }
+        if (data != nullptr) {
+            *data = co.data();
+        }
+        if (size != nullptr) {
+            *size = co.size();
+        }
+    });
+}
+uint32_t hy_tab_n_event_actions(hy_tab t)
+{
+    return t->core.get_n_event_actions();
+}
+int hy_tab_event_action_kernel_ms(hy_tab t, double *ms, uint64_t *launches)
+{
+    return guarded([&] {
+        const auto [m, n] = t->core.get_event_action_kernel_ms();
+        *ms = m;
+        *launches = n;
     });
 }
 char *hy_event_detection_source(uint32_t order, uint32_t n_t_events, uint32_t n_nt_events)

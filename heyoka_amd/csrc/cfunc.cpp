@@ -1,6 +1,7 @@
 // Compiled functions on the device. See cfunc.hpp.
 #include "cfunc.hpp"
 
+#include <functional>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -24,9 +25,11 @@ struct cf_kargs {
     unsigned long long n;
 };
 
-// One lane per evaluation; straight-line order-0 evaluation of the decomposition with the same node
-// emitters as the Taylor stepper (hip_emit_detail.hpp, ssa_emitter::node(i, 0)).
-std::string emit_cfunc_source(const taylor_program &p)
+} // namespace
+
+// Straight-line order-0 evaluation of the decomposition with the same node emitters as the Taylor stepper
+// (hip_emit_detail.hpp, ssa_emitter::node(i, 0)). See cfunc.hpp.
+order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input)
 {
     // NOTE: the decomposition is sorted breadth-first (all the nodes of a dependency level before the next one),
     // which is the right order for the Taylor recursions but, for a straight-line evaluation, keeps every value of
@@ -36,7 +39,7 @@ std::string emit_cfunc_source(const taylor_program &p)
     // used.
     emit_detail::ssa_emitter e(p, 0);
     for (std::uint32_t i = 0; i < p.n_eq; ++i) {
-        e.val(i, 0) = "a.in[(u64)" + std::to_string(i) + "u * N + s]";
+        e.val(i, 0) = input(i);
     }
     std::vector<char> done(p.nodes.size(), 0);
     const auto emit_from = [&](std::uint32_t root) {
@@ -68,6 +71,21 @@ std::string emit_cfunc_source(const taylor_program &p)
             emit_from(d.idx);
         }
     }
+    order0_code ret;
+    ret.body = e.os.str();
+    for (const auto &d : p.sv_defs) {
+        ret.outs.push_back(d.type == operand::kind::uvar ? e.val(d.idx, 0) : e.numpar(d));
+    }
+    return ret;
+}
+
+namespace
+{
+
+// One lane per evaluation.
+std::string emit_cfunc_source(const taylor_program &p)
+{
+    const auto code = emit_order0(p, [](std::uint32_t i) { return "a.in[(u64)" + std::to_string(i) + "u * N + s]"; });
     std::ostringstream src;
     src << emit_detail::prelude << emit_detail::rules_source(p);
     src << R"HIP(
@@ -91,11 +109,9 @@ extern "C" __global__ void __launch_bounds__(256) hy_cfunc(const hy_cf_args a)
     if (p.time_dependent) {
         src << "const double t_hi = a.tm[s];\n";
     }
-    src << e.os.str();
-    for (std::size_t o = 0; o < p.sv_defs.size(); ++o) {
-        const auto &d = p.sv_defs[o];
-        src << "a.out[(u64)" << o << "u * N + s] = "
-            << (d.type == operand::kind::uvar ? e.val(d.idx, 0) : e.numpar(d)) << ";\n";
+    src << code.body;
+    for (std::size_t o = 0; o < code.outs.size(); ++o) {
+        src << "a.out[(u64)" << o << "u * N + s] = " << code.outs[o] << ";\n";
     }
     src << "}\n";
     return src.str();

@@ -12,6 +12,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <optional>
 #include <string>
@@ -28,6 +29,16 @@ namespace heyoka_amd
 
 namespace detail
 {
+
+// The order-0 emitter of the compiled functions: the statements which evaluate the decomposition p of a vector function
+// depth-first from its outputs, and the name (or literal) of every output. input(i): the text which reads variable i.
+// The statements refer to par_<i> (parameter i) and t_hi (the time), which the caller defines. Shared with the
+// terminal-event actions (event_action.hpp), whose values are therefore those of a cfunc of the same expressions.
+struct order0_code {
+    std::string body;
+    std::vector<std::string> outs;
+};
+order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input);
 
 class cfunc_core
 {

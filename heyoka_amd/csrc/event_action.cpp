@@ -1,0 +1,154 @@
+// Terminal-event actions. See event_action.hpp.
+#include "event_action.hpp"
+
+#include <algorithm>
+#include <set>
+#include <sstream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "cfunc.hpp"
+#include "hip_emit_detail.hpp"
+
+namespace heyoka_amd
+{
+
+std::string event_action::to_string() const
+{
+    std::string ret = "event_action({";
+    for (std::size_t i = 0; i < assignments.size(); ++i) {
+        ret += (i != 0u ? ", " : "") + assignments[i].first.to_string() + ": " + assignments[i].second.to_string();
+    }
+    return ret + "})";
+}
+
+namespace detail
+{
+
+event_action_section make_event_action_section(const event_action &act, std::uint32_t te_idx,
+                                               const std::vector<expression> &state_vars, std::uint32_t n_par)
+{
+    const auto where = " (terminal event " + std::to_string(te_idx) + ")";
+    if (act.assignments.empty()) {
+        throw std::invalid_argument("Cannot construct an event action from an empty list of assignments" + where);
+    }
+    event_action_section ret;
+    ret.te_idx = te_idx;
+    std::vector<expression> rhs;
+    std::set<std::string> names;
+    for (const auto &sv : state_vars) {
+        names.insert(sv.var_name());
+    }
+    for (const auto &[lhs, ex] : act.assignments) {
+        const auto it = std::find(state_vars.begin(), state_vars.end(), lhs);
+        if (!lhs.is_variable() || it == state_vars.end()) {
+            throw std::invalid_argument("The left-hand side '" + lhs.to_string()
+                                        + "' of an assignment of an event action is not a state variable of the system" + where);
+        }
+        const auto row = static_cast<std::uint32_t>(it - state_vars.begin());
+        if (std::find(ret.rows.begin(), ret.rows.end(), row) != ret.rows.end()) {
+            throw std::invalid_argument("The state variable '" + lhs.to_string()
+                                        + "' is assigned more than once by an event action" + where);
+        }
+        for (const auto &v : get_variables(ex)) {
+            if (names.count(v) == 0u) {
+                throw std::invalid_argument("The right-hand side of the assignment to '" + lhs.to_string()
+                                            + "' in an event action uses the variable '" + v
+                                            + "', which is not a state variable of the system" + where);
+            }
+        }
+        ret.rows.push_back(row);
+        rhs.push_back(ex);
+    }
+    const auto dc = function_decompose(rhs, state_vars);
+    ret.prog = make_program(dc, static_cast<std::uint32_t>(state_vars.size()), static_cast<std::uint32_t>(rhs.size()));
+    if (ret.prog.n_par > n_par) {
+        throw std::invalid_argument("An event action uses par[" + std::to_string(ret.prog.n_par - 1u)
+                                    + "], but the system and its event equations have " + std::to_string(n_par)
+                                    + " parameter(s)" + where);
+    }
+    return ret;
+}
+
+std::string make_event_action_source(const std::vector<event_action_section> &sections)
+{
+    std::ostringstream src;
+    src << emit_detail::prelude;
+    {
+        // (The device code of the node rules of every section, once.)
+        taylor_program all;
+        for (const auto &sec : sections) {
+            all.nodes.insert(all.nodes.end(), sec.prog.nodes.begin(), sec.prog.nodes.end());
+        }
+        src << emit_detail::rules_source(all);
+    }
+    src << R"HIP(
+struct hy_eva_args {
+    const i64 *outcome;
+    double *state;
+    const double *pars;
+    const double *time_hi;
+    u64 N, first, count;
+    i64 force;
+};
+
+// One lane per system. A system whose step ended at a terminal event with an action (continuing outcome = index of the
+// event) runs the section of that event; every other system leaves after the load of its outcome. A section is
+// straight-line code: the state rows it reads, parameters and time, all the right-hand sides, then the stores - every
+// right-hand side sees the state from before the action.
+extern "C" __global__ void __launch_bounds__(256) hy_ev_action(const hy_eva_args a)
+{
+    const u64 lane = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (lane >= a.count) return;
+    const u64 s = a.first + lane;
+    if (s >= N) return;
+    const i64 oc = (a.force >= 0) ? a.force : a.outcome[s];
+    switch (oc) {
+)HIP";
+    for (const auto &sec : sections) {
+        const auto &p = sec.prog;
+        const auto code = emit_order0(p, [](std::uint32_t i) { return "x" + std::to_string(i); });
+        // State rows the section reads: the operands of its elementary functions and the outputs which are plain copies.
+        std::set<std::uint32_t> reads;
+        for (const auto &n : p.nodes) {
+            for (const auto &o : n.args) {
+                if (o.type == operand::kind::uvar && o.idx < p.n_eq) {
+                    reads.insert(o.idx);
+                }
+            }
+        }
+        for (const auto &d : p.sv_defs) {
+            if (d.type == operand::kind::uvar && d.idx < p.n_eq) {
+                reads.insert(d.idx);
+            }
+        }
+        src << "case " << sec.te_idx << ": {\n";
+        for (const auto r : reads) {
+            src << "const double x" << r << " = a.state[(u64)" << r << "u * N + s];\n";
+        }
+        for (std::uint32_t i = 0; i < p.n_par; ++i) {
+            src << "const double par_" << i << " = a.pars[(u64)" << i << "u * N + s];\n";
+        }
+        if (p.time_dependent) {
+            src << "const double t_hi = a.time_hi[s];\n";
+        }
+        src << code.body;
+        // (Named results first: an output which is a plain copy of a row, or a literal, is a value of its own before any
+        // row is written.)
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            src << "const double r" << o << " = " << code.outs[o] << ";\n";
+        }
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            src << "a.state[(u64)" << sec.rows[o] << "u * N + s] = r" << o << ";\n";
+        }
+        src << "break;\n}\n";
+    }
+    src << "default:\nbreak;\n}\n}\n";
+    return src.str();
+}
+
+} // namespace detail
+
+} // namespace heyoka_amd

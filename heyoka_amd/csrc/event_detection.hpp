@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "event_action.hpp"
 #include "expression.hpp"
 
 namespace heyoka_amd
@@ -68,6 +69,10 @@ struct core_t_event {
     // C++ interface): every invocation appends a row to the integrator's event log (see event_log_header) and lets the
     // integration continue; native_counter, if set, is incremented as by the counting callback.
     bool recorder = false;
+    // The callback is a library-side action (event_action.hpp): assignments to state variables applied by the
+    // kernel hy_ev_action, on the device when every event of the integrator is library-side, in a one-system launch at
+    // the callback's place in the host loop otherwise. It continues; `callback` is not invoked.
+    std::shared_ptr<const event_action> action;
 };
 
 // One detected event of a lane: (event index, root (time from the beginning of the step), sign of the time

@@ -495,6 +495,33 @@ void aux_module::launch(const char *name, std::uint64_t n_threads, unsigned bloc
               "hipModuleLaunchKernel(aux)");
 }
 
+double aux_module::launch_timed(const char *name, std::uint64_t n_threads, unsigned block, const void *args,
+                                std::size_t args_size, void *stream)
+{
+    hip_check(hipSetDevice(m_impl->device), "hipSetDevice");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hip_check(hipEventCreate(&e0), "hipEventCreate");
+    if (const auto rc = hipEventCreate(&e1); rc != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        hip_check(rc, "hipEventCreate");
+    }
+    float ms = 0;
+    try {
+        hip_check(hipEventRecord(e0, static_cast<hipStream_t>(stream)), "hipEventRecord");
+        launch(name, n_threads, block, args, args_size, stream);
+        hip_check(hipEventRecord(e1, static_cast<hipStream_t>(stream)), "hipEventRecord");
+        hip_check(hipEventSynchronize(e1), "hipEventSynchronize");
+        hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+    } catch (...) {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        throw;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return static_cast<double>(ms);
+}
+
 std::shared_ptr<const compiled_module> hiprtc_compile_source(const std::string &source)
 {
     emitted_module m;

@@ -76,6 +76,9 @@ public:
     // Launch kernel `name` with n_threads threads in blocks of `block`, passing the args_size bytes at args.
     void launch(const char *name, std::uint64_t n_threads, unsigned block, const void *args, std::size_t args_size,
                 void *stream);
+    // The same launch between two HIP events on the stream; waits for the kernel and returns its duration in ms.
+    double launch_timed(const char *name, std::uint64_t n_threads, unsigned block, const void *args, std::size_t args_size,
+                        void *stream);
 };
 
 // Plain source -> code object helper for the auxiliary modules (cached like hiprtc_compile()).

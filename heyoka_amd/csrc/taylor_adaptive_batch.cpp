@@ -350,7 +350,39 @@ struct tab_core::impl {
     // WITHOUT a callback (plain stops: hy_ev_stop writes the stopping outcome behind hy_ev_native, d_te_stop holds the flags).
     [[nodiscard]] bool event_is_native(const core_t_event &ev) const
     {
-        return ev.native_counter != nullptr || ev.recorder || (batch_semantics == 3 && !ev.callback);
+        return ev.native_counter != nullptr || ev.recorder || ev.action || (batch_semantics == 3 && !ev.callback);
+    }
+    // ---- terminal-event actions (core_t_event::action, event_action.hpp) ----
+    // One section of the kernel hy_ev_action per terminal event with an action; the module is compiled with the
+    // integrator and loaded at the first step which needs it.
+    std::vector<event_action_section> act_sections;
+    std::string act_source;
+    std::shared_ptr<const compiled_module> act_cmod;
+    mutable std::unique_ptr<aux_module> act_mod;
+    // Systems [first, first + count): by their outcomes (force < 0) or by the section of the terminal event `force`.
+    void launch_event_action(std::uint64_t first, std::uint64_t count, long long force) const
+    {
+        if (!act_mod) {
+            act_mod = std::make_unique<aux_module>(act_cmod, device);
+        }
+        const eva_kargs ka{d_outcome.as<long long>(), d_state.as<double>(), d_pars.as<double>(), d_thi.as<double>(), N, first, count, force};
+        if (ev_timing) {
+            // (Event timing on: the duration of the kernel from HIP events, see get_event_action_kernel_ms().)
+            act_ms += act_mod->launch_timed("hy_ev_action", count, 256, &ka, sizeof(ka), stream);
+            ++act_timed;
+        } else {
+            act_mod->launch("hy_ev_action", count, 256, &ka, sizeof(ka), stream);
+        }
+    }
+    mutable double act_ms = 0;
+    mutable std::uint64_t act_timed = 0;
+    // The host-loop path and the marker callback of the C ABI: the action of terminal event te_idx on system i alone,
+    // on the newest copy of the state; the mirrors follow as after any kernel.
+    void apply_event_action(std::uint32_t te_idx, std::uint32_t i)
+    {
+        before_kernel();
+        launch_event_action(i, 1, static_cast<long long>(te_idx));
+        after_kernel(false);
     }
     [[nodiscard]] bool all_events_native() const
     {
@@ -380,7 +412,8 @@ struct tab_core::impl {
                                     + names[batch_semantics] + "), " + std::to_string(sweeps) + " sweeps, "
                                     + std::to_string(n_retired - n_retired_nf) + " systems retired by events, "
                                     + std::to_string(n_retired_nf) + " retired as non-finite, events applied on the device: "
-                                    + ((has_events() && all_events_native()) ? "yes" : "no"));
+                                    + ((has_events() && all_events_native()) ? "yes" : "no") + " ("
+                                    + std::to_string(act_sections.size()) + " event actions)");
         }
     }
     long long *start_retirement()
@@ -947,6 +980,22 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
     for (const auto &ev : d.ntes) {
         d.ev_has_rec = d.ev_has_rec || ev.recorder;
     }
+    {
+        // Terminal-event actions: checked against the system, one section each, the kernel in a module of its own.
+        std::vector<expression> svars;
+        for (const auto &eq : sys) {
+            svars.push_back(eq.first);
+        }
+        for (std::size_t e = 0; e < d.tes.size(); ++e) {
+            if (d.tes[e].action) {
+                d.act_sections.push_back(make_event_action_section(*d.tes[e].action, static_cast<std::uint32_t>(e), svars, d.prog.n_par));
+            }
+        }
+        if (!d.act_sections.empty()) {
+            d.act_source = make_event_action_source(d.act_sections);
+            d.act_cmod = hiprtc_compile_source(d.act_source);
+        }
+    }
     if (d.ev_has_rec) {
         // Recording callbacks: the kernels of the event log, in modules of their own.
         auto eo_log = eo;
@@ -1015,6 +1064,9 @@ tab_core::tab_core(const tab_core &o) : m_impl(o.m_impl ? std::make_unique<impl>
     d.log_states = s.log_states;
     d.evr_cmod = s.evr_cmod;
     d.drow_cmod = s.drow_cmod;
+    d.act_sections = s.act_sections;
+    d.act_source = s.act_source;
+    d.act_cmod = s.act_cmod;
     d.state = s.state;
     d.pars = s.pars;
     d.time_hi = s.time_hi;
@@ -1552,7 +1604,7 @@ void tab_core::impl::ensure_event_buffers()
         for (const auto &ev : tes) {
             te_cd.push_back(ev.cooldown);
             is_rec.push_back(ev.recorder ? 1 : 0);
-            te_stop.push_back((batch_semantics == 3 && !ev.callback) ? 1 : 0);
+            te_stop.push_back((batch_semantics == 3 && !ev.callback && !ev.action) ? 1 : 0);
         }
         for (const auto &ev : ntes) {
             is_rec.push_back(ev.recorder ? 1 : 0);
@@ -1912,6 +1964,12 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
             log_fill_states(log_rows, ra.total, log_ub);
         }
     }
+    if (ev_native && cur[0] != 0u && act_cmod) {
+        // Terminal-event actions: hy_ev_native has given the first terminal event of a system its cooldown and the
+        // continuing outcome `index`; the rows of the log (a terminal row copies the state) are written. One lane per
+        // system, the systems without such an outcome leave after one load.
+        launch_event_action(0, N, -1);
+    }
     const double *rec = nullptr;
     std::size_t rec_size = 0;
     if (ev_native) {
@@ -2068,7 +2126,17 @@ void tab_core::impl::step_with_events_device(const std::vector<double> *lims)
             te_cooldowns[i][ev.idx].emplace(0., cd);
         }
         bool te_cb_ret = false;
-        if (te.callback) {
+        if (te.action) {
+            // (The same compiled section as on the device path, restricted to this system: the callbacks which run later
+            // in the step see the changed state.)
+            try {
+                apply_event_action(ev.idx, i);
+                te_cb_ret = true;
+            } catch (...) {
+                cb_eptrs.emplace_back(i, std::current_exception());
+                continue;
+            }
+        } else if (te.callback) {
             try {
                 te_cb_ret = te.callback(cb_ctx, ev.d_sgn, i);
             } catch (...) {
@@ -3580,6 +3648,49 @@ const std::vector<char> &tab_core::event_log_code_object(int which) const
     return m->code;
 }
 
+std::uint32_t tab_core::get_n_event_actions() const
+{
+    return static_cast<std::uint32_t>(m_impl->act_sections.size());
+}
+
+std::pair<double, std::uint64_t> tab_core::get_event_action_kernel_ms() const
+{
+    return {m_impl->act_ms, m_impl->act_timed};
+}
+
+const std::string &tab_core::event_action_source() const
+{
+    if (!m_impl->act_cmod) {
+        throw std::invalid_argument("This integrator has no event actions: no action kernel was compiled");
+    }
+    return m_impl->act_source;
+}
+
+const std::vector<char> &tab_core::event_action_code_object() const
+{
+    if (!m_impl->act_cmod) {
+        throw std::invalid_argument("This integrator has no event actions: no action kernel was compiled");
+    }
+    return m_impl->act_cmod->code;
+}
+
+void tab_core::apply_event_action(const event_action &act, std::uint32_t batch_idx)
+{
+    auto &d = *m_impl;
+    if (batch_idx >= d.N) {
+        throw std::invalid_argument("Invalid batch index " + std::to_string(batch_idx) + " passed to an event action: the batch size is "
+                                    + std::to_string(d.N));
+    }
+    for (std::size_t e = 0; e < d.tes.size(); ++e) {
+        if (d.tes[e].action && d.tes[e].action->assignments == act.assignments) {
+            d.apply_event_action(static_cast<std::uint32_t>(e), batch_idx);
+            stream_synchronize(d.device, d.stream);
+            return;
+        }
+    }
+    throw std::invalid_argument("The event action " + act.to_string() + " does not belong to a terminal event of this integrator");
+}
+
 void tab_core::set_event_timing(bool on)
 {
     m_impl->ev_timing = on;
@@ -3677,6 +3788,7 @@ void tab_core::set_device(int device)
     }
     d.evr_mod.reset();
     d.drow_mod.reset();
+    d.act_mod.reset();
     d.d_ev_log = {};
     d.d_evr_isrec = {};
     d.d_evr_lane = {};

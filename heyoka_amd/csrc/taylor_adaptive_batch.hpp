@@ -290,6 +290,16 @@ public:
     [[nodiscard]] bool get_event_log_states() const;
     [[nodiscard]] bool has_event_recorders() const;
     [[nodiscard]] const std::vector<char> &event_log_code_object(int which) const;
+    // Terminal-event actions (event_action.hpp): their number, the HIP source and the gfx950 code object of
+    // the action module (kernel hy_ev_action; std::invalid_argument without actions), and what the marker callback of
+    // the C ABI does when it is called directly - the action (one of this integrator's) applied to one system.
+    [[nodiscard]] std::uint32_t get_n_event_actions() const;
+    // With set_event_timing(true): the launches of hy_ev_action run between two HIP events - (sum of the kernel durations
+    // in ms, number of timed launches) since the construction.
+    [[nodiscard]] std::pair<double, std::uint64_t> get_event_action_kernel_ms() const;
+    [[nodiscard]] const std::string &event_action_source() const;
+    [[nodiscard]] const std::vector<char> &event_action_code_object() const;
+    void apply_event_action(const event_action &act, std::uint32_t batch_idx);
     // Mark the device copies as modified by the caller (e.g. initial conditions written by a kernel).
     void mark_device_modified();
     void set_stream(void *hip_stream);
@@ -340,6 +350,7 @@ std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool high_a
 // it lets the integration continue.
 struct event_recorder {
 };
+// (The other tag accepted as the callback of a terminal event: event_action, event_action.hpp.)
 
 template <typename T>
 class nt_event_batch
@@ -412,6 +423,7 @@ private:
     event_direction m_dir = event_direction::any;
     T m_cooldown = -1;
     bool m_recorder = false;
+    std::shared_ptr<const event_action> m_action;
 
 public:
     // Default construction: the event equation 0, no callback, any direction, automatic cooldown
@@ -428,6 +440,10 @@ public:
             if constexpr (std::is_same_v<std::decay_t<decltype(kw::get(kw::callback, 0, kw_args...))>, event_recorder>) {
                 m_cb = [](taylor_adaptive_batch<T> &, int, std::uint32_t) { return true; };
                 m_recorder = true;
+            } else if constexpr (std::is_same_v<std::decay_t<decltype(kw::get(kw::callback, 0, kw_args...))>, event_action>) {
+                // (The assignments are checked against the system by the constructor of the integrator.)
+                m_cb = [](taylor_adaptive_batch<T> &, int, std::uint32_t) { return true; };
+                m_action = std::make_shared<const event_action>(kw::get(kw::callback, 0, kw_args...));
             } else {
                 m_cb = kw::get(kw::callback, 0, kw_args...);
             }
@@ -458,6 +474,11 @@ public:
     [[nodiscard]] bool is_recorder() const
     {
         return m_recorder;
+    }
+    // The action given as kw::callback (null otherwise).
+    [[nodiscard]] const std::shared_ptr<const event_action> &get_action() const
+    {
+        return m_action;
     }
 };
 
@@ -554,6 +575,7 @@ class taylor_adaptive_batch<double>
                 ce.dir = ev.get_direction();
                 ce.cooldown = ev.get_cooldown();
                 ce.recorder = ev.is_recorder();
+                ce.action = ev.get_action();
                 if (const auto &cb = ev.get_callback()) {
                     ce.callback = [cb](void *ctx, int d_sgn, std::uint32_t idx) {
                         return cb(*static_cast<self_t *>(ctx), d_sgn, idx);

@@ -2,6 +2,7 @@
 // heyoka_amd/csrc/ and exposes it as namespace heyoka, so that sources written against the reference's headers
 // compile unchanged with -I <repo>/include -lheyoka_amd.
 #pragma once
+#include "../../heyoka_amd/csrc/event_action.hpp"
 #include "../../heyoka_amd/csrc/event_detection.hpp"
 #include "../../heyoka_amd/csrc/taylor_adaptive_batch.hpp"
 

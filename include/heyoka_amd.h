@@ -325,6 +325,37 @@ int hy_tab_get_event_log_states(hy_tab);
  * Code objects (gfx950) of the event-log kernels of an integrator with recording callbacks: which = 0 row headers
  * (hy_evr_count / hy_evr_scan / hy_evr_write), 1 dense output over the rows (hy_dout_rows). Owned by the integrator. */
 int hy_tab_event_log_code_object(hy_tab, int which, const char **data, size_t *size);
+/* Terminal-event ACTIONS: a library-side terminal callback defined by n assignments vars[k] <- rhs[k] (in this order)
+ * instead of code of the caller's - a bounce v <- -c v, an impulse v <- v + dv, a wrap of a coordinate. The left-hand
+ * sides are distinct state variables of the system; the right-hand sides may read state variables, parameters, the time
+ * and numbers, and all of them read the state from BEFORE the action ({x <- v, v <- x} swaps). hy_event_action_new()
+ * fails (NULL, hy_last_error()) on an empty list or a left-hand side which is not a variable; the checks against a
+ * system (left-hand side not a state variable or repeated, right-hand side using a variable which is not a state variable
+ * or a parameter the system does not have) are made by hy_tab_create_with_events().
+ * Use: hy_t_event{eq, hy_event_action_t, handle, ...}. The integrator takes a copy of the handle's contents (the handle
+ * may be freed right after the construction) and hy_tab_copy() carries it along. The action runs where the reference
+ * invokes the terminal callback - the step has been truncated at the event, state and time are those of the trigger
+ * time, the cooldown is set -, for the first terminal event of a system in a step only, and the integration continues
+ * (outcome = index of the event). It is applied by a generated kernel (hy_ev_action, one lane per system): behind the
+ * device-side event handling when every event of the integrator is library-side (counters, recorders, actions; plain
+ * stops under batch_semantics 3), at its place in the host loop, one system at a time, otherwise - the same compiled
+ * code, the same bits: those of a hy_cfunc of the right-hand sides over the state variables. Results are not checked for
+ * finiteness (the next step reports err_nf_state); Taylor coefficients, last_h, the event log and the cooldowns are left
+ * alone. Calling hy_event_action_t directly applies the action (which must be one of the integrator's) to the system
+ * batch_idx; it returns 1, or 0 on error (hy_last_error()). */
+typedef struct hy_event_action_s *hy_event_action;
+hy_event_action hy_event_action_new(const hy_expr *vars, const hy_expr *rhs, size_t n);
+hy_event_action hy_event_action_clone(hy_event_action);
+void hy_event_action_free(hy_event_action);
+char *hy_event_action_str(hy_event_action); /* hy_free_str() */
+int hy_event_action_t(hy_tab, int d_sgn, uint32_t batch_idx, void *user);
+/* Introspection hook (test suite): HIP source (hy_free_str()) and gfx950 code object (owned by the integrator) of the
+ * action module of an integrator with actions; error without one. Either output may be NULL. */
+int hy_tab_event_action_module(hy_tab, char **source, const char **data, size_t *size);
+uint32_t hy_tab_n_event_actions(hy_tab);
+/* While hy_tab_set_event_timing() is on, every launch of hy_ev_action runs between two HIP events: the sum of the kernel
+ * durations (ms) and the number of timed launches since the construction. */
+int hy_tab_event_action_kernel_ms(hy_tab, double *ms, uint64_t *launches);
 /* HIP source of the event-detection module for (order, number of terminal / non-terminal events); hy_free_str(). */
 char *hy_event_detection_source(uint32_t order, uint32_t n_t_events, uint32_t n_nt_events);
 /* reset_cooldowns(): batch_idx < 0 -> all the lanes. */
