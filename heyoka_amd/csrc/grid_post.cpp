@@ -1,0 +1,319 @@
+// Post-step kernels of the device-driven sweep loops of propagate_until() and propagate_grid() (tab_propagate.cpp).
+#include "tab_impl.hpp"
+
+namespace heyoka_amd::detail
+{
+
+// Post-step kernel of the device-resident propagate_grid() loop: the per-lane body of the reference's loop
+// (src/taylor_adaptive_batch.cpp:1760-2040) - step counters, remaining time, dense output at every grid
+// point inside the step just taken (h' = t_grid - (t_now - last_h) in double-length arithmetic, Horner or
+// compensated summation as in taylor_add_d_out_function()), limit of the next step.
+std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool ha)
+{
+    std::ostringstream src;
+    src << emit_detail::prelude;
+    src << "#define HY_ORDER " << order << "u\n#define HY_DIM " << dim << "u\n#define HY_HA " << (ha ? 1 : 0) << "\n";
+    src << R"HIP(
+struct hy_grid_args {
+    const double *grid;
+    double *out;
+    const double *tc;
+    const double *thi;
+    const double *tlo;
+    const double *last_h;
+    const i64 *outcome;
+    double *rem_hi;
+    double *rem_lo;
+    const double *mdt;
+    const int *t_dir;
+    double *lim;
+    unsigned *gidx;
+    double *min_h;
+    double *max_h;
+    u64 *n_steps;
+    unsigned *counters;
+    u64 N;
+    unsigned n_grid;
+    double *next_tg;
+    u64 *acc_n_steps;
+    double *acc_min_h;
+    double *acc_max_h;
+    const double *grid_done;
+    const unsigned *launch_nf;
+    unsigned *gidx_prev;
+    i64 *retired;
+    i64 *outcome_w;
+    i64 override_oc;
+    int *cd_active;
+    const double *cd_second;
+};
+
+// Post-step kernel of the device-driven propagate_until() lock-step loop (callbacks / continuous output): the
+// per-lane bookkeeping of src/taylor_adaptive_batch.cpp:1395-1440 (step counters, min/max |h|, remaining time, limit of
+// the next step). counters[0] = lanes done in this sweep, counters[1] = lanes with a non-finite state. The final
+// times are in the (double-length) grid row 0: grid[i] = hi, out[i] = lo.
+// One atomic per wavefront instead of one per lane: the lanes which reach a call site with pred set elect the lowest of
+// them, which adds their number. (hy_grid_post counts the lanes which are NOT through their grid - every lane of every
+// sweep: 262 144 atomics on one address were 6 ms of a 6.5-ms sweep, profiles/r05_grid_sweeps.log.)
+__device__ __forceinline__ void hy_count(unsigned *p, bool pred)
+{
+    const u64 m = __builtin_amdgcn_ballot_w64(pred);
+    if (pred && (unsigned)__builtin_ctzll(m) == (threadIdx.x & 63u)) atomicAdd(p, (unsigned)__builtin_popcountll(m));
+}
+
+// Independent semantics (hy_grid_args::retired != nullptr; the branches below do not run otherwise). A system is retired by
+// the step which ends in a stopping terminal event (outcome -index - 1) or in a non-finite state: the outcome becomes sticky
+// in retired[i] (0: not retired) and the limit of its next steps is zero, so that it takes zero-length steps like a system
+// which has reached its final time - state, time, cooldowns, step count and min / max |h| stay those of that step. The
+// zero-length steps report time_limit: the sticky outcome is put back after each of them. counters[4] / [5]: systems
+// retired by events / as non-finite so far.
+// Returns true for a system retired in an EARLIER sweep: nothing else is to be done for it.
+__device__ __forceinline__ bool hy_indep_retired(const hy_grid_args &a, u64 i)
+{
+    const i64 so = a.retired[i];
+    if (so == 0) return false;
+    a.outcome_w[i] = so;
+    a.lim[i] = 0.0;
+    // (Frozen cooldowns: a zero-length step ages a cooldown by nothing, but it ends one of duration zero - the one the
+    // retiring event may have set.)
+    if (so != HY_OC_ERR_NF_STATE && a.cd_active != nullptr) {
+        const u64 p = (u64)(-so - 1) * a.N + i;
+        if (a.cd_second[p] == 0.0) a.cd_active[p] = 1;
+    }
+    hy_count(a.counters + 4, so != HY_OC_ERR_NF_STATE);
+    hy_count(a.counters + 5, so == HY_OC_ERR_NF_STATE);
+    return true;
+}
+
+extern "C" __global__ void __launch_bounds__(256) hy_until_post(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (i >= N) return;
+    const bool indep = a.retired != nullptr;
+    if (indep && hy_indep_retired(a, i)) {
+        hy_count(a.counters, true);
+        return;
+    }
+    const i64 oc = a.outcome[i];
+    const double h = a.last_h[i];
+    if (oc == HY_OC_ERR_NF_STATE) {
+        if (indep) {
+            // (Retired as non-finite: done as far as the loop is concerned, the other systems carry on.)
+            a.retired[i] = oc;
+            a.lim[i] = 0.0;
+            hy_count(a.counters, true);
+            hy_count(a.counters + 5, true);
+            return;
+        }
+        hy_count(a.counters + 1, true);
+        return;
+    }
+    a.n_steps[i] += (h != 0.0) ? 1u : 0u;
+    if (oc == HY_OC_SUCCESS) {
+        const double ah = fabs(h);
+        a.min_h[i] = hy_min(a.min_h[i], ah);
+        a.max_h[i] = hy_max(a.max_h[i], ah);
+    }
+    // Stopping terminal event: outcome -index - 1 (src/taylor_adaptive_batch.cpp:1411).
+    const bool stopped = oc > HY_OC_SUCCESS && oc < 0;
+    hy_count(a.counters + 2, stopped);
+    hy_df rem; rem.hi = a.rem_hi[i]; rem.lo = a.rem_lo[i];
+    // (Independent semantics: the system retired by this step counts as done; the bookkeeping of the step is the one above
+    // and below - what the same step leaves behind when it ends the loop of the whole batch.)
+    const bool retire = indep && stopped;
+    if (retire) {
+        a.retired[i] = oc;
+        hy_count(a.counters + 4, true);
+    }
+    hy_count(a.counters, h == rem.hi || retire);
+    if (h == rem.hi) {
+        rem.hi = 0.0; rem.lo = 0.0;
+    } else {
+        hy_df tcur; tcur.hi = a.thi[i]; tcur.lo = a.tlo[i];
+        hy_df tf; tf.hi = a.grid[i]; tf.lo = a.out[i];
+        rem = hy_df_sub(tf, tcur);
+    }
+    a.rem_hi[i] = rem.hi; a.rem_lo[i] = rem.lo;
+    hy_df m; m.lo = 0.0;
+    double lim;
+    if (a.t_dir[i] != 0) { m.hi = a.mdt[i]; lim = hy_df_lt(rem, m) ? rem.hi : m.hi; }
+    else { m.hi = -a.mdt[i]; lim = hy_df_lt(m, rem) ? rem.hi : m.hi; }
+    a.lim[i] = retire ? 0.0 : lim;
+}
+
+// Independent semantics, events applied on the device: behind hy_ev_native, which has given the first terminal event of a
+// system its cooldown and the continuing outcome `index` - a terminal event WITHOUT a callback stops (te_stop[index] != 0:
+// the flag is data), outcome -index - 1.
+struct hy_ev_stop_args {
+    i64 *outcome;
+    const int *te_stop;
+    u64 N;
+    unsigned n_te, pad;
+};
+extern "C" __global__ void __launch_bounds__(256) hy_ev_stop(const hy_ev_stop_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.N) return;
+    const i64 oc = a.outcome[i];
+    if (oc >= 0 && oc < (i64)a.n_te && a.te_stop[oc] != 0) a.outcome[i] = -oc - 1;
+}
+
+// Independent semantics: the loop was ended by max_steps or by the step callback - the systems which are neither retired
+// nor done (remaining time zero) report override_oc (step_limit / cb_stop), the others keep their outcomes.
+extern "C" __global__ void __launch_bounds__(256) hy_indep_override(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.N) return;
+    if (a.retired[i] != 0) return;
+    const bool done = (a.gidx != nullptr) ? (a.gidx[i] >= a.n_grid) : (a.rem_hi[i] == 0.0 && a.rem_lo[i] == 0.0);
+    if (!done) a.outcome_w[i] = a.override_oc;
+}
+
+extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (i >= N) return;
+    if (a.launch_nf != nullptr && *a.launch_nf != 0u) {
+        if (i == 0u) a.counters[3] = 1u;
+        return;
+    }
+    if (a.gidx_prev != nullptr) a.gidx_prev[i] = a.gidx[i];
+    const bool indep = a.retired != nullptr;
+    // (A retired system is through its grid: it is not counted in counters[0].)
+    if (indep && hy_indep_retired(a, i)) return;
+    const i64 oc = a.outcome[i];
+    const double h = a.last_h[i];
+    if (oc == HY_OC_ERR_NF_STATE) {
+        // (A launch of several steps per lane - per-lane semantics: the steps before the non-finite one count.)
+        if (a.acc_n_steps != nullptr) {
+            a.acc_n_steps[i] += a.n_steps[i];
+            a.acc_min_h[i] = hy_min(a.acc_min_h[i], a.min_h[i]);
+            a.acc_max_h[i] = hy_max(a.acc_max_h[i], a.max_h[i]);
+        }
+        if (indep) {
+            // (Retired as non-finite: no samples of this step, the remaining rows stay NaN, the other systems carry on.)
+            a.retired[i] = oc;
+            a.lim[i] = 0.0;
+            a.gidx[i] = a.n_grid;
+            if (a.next_tg != nullptr) a.next_tg[i] = (a.t_dir[i] != 0) ? __builtin_inf() : -__builtin_inf();
+            hy_count(a.counters + 5, true);
+            return;
+        }
+        hy_count(a.counters + 1, true);
+        return;
+    }
+    if (a.acc_n_steps != nullptr) {
+        // (A launch of several steps per lane: its own counters and extrema.)
+        a.acc_n_steps[i] += a.n_steps[i];
+        a.acc_min_h[i] = hy_min(a.acc_min_h[i], a.min_h[i]);
+        a.acc_max_h[i] = hy_max(a.acc_max_h[i], a.max_h[i]);
+    } else {
+        a.n_steps[i] += (h != 0.0) ? 1u : 0u;
+        if (oc == HY_OC_SUCCESS) {
+            const double ah = fabs(h);
+            a.min_h[i] = hy_min(a.min_h[i], ah);
+            a.max_h[i] = hy_max(a.max_h[i], ah);
+        }
+    }
+    // Stopping terminal event: outcome -index - 1 (:1903-1908).
+    const bool stopped = oc > HY_OC_SUCCESS && oc < 0;
+    hy_count(a.counters + 2, stopped);
+    // (Independent semantics: the system is retired by this step. It takes the samples inside the truncated step below,
+    // like the step which ends the loop of the whole batch; then its grid index goes to the end - not through the
+    // done_lane branch, which would sample every remaining point.)
+    const bool retire = indep && stopped;
+    if (retire) {
+        a.retired[i] = oc;
+        hy_count(a.counters + 4, true);
+    }
+    hy_df tcur; tcur.hi = a.thi[i]; tcur.lo = a.tlo[i];
+    hy_df rem; rem.hi = a.rem_hi[i]; rem.lo = a.rem_lo[i];
+    const unsigned ng = a.n_grid;
+    // (A launch of several steps per lane: the stored remaining time is the one before its FIRST step - the stepper says
+    // whether its last step was the one clamped to the remaining time.)
+    const bool clamped_to_rem = (a.grid_done != nullptr) ? (a.grid_done[i] != 0.0) : (h == rem.hi);
+    if (clamped_to_rem) {
+        rem.hi = 0.0; rem.lo = 0.0;
+    } else {
+        hy_df tl; tl.hi = a.grid[(u64)(ng - 1u) * N + i]; tl.lo = 0.0;
+        rem = hy_df_sub(tl, tcur);
+    }
+    a.rem_hi[i] = rem.hi; a.rem_lo[i] = rem.lo;
+    // Time interval covered by the step, and the start of the step for the dense output.
+    hy_df hh; hh.hi = h; hh.lo = 0.0;
+    const hy_df tstart = hy_df_sub(tcur, hh);
+    const bool fwd = !hy_df_lt(tcur, tstart);
+    const hy_df t0 = fwd ? tstart : tcur, t1 = fwd ? tcur : tstart;
+    const bool done_lane = (rem.hi == 0.0 && rem.lo == 0.0);
+    unsigned g = a.gidx[i];
+    while (g < ng) {
+        hy_df tg; tg.hi = a.grid[(u64)g * N + i]; tg.lo = 0.0;
+        const bool avail = (!hy_df_lt(tg, t0) && !hy_df_lt(t1, tg)) || done_lane;
+        if (!avail) break;
+        const double hd = hy_df_sub(tg, tstart).hi;
+        for (unsigned v = 0; v < HY_DIM; ++v) {
+            const double *c = a.tc + (u64)v * (HY_ORDER + 1u) * N + i;
+#if HY_HA
+            double res = c[0], comp = 0.0, cur_h = hd;
+            for (unsigned k = 1; k <= HY_ORDER; ++k) {
+                const double tmp = c[(u64)k * N] * cur_h;
+                const double y = tmp - comp;
+                const double t = res + y;
+                comp = (t - res) - y;
+                res = t;
+                cur_h = cur_h * hd;
+            }
+#else
+            double res = c[(u64)HY_ORDER * N];
+            for (unsigned k = 1; k <= HY_ORDER; ++k) {
+                res = c[(u64)(HY_ORDER - k) * N] + res * hd;
+            }
+#endif
+            a.out[((u64)g * HY_DIM + v) * N + i] = res;
+        }
+        ++g;
+    }
+    if (retire) g = ng;
+    a.gidx[i] = g;
+    // (The next grid time of the lane: the steps which do not reach it need not store their Taylor coefficients.)
+    if (a.next_tg != nullptr) {
+        a.next_tg[i] = (g < ng) ? a.grid[(u64)g * N + i] : ((a.t_dir[i] != 0) ? __builtin_inf() : -__builtin_inf());
+    }
+    // Limit of the next step.
+    hy_df m; m.lo = 0.0;
+    double lim;
+    if (a.t_dir[i] != 0) { m.hi = a.mdt[i]; lim = hy_df_lt(rem, m) ? rem.hi : m.hi; }
+    else { m.hi = -a.mdt[i]; lim = hy_df_lt(m, rem) ? rem.hi : m.hi; }
+    a.lim[i] = retire ? 0.0 : lim;
+    hy_count(a.counters, g < ng);
+}
+
+// A sweep in which a lane went non-finite: the reference leaves its loop right after that step, before the dense output of
+// the step (src/taylor_adaptive_batch.cpp:1962-1968; the samples of a step are taken at the top of the NEXT iteration,
+// :1800-1871) - the samples hy_grid_post has just taken in the other lanes are NaN again.
+extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (i >= N) return;
+    const unsigned g1 = a.gidx[i];
+    for (unsigned g = a.gidx_prev[i]; g < g1; ++g) {
+        for (unsigned v = 0; v < HY_DIM; ++v) {
+            a.out[((u64)g * HY_DIM + v) * N + i] = __builtin_nan("");
+        }
+    }
+}
+)HIP";
+    return src.str();
+}
+
+void tab_core::impl::ensure_grid_mod() const
+{
+    if (!grid_mod) {
+        grid_mod = std::make_unique<aux_module>(hiprtc_compile_source(make_grid_source(order, dim, high_accuracy)), device);
+    }
+}
+
+} // namespace heyoka_amd::detail

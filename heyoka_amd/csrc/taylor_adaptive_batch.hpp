@@ -229,7 +229,7 @@ public:
     // and the seconds its last compilation took (0: never compiled / cached).
     [[nodiscard]] std::string get_angle_reduce_variant_source(const std::vector<std::uint32_t> &idx, std::string &why_not) const;
     [[nodiscard]] double get_angle_reduce_compile_seconds() const;
-    // Device-resident loop of propagate_grid(): see taylor_adaptive_batch.cpp.
+    // Device-resident loop of propagate_grid(): see tab_propagate.cpp.
     void propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                     const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
                                     const std::vector<double> &max_delta_ts, std::size_t max_steps,
