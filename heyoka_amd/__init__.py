@@ -63,6 +63,11 @@ __all__ = [
     "event_action",
     "event_log",
     "callback",
+    "diff",
+    "eval",
+    "var_args",
+    "var_ode_sys",
+    "taylor_map_source",
 ]
 
 _builtin_sum = sum
@@ -518,6 +523,14 @@ class _Sys:
         raise_for(lib.hy_sys_get_vars(self._h, arr))
         return [expression(_handle=check_handle(arr[i])) for i in range(n)]
 
+    @property
+    def rhs(self):
+        """The right-hand sides, in the same order."""
+        n = len(self)
+        arr = (ctypes.c_void_p * n)()
+        raise_for(lib.hy_sys_get_rhs(self._h, arr))
+        return [expression(_handle=check_handle(arr[i])) for i in range(n)]
+
 
 def _to_sys(sys):
     return sys if isinstance(sys, _Sys) else _Sys(sys)
@@ -663,6 +676,142 @@ class model:
     @staticmethod
     def mascon_potential(Gconst=1.0, masses=(), positions=(), omega=()):
         return model._fc_call(lib.hy_model_mascon_potential, Gconst, masses, positions, omega, with_omega=True)
+
+
+def diff(e, x):
+    """diff(e, x): the derivative of an expression with respect to a variable or a ``par[i]`` (one rule per built-in
+    function, shared nodes differentiated once, zeros and ones folded). A function defined through a node rule (kepF, kepDE,
+    custom_func) raises NotImplementedError naming it."""
+    e, x = _as_ex(e), _as_ex(x)
+    return expression._wrap(lib.hy_expr_diff(e._h, x._h))
+
+
+def eval(e, vars=None, pars=(), time=0.0):  # noqa: A001, A002 - mirrors heyoka::eval
+    """Value of an expression on the HOST: ``vars`` maps variable names (or variable expressions) to numbers, ``pars[i]`` is
+    the value of ``par[i]``. Plain libm, Newton iteration for kepE; node-rule functions raise NotImplementedError."""
+    e = _as_ex(e)
+    items = [((k if isinstance(k, str) else repr(k)).encode(), float(v)) for k, v in (vars or {}).items()]
+    n = len(items)
+    names = (ctypes.c_char_p * max(n, 1))(*[k for k, _ in items])
+    vals = (ctypes.c_double * max(n, 1))(*[v for _, v in items])
+    p = _f64(pars).reshape(-1)
+    out = ctypes.c_double(0.0)
+    raise_for(lib.hy_expr_eval(e._h, names, vals, n, p.ctypes.data if p.size else None, p.size, float(time),
+                               ctypes.byref(out)))
+    return float(out.value)
+
+
+def _node_count(exs):
+    """Number of distinct function nodes below the expressions (shared nodes once)."""
+    exs, arr = _handle_array(exs)
+    return int(lib.hy_expr_node_count(arr, len(exs)))
+
+
+class var_args(enum.IntFlag):
+    """var_args (include/heyoka/var_ode_sys.hpp:29): what the variational equations are formulated with respect to."""
+
+    vars = 1
+    params = 2
+    time = 4
+    all = 7
+
+
+class var_ode_sys:
+    """var_ode_sys (include/heyoka/var_ode_sys.hpp:34-77): ``sys`` augmented with the equations of the derivatives of the
+    state with respect to ``args`` - a ``var_args`` value or a list of state variables (their initial conditions) and
+    ``par[i]`` - up to ``order``. Time as an argument raises NotImplementedError."""
+
+    def __init__(self, sys, args, order=1):
+        s = _to_sys(sys)
+        if isinstance(args, (var_args, int)) and not isinstance(args, bool):
+            if int(args) == 0:
+                # (The mask 0 selects the explicit list in the C ABI: give the reference's message for the bad enumerator.)
+                raise ValueError("Invalid var_args enumerator detected: the value of the enumerator must be in the [1, 7] "
+                                 "range, but a value of 0 was detected instead")
+            h = lib.hy_var_sys_new(s._h, int(args), None, 0, int(order))
+        else:
+            exs, arr = _handle_array(list(args))
+            h = lib.hy_var_sys_new(s._h, 0, arr, len(exs), int(order))
+        self._h = check_handle(h)
+
+    def __del__(self, _free=lib.hy_var_sys_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def _full_sys(self):
+        return _Sys(_handle=check_handle(lib.hy_var_sys_get_sys(self._h)))
+
+    @property
+    def sys(self):
+        """get_sys(): the list of (variable, right-hand side) pairs."""
+        s = self._full_sys()
+        return list(zip(s.vars, s.rhs))
+
+    @property
+    def vargs(self):
+        n = int(lib.hy_var_sys_get_n_vargs(self._h))
+        arr = (ctypes.c_void_p * max(n, 1))()
+        raise_for(lib.hy_var_sys_get_vargs(self._h, arr))
+        return [expression(_handle=check_handle(arr[i])) for i in range(n)]
+
+    @property
+    def n_orig_sv(self):
+        return int(lib.hy_var_sys_get_n_orig_sv(self._h))
+
+    @property
+    def order(self):
+        return int(lib.hy_var_sys_get_order(self._h))
+
+    @property
+    def didx(self):
+        """One (component, dense multi-index tuple) per equation, in equation order."""
+        n_eq, na = len(self._full_sys()), int(lib.hy_var_sys_get_n_vargs(self._h))
+        comp = np.zeros(max(n_eq, 1), dtype=np.uint32)
+        mi = np.zeros(max(n_eq * na, 1), dtype=np.uint32)
+        raise_for(lib.hy_var_sys_get_didx(self._h, comp.ctypes.data, mi.ctypes.data))
+        return [(int(comp[e]), tuple(int(v) for v in mi[e * na:(e + 1) * na])) for e in range(n_eq)]
+
+
+def taylor_map_source(n_orig_sv, n_args, order, lds_bytes=0):
+    """(HIP source of the Taylor-map module for (n_orig_sv, n_args, order), the stage logger's line about the LDS decision).
+    ``lds_bytes``: LDS the cloud kernel may use per workgroup for coefficients (0: the default)."""
+    note = ctypes.c_void_p()
+    src = take_str(check_handle(lib.hy_taylor_map_source(int(n_orig_sv), int(n_args), int(order), int(lds_bytes),
+                                                         ctypes.byref(note))))
+    return src, take_str(note.value)
+
+
+def _dev_ptr(x, numel=None, what="buffer", device=None):
+    """Device address of a torch tensor / an object with __cuda_array_interface__ / a plain integer. With ``numel`` the
+    kernels are about to read or write that many doubles: a tensor or array which is not float64, not contiguous, not on the
+    (integrator's) device or shorter than that is refused here rather than becoming an out-of-bounds device access. A plain
+    address cannot be checked: it is the caller's word."""
+    if hasattr(x, "data_ptr"):
+        if numel is not None:
+            if str(x.dtype) != "torch.float64":
+                raise TypeError("%s: expected a float64 tensor, got %s" % (what, x.dtype))
+            if not x.is_contiguous():
+                raise ValueError("%s: the tensor must be contiguous" % what)
+            if not x.is_cuda or (device is not None and x.device.index not in (None, int(device))):
+                raise ValueError("%s: the tensor must live on %s, it is on %s"
+                                 % (what, "a HIP device" if device is None else "HIP device %d" % int(device), x.device))
+            if x.numel() < numel:
+                raise ValueError("%s: %d elements are needed, the tensor has %d" % (what, numel, x.numel()))
+        return int(x.data_ptr())
+    if hasattr(x, "__cuda_array_interface__"):
+        cai = x.__cuda_array_interface__
+        if numel is not None:
+            if cai["typestr"] != "<f8":
+                raise TypeError("%s: expected float64 ('<f8'), got %s" % (what, cai["typestr"]))
+            if cai.get("strides") is not None:
+                raise ValueError("%s: the array must be contiguous" % what)
+            have = int(np.prod(cai["shape"], dtype=np.int64))
+            if have < numel:
+                raise ValueError("%s: %d elements are needed, the array has %d" % (what, numel, have))
+        return int(cai["data"][0])
+    return int(x)
 
 
 def hiprtc_compile(source):
@@ -1050,7 +1199,10 @@ class taylor_adaptive_batch:
             self._events = _events
             _TAB_REGISTRY[int(self._h)] = self
             return
-        self._sys = _to_sys(sys)
+        # A variational integrator: the integrator over vsys.sys which remembers vsys (the handle of the full system is kept
+        # for the copies; the var_ode_sys object itself may go away).
+        self._vsys = sys if isinstance(sys, var_ode_sys) else None
+        self._sys = sys._full_sys() if self._vsys is not None else _to_sys(sys)
         if state is None:
             st = np.zeros(0)
         else:
@@ -1143,10 +1295,14 @@ class taylor_adaptive_batch:
                 user = ctypes.cast(ctypes.byref(ev.callback._c), ctypes.c_void_p) if isinstance(ev.callback, native_event_counter) else None
                 nte_arr[k] = _lib.NtEvent(ev.eq._h, cb, user, int(ev.direction))
             self._events = (t_events, nt_events, cbs)
+            create = lib.hy_tab_create_var if self._vsys is not None else lib.hy_tab_create_with_events
             self._h = check_handle(
-                lib.hy_tab_create_with_events(self._sys._h, st.ctypes.data if st.size else None, st.size,
-                                              int(batch_size), ctypes.byref(cfg), te_arr, len(t_events), nte_arr,
-                                              len(nt_events)))
+                create(self._vsys._h if self._vsys is not None else self._sys._h, st.ctypes.data if st.size else None, st.size,
+                       int(batch_size), ctypes.byref(cfg), te_arr, len(t_events), nte_arr, len(nt_events)))
+        elif self._vsys is not None:
+            self._h = check_handle(
+                lib.hy_tab_create_var(self._vsys._h, st.ctypes.data if st.size else None, st.size, int(batch_size),
+                                      ctypes.byref(cfg), None, 0, None, 0))
         else:
             self._h = check_handle(
                 lib.hy_tab_create(self._sys._h, st.ctypes.data if st.size else None, st.size, int(batch_size),
@@ -1263,6 +1419,70 @@ class taylor_adaptive_batch:
 
     def reset_cooldowns(self, batch_idx=None):
         raise_for(lib.hy_tab_reset_cooldowns(self._h, -1 if batch_idx is None else int(batch_idx)))
+
+    # ---- variational integrators ----
+    @property
+    def is_variational(self):
+        return bool(lib.hy_tab_is_variational(self._h))
+
+    @property
+    def n_orig_sv(self):
+        return int(lib.hy_tab_get_n_orig_sv(self._h))
+
+    @property
+    def vorder(self):
+        o = ctypes.c_uint32(0)
+        raise_for(lib.hy_tab_get_vorder(self._h, ctypes.byref(o)))
+        return int(o.value)
+
+    @property
+    def vargs(self):
+        n = ctypes.c_size_t(0)
+        raise_for(lib.hy_tab_get_n_vargs(self._h, ctypes.byref(n)))
+        arr = (ctypes.c_void_p * max(n.value, 1))()
+        raise_for(lib.hy_tab_get_vargs(self._h, arr))
+        return [expression(_handle=check_handle(arr[i])) for i in range(n.value)]
+
+    @property
+    def tstate(self):
+        """get_tstate(): the result of the last eval_taylor_map(), shape (n_orig_sv, batch_size)."""
+        out = np.zeros((self.n_orig_sv, self.batch_size))
+        raise_for(lib.hy_tab_get_tstate(self._h, out.ctypes.data))
+        return out
+
+    def eval_taylor_map(self, inputs):
+        """eval_taylor_map(): the Taylor map at the displacements inputs[a, sys] (n_vargs * batch_size values), one launch of
+        the kernel hy_tmap over the device-resident state; returns (and leaves in ``tstate``) an (n_orig_sv, batch_size)
+        array."""
+        a = _f64(inputs).reshape(-1)
+        out = np.zeros((self.n_orig_sv, self.batch_size))
+        raise_for(lib.hy_tab_eval_taylor_map(self._h, a.ctypes.data if a.size else None, a.size, out.ctypes.data))
+        return out
+
+    def eval_taylor_map_device(self, d_in, d_out):
+        """The same on device buffers (torch tensors, __cuda_array_interface__ objects or addresses): d_in[a * batch_size +
+        sys] -> d_out[i * batch_size + sys], asynchronous on the integrator's stream."""
+        n, dev = self.batch_size, None  # (the ordinal is not known here: ensemble copies move between devices)
+        p_in = _dev_ptr(d_in, len(self.vargs) * n, "eval_taylor_map_device(): d_in", dev)
+        p_out = _dev_ptr(d_out, self.n_orig_sv * n, "eval_taylor_map_device(): d_out", dev)
+        raise_for(lib.hy_tab_eval_taylor_map_device(self._h, p_in, p_out))
+
+    def eval_taylor_map_cloud(self, d_delta, d_out, n_samples, shared=False):
+        """n_samples displacement vectors per system (kernel hy_tmap_cloud), sample-fastest device buffers:
+        d_delta[(sys * n_vargs + a) * n_samples + m] - or one cloud for every system, d_delta[a * n_samples + m], with
+        ``shared`` - and d_out[(sys * n_orig_sv + i) * n_samples + m]. Asynchronous on the integrator's stream."""
+        n, ns, dev = self.batch_size, int(n_samples), None
+        if ns < 0:
+            raise ValueError("eval_taylor_map_cloud(): the number of samples cannot be negative")
+        p_delta = _dev_ptr(d_delta, (1 if shared else n) * len(self.vargs) * ns, "eval_taylor_map_cloud(): d_delta", dev)
+        p_out = _dev_ptr(d_out, n * self.n_orig_sv * ns, "eval_taylor_map_cloud(): d_out", dev)
+        raise_for(lib.hy_tab_eval_taylor_map_cloud(self._h, p_delta, p_out, ns, int(bool(shared))))
+
+    def taylor_map_module(self):
+        """(HIP source, gfx950 code object) of the Taylor-map module (kernels hy_tmap, hy_tmap_cloud)."""
+        src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        raise_for(lib.hy_tab_taylor_map_module(self._h, ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
+        return take_str(src.value), ctypes.string_at(data.value, n.value)
 
     @property
     def te_cooldowns(self):

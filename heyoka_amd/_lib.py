@@ -290,6 +290,31 @@ SIGNATURES = [
     ("hy_model_mascon_energy", c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     ("hy_model_mascon_potential", c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]),
     ("hy_sys_get_vars", c_int, [c_void_p, c_void_p]),
+    ("hy_sys_get_rhs", c_int, [c_void_p, c_void_p]),
+    ("hy_expr_diff", c_void_p, [c_void_p, c_void_p]),
+    ("hy_expr_eval", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_double, c_void_p]),
+    ("hy_expr_node_count", c_size_t, [c_void_p, c_size_t]),
+    ("hy_var_sys_new", c_void_p, [c_void_p, c_int, c_void_p, c_size_t, c_uint32]),
+    ("hy_var_sys_free", None, [c_void_p]),
+    ("hy_var_sys_get_sys", c_void_p, [c_void_p]),
+    ("hy_var_sys_get_n_orig_sv", c_uint32, [c_void_p]),
+    ("hy_var_sys_get_order", c_uint32, [c_void_p]),
+    ("hy_var_sys_get_n_vargs", c_size_t, [c_void_p]),
+    ("hy_var_sys_get_vargs", c_int, [c_void_p, c_void_p]),
+    ("hy_var_sys_get_didx", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("hy_tab_create_var", c_void_p,
+     [c_void_p, c_void_p, c_size_t, c_uint32, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("hy_tab_is_variational", c_int, [c_void_p]),
+    ("hy_tab_get_n_orig_sv", c_uint32, [c_void_p]),
+    ("hy_tab_get_vorder", c_int, [c_void_p, c_void_p]),
+    ("hy_tab_get_n_vargs", c_int, [c_void_p, c_void_p]),
+    ("hy_tab_get_vargs", c_int, [c_void_p, c_void_p]),
+    ("hy_tab_eval_taylor_map", c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("hy_tab_get_tstate", c_int, [c_void_p, c_void_p]),
+    ("hy_tab_eval_taylor_map_device", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("hy_tab_eval_taylor_map_cloud", c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int]),
+    ("hy_tab_taylor_map_module", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("hy_taylor_map_source", c_void_p, [c_uint32, c_uint32, c_uint32, c_size_t, c_void_p]),
     ("hy_compile_aux_kernels", c_int, [c_uint32, c_uint32, c_int]),
     ("hy_cfunc_new", c_void_p, [c_void_p, c_size_t, c_void_p, c_size_t, c_int]),
     ("hy_cfunc_free", None, [c_void_p]),

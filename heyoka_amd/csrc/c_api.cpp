@@ -22,11 +22,14 @@
 #include "decompose.hpp"
 #include "ensemble.hpp"
 #include "expression.hpp"
+#include "expression_diff.hpp"
 #include "hip_backend.hpp"
 #include "hip_emit.hpp"
 #include "model.hpp"
 #include "node_rule.hpp"
 #include "taylor_adaptive_batch.hpp"
+#include "taylor_map.hpp"
+#include "var_ode_sys.hpp"
 
 using namespace heyoka_amd;
 
@@ -40,6 +43,10 @@ struct hy_sys_s {
 
 struct hy_tab_s {
     detail::tab_core core;
+};
+
+struct hy_var_sys_s {
+    var_ode_sys vsys;
 };
 
 struct hy_angle_reducer_s {
@@ -768,6 +775,14 @@ int hy_sys_get_vars(hy_sys s, hy_expr *out)
         }
     });
 }
+int hy_sys_get_rhs(hy_sys s, hy_expr *out)
+{
+    return guarded([&] {
+        for (std::size_t i = 0; i < s->sys.size(); ++i) {
+            out[i] = new hy_expr_s{s->sys[i].second};
+        }
+    });
+}
 hy_sys hy_model_pendulum(double gconst, double length)
 {
     try {
@@ -793,9 +808,14 @@ hy_tab hy_tab_create(hy_sys sys, const double *state, size_t n_state, uint32_t b
 {
     return hy_tab_create_with_events(sys, state, n_state, batch_size, cfg, nullptr, 0, nullptr, 0);
 }
-hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state, uint32_t batch_size,
-                                 const hy_tab_config *cfg, const hy_t_event *tes, size_t n_tes, const hy_nt_event *ntes,
-                                 size_t n_ntes)
+extern "C++" {
+namespace
+{
+
+// The constructors: over a system, or over a variational system (vsys != nullptr).
+hy_tab create_tab(const std::vector<std::pair<expression, expression>> *sys, const var_ode_sys *vsys, const double *state,
+                  size_t n_state, uint32_t batch_size, const hy_tab_config *cfg, const hy_t_event *tes, size_t n_tes,
+                  const hy_nt_event *ntes, size_t n_ntes)
 {
     try {
         detail::tab_core::config c;
@@ -866,10 +886,185 @@ hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state
             c.events_on_cluster = cfg->events_on_cluster;
             c.batch_semantics = cfg->batch_semantics;
         }
-        auto *ret = new hy_tab_s{detail::tab_core(sys->sys, vec_from(state, n_state), batch_size, std::move(c))};
+        auto *ret = vsys != nullptr
+                        ? new hy_tab_s{detail::tab_core(*vsys, vec_from(state, n_state), batch_size, std::move(c))}
+                        : new hy_tab_s{detail::tab_core(*sys, vec_from(state, n_state), batch_size, std::move(c))};
         // The event callbacks receive the handle itself.
         ret->core.set_callback_context(ret);
         return ret;
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+
+} // namespace
+} // extern "C++"
+
+hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state, uint32_t batch_size,
+                                 const hy_tab_config *cfg, const hy_t_event *tes, size_t n_tes, const hy_nt_event *ntes,
+                                 size_t n_ntes)
+{
+    return create_tab(&sys->sys, nullptr, state, n_state, batch_size, cfg, tes, n_tes, ntes, n_ntes);
+}
+hy_tab hy_tab_create_var(hy_var_sys vsys, const double *state, size_t n_state, uint32_t batch_size, const hy_tab_config *cfg,
+                         const hy_t_event *tes, size_t n_tes, const hy_nt_event *ntes, size_t n_ntes)
+{
+    return create_tab(nullptr, &vsys->vsys, state, n_state, batch_size, cfg, tes, n_tes, ntes, n_ntes);
+}
+
+// ---- differentiation, host evaluation, variational systems ----
+hy_expr hy_expr_diff(hy_expr e, hy_expr x)
+{
+    return make_expr([&] { return diff(e->ex, x->ex); });
+}
+int hy_expr_eval(hy_expr e, const char *const *names, const double *values, size_t n_vars, const double *pars, size_t n_pars,
+                 double time, double *out)
+{
+    return guarded([&] {
+        std::unordered_map<std::string, double> vars;
+        for (size_t i = 0; i < n_vars; ++i) {
+            vars[names[i]] = values[i];
+        }
+        *out = eval(e->ex, vars, vec_from(pars, n_pars), time);
+    });
+}
+size_t hy_expr_node_count(const hy_expr *v, size_t n)
+{
+    try {
+        return count_function_nodes(expr_vector(v, n));
+    } catch (...) {
+        handle_exception();
+        return 0;
+    }
+}
+hy_var_sys hy_var_sys_new(hy_sys sys, int var_args_mask, const hy_expr *args, size_t n_args, uint32_t order)
+{
+    try {
+        if (var_args_mask != 0) {
+            return new hy_var_sys_s{var_ode_sys(sys->sys, static_cast<var_args>(static_cast<unsigned>(var_args_mask)), order)};
+        }
+        return new hy_var_sys_s{var_ode_sys(sys->sys, expr_vector(args, n_args), order)};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+void hy_var_sys_free(hy_var_sys v)
+{
+    delete v;
+}
+hy_sys hy_var_sys_get_sys(hy_var_sys v)
+{
+    return make_sys([&] { return v->vsys.get_sys(); });
+}
+uint32_t hy_var_sys_get_n_orig_sv(hy_var_sys v)
+{
+    return v->vsys.get_n_orig_sv();
+}
+uint32_t hy_var_sys_get_order(hy_var_sys v)
+{
+    return v->vsys.get_order();
+}
+size_t hy_var_sys_get_n_vargs(hy_var_sys v)
+{
+    return v->vsys.get_vargs().size();
+}
+int hy_var_sys_get_vargs(hy_var_sys v, hy_expr *out)
+{
+    return guarded([&] {
+        const auto &va = v->vsys.get_vargs();
+        for (std::size_t i = 0; i < va.size(); ++i) {
+            out[i] = new hy_expr_s{va[i]};
+        }
+    });
+}
+int hy_var_sys_get_didx(hy_var_sys v, uint32_t *components, uint32_t *multi_indices)
+{
+    return guarded([&] {
+        const auto &dx = v->vsys.get_didx();
+        const auto na = v->vsys.get_vargs().size();
+        for (std::size_t e = 0; e < dx.size(); ++e) {
+            components[e] = dx[e].first;
+            std::copy(dx[e].second.begin(), dx[e].second.end(), multi_indices + e * na);
+        }
+    });
+}
+int hy_tab_is_variational(hy_tab t)
+{
+    return t->core.is_variational() ? 1 : 0;
+}
+uint32_t hy_tab_get_n_orig_sv(hy_tab t)
+{
+    return t->core.get_n_orig_sv();
+}
+int hy_tab_get_vorder(hy_tab t, uint32_t *order)
+{
+    return guarded([&] { *order = t->core.get_vsys("get_vorder").get_order(); });
+}
+int hy_tab_get_n_vargs(hy_tab t, size_t *n)
+{
+    return guarded([&] { *n = t->core.get_vsys("get_vargs").get_vargs().size(); });
+}
+int hy_tab_get_vargs(hy_tab t, hy_expr *out)
+{
+    return guarded([&] {
+        const auto &va = t->core.get_vsys("get_vargs").get_vargs();
+        for (std::size_t i = 0; i < va.size(); ++i) {
+            out[i] = new hy_expr_s{va[i]};
+        }
+    });
+}
+int hy_tab_eval_taylor_map(hy_tab t, const double *in, size_t n, double *out)
+{
+    return guarded([&] {
+        const auto &r = t->core.eval_taylor_map(in, n);
+        if (out != nullptr) {
+            std::copy(r.begin(), r.end(), out);
+        }
+    });
+}
+int hy_tab_get_tstate(hy_tab t, double *out)
+{
+    return guarded([&] {
+        const auto &r = t->core.get_tstate();
+        std::copy(r.begin(), r.end(), out);
+    });
+}
+int hy_tab_eval_taylor_map_device(hy_tab t, const double *d_in, double *d_out)
+{
+    return guarded([&] { t->core.eval_taylor_map_device(d_in, d_out); });
+}
+int hy_tab_eval_taylor_map_cloud(hy_tab t, const double *d_delta, double *d_out, uint64_t n_samples, int shared_cloud)
+{
+    return guarded([&] { t->core.eval_taylor_map_cloud(d_delta, d_out, n_samples, shared_cloud != 0); });
+}
+int hy_tab_taylor_map_module(hy_tab t, char **source, const char **data, size_t *size)
+{
+    return guarded([&] {
+        const auto &src = t->core.taylor_map_source();
+        const auto &co = t->core.taylor_map_code_object();
+        if (source != nullptr) {
+            *source = dup_str(src);
+        }
+        if (data != nullptr) {
+            *data = co.data();
+        }
+        if (size != nullptr) {
+            *size = co.size();
+        }
+    });
+}
+char *hy_taylor_map_source(uint32_t n_orig_sv, uint32_t n_args, uint32_t order, size_t lds_bytes, char **note)
+{
+    try {
+        std::string nt;
+        auto src = detail::make_taylor_map_source(n_orig_sv, n_args, order,
+                                                  lds_bytes == 0u ? detail::taylor_map_default_lds_bytes : lds_bytes, &nt);
+        if (note != nullptr) {
+            *note = dup_str(nt);
+        }
+        return dup_str(src);
     } catch (...) {
         handle_exception();
         return nullptr;

@@ -334,6 +334,21 @@ struct tab_core::impl {
         // rolled-back propagation, which would overwrite the restored snapshot in the re-run. Bring them back as well.
         refresh_held_mirrors();
     }
+    // ---- variational integrators (var_ode_sys.hpp, taylor_map.hpp) ----
+    // What a variational integrator knows beyond its (larger) system: immutable, shared by the copies. The module of the
+    // Taylor map is compiled with the integrator and loaded at the first evaluation; tstate is the result of the last
+    // eval_taylor_map().
+    struct var_data {
+        var_ode_sys vsys;
+        std::string tmap_source;
+        std::shared_ptr<const compiled_module> tmap_cmod;
+        // Why there is no module (no arguments, or a map beyond what the kernels hold): the message of the evaluations.
+        std::string tmap_why;
+    };
+    std::shared_ptr<const var_data> var;
+    mutable std::unique_ptr<aux_module> tmap_mod;
+    device_buffer d_tmap_in, d_tmap_out;
+    std::vector<double> tstate;
     // Continuous output produced by the last propagate_for/until() with c_output = true.
     std::optional<c_out_core> last_c_out;
     // Post-step kernel of the device-resident propagate_grid() loop (created on first use).

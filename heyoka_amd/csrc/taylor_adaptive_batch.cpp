@@ -369,6 +369,8 @@ tab_core::tab_core(const tab_core &o) : m_impl(o.m_impl ? std::make_unique<impl>
     d.act_sections = s.act_sections;
     d.act_source = s.act_source;
     d.act_cmod = s.act_cmod;
+    d.var = s.var;
+    d.tstate = s.tstate;
     d.state = s.state;
     d.pars = s.pars;
     d.time_hi = s.time_hi;
@@ -880,6 +882,9 @@ void tab_core::set_device(int device)
     d.grid_mod.reset();
     d.evj_mod.reset();
     d.ar_mod.reset();
+    d.tmap_mod.reset();
+    d.d_tmap_in = {};
+    d.d_tmap_out = {};
     d.d_ar_idx = {};
     d.ar_idx_dev.clear();
     for (auto &[k, v] : d.ar_variants) {

@@ -32,6 +32,7 @@
 #include "expression.hpp"
 #include "kw.hpp"
 #include "step_callback.hpp"
+#include "var_ode_sys.hpp"
 
 namespace heyoka_amd
 {
@@ -134,6 +135,10 @@ public:
     // default constructor leaves the integrator in an invalid state, src/taylor_adaptive_batch.cpp:430).
     tab_core() noexcept;
     tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_size, config cfg);
+    // A variational integrator: an integrator over vsys.get_sys() which remembers vsys. state: the full state, or the
+    // n_orig_sv * batch_size values of the original state variables (or nothing) - the initial conditions of the variational
+    // variables are then set up as in the reference (src/detail/setup_variational_ics.cpp:49-121). Defined in taylor_map.cpp.
+    tab_core(const var_ode_sys &vsys, std::vector<double> state, std::uint32_t batch_size, config cfg);
     tab_core(const tab_core &);
     tab_core(tab_core &&) noexcept;
     tab_core &operator=(const tab_core &);
@@ -300,6 +305,23 @@ public:
     [[nodiscard]] const std::string &event_action_source() const;
     [[nodiscard]] const std::vector<char> &event_action_code_object() const;
     void apply_event_action(const event_action &act, std::uint32_t batch_idx);
+    // ---- variational integrators (reference: taylor.hpp is_variational() ... eval_taylor_map(); taylor_map.hpp) ----
+    [[nodiscard]] bool is_variational() const noexcept;
+    // Number of original state variables (get_dim() for a non-variational integrator).
+    [[nodiscard]] std::uint32_t get_n_orig_sv() const noexcept;
+    // The variational system; fname: the caller's name for the reference's message on non-variational integrators.
+    [[nodiscard]] const var_ode_sys &get_vsys(const char *fname) const;
+    [[nodiscard]] const std::vector<double> &get_tstate() const;
+    // The Taylor map at the n = n_args * batch_size displacements in[a * batch_size + sys] (kernel hy_tmap on the device-
+    // resident state); the result, out[i * batch_size + sys], is also what get_tstate() returns afterwards.
+    const std::vector<double> &eval_taylor_map(const double *in, std::size_t n);
+    // The same on device buffers, asynchronous on the integrator's stream; get_tstate() is left alone.
+    void eval_taylor_map_device(const double *d_in, double *d_out);
+    // n_samples displacements per system (kernel hy_tmap_cloud): d_delta[(sys * n_args + a) * n_samples + m], or one cloud
+    // for all the systems, d_delta[a * n_samples + m]; d_out[(sys * n_orig_sv + i) * n_samples + m]. Asynchronous.
+    void eval_taylor_map_cloud(const double *d_delta, double *d_out, std::uint64_t n_samples, bool shared);
+    [[nodiscard]] const std::string &taylor_map_source() const;
+    [[nodiscard]] const std::vector<char> &taylor_map_code_object() const;
     // Mark the device copies as modified by the caller (e.g. initial conditions written by a kernel).
     void mark_device_modified();
     void set_stream(void *hip_stream);
@@ -683,6 +705,33 @@ public:
         : taylor_adaptive_batch(std::move(sys), std::vector<double>(state), batch_size, std::forward<KwArgs>(kw_args)...)
     {
     }
+    // Variational integrators (reference: the var_ode_sys overloads of the constructor, taylor.hpp:905-941).
+    template <typename... KwArgs>
+    taylor_adaptive_batch(const var_ode_sys &vsys, std::vector<double> state, std::uint32_t batch_size, KwArgs &&...kw_args)
+        : m_core(vsys, std::move(state), batch_size, make_config(std::forward<KwArgs>(kw_args)...))
+    {
+        if constexpr (kw::has_v<kw::t_events_tag, KwArgs...>) {
+            for (const auto &ev : kw::get(kw::t_events, 0, kw_args...)) {
+                m_t_events.push_back(ev);
+            }
+        }
+        if constexpr (kw::has_v<kw::nt_events_tag, KwArgs...>) {
+            for (const auto &ev : kw::get(kw::nt_events, 0, kw_args...)) {
+                m_nt_events.push_back(ev);
+            }
+        }
+    }
+    template <typename... KwArgs>
+    taylor_adaptive_batch(const var_ode_sys &vsys, std::initializer_list<double> state, std::uint32_t batch_size,
+                          KwArgs &&...kw_args)
+        : taylor_adaptive_batch(vsys, std::vector<double>(state), batch_size, std::forward<KwArgs>(kw_args)...)
+    {
+    }
+    template <typename... KwArgs>
+    taylor_adaptive_batch(const var_ode_sys &vsys, std::uint32_t batch_size, KwArgs &&...kw_args)
+        : taylor_adaptive_batch(vsys, std::vector<double>{}, batch_size, std::forward<KwArgs>(kw_args)...)
+    {
+    }
     // Construction without an initial state (zero-initialised, reference: taylor.hpp:917-929).
     template <typename... KwArgs>
     taylor_adaptive_batch(sys_t sys, std::uint32_t batch_size, KwArgs &&...kw_args)
@@ -736,7 +785,7 @@ public:
     }
     [[nodiscard]] std::uint32_t get_n_orig_sv() const noexcept
     {
-        return m_core.get_dim();
+        return m_core.get_n_orig_sv();
     }
     [[nodiscard]] const sys_t &get_sys() const noexcept
     {
@@ -784,9 +833,48 @@ public:
     {
         return m_core.get_te_cooldowns();
     }
+    // Variational integrators (include/heyoka/taylor.hpp, src/taylor_adaptive_batch.cpp:2360-2470).
     [[nodiscard]] bool is_variational() const noexcept
     {
-        return false;
+        return m_core.is_variational();
+    }
+    [[nodiscard]] const std::vector<expression> &get_vargs() const
+    {
+        return m_core.get_vsys("get_vargs").get_vargs();
+    }
+    [[nodiscard]] std::uint32_t get_vorder() const
+    {
+        return m_core.get_vsys("get_vorder").get_order();
+    }
+    [[nodiscard]] const std::vector<double> &get_tstate() const
+    {
+        return m_core.get_tstate();
+    }
+    [[nodiscard]] const double *get_tstate_data() const
+    {
+        return m_core.get_tstate().data();
+    }
+    // eval_taylor_map(range of n_args * batch_size values) - vectors, arrays, initializer lists.
+    const std::vector<double> &eval_taylor_map(const std::vector<double> &in)
+    {
+        return m_core.eval_taylor_map(in.data(), in.size());
+    }
+    const std::vector<double> &eval_taylor_map(std::span<const double> in)
+    {
+        return m_core.eval_taylor_map(in.data(), in.size());
+    }
+    const std::vector<double> &eval_taylor_map(std::initializer_list<double> in)
+    {
+        return m_core.eval_taylor_map(in.begin(), in.size());
+    }
+    // MI355X extensions: the map on device buffers (taylor_map.hpp), asynchronous on the integrator's stream.
+    void eval_taylor_map_device(const double *d_in, double *d_out)
+    {
+        m_core.eval_taylor_map_device(d_in, d_out);
+    }
+    void eval_taylor_map_cloud(const double *d_delta, double *d_out, std::uint64_t n_samples, bool shared = false)
+    {
+        m_core.eval_taylor_map_cloud(d_delta, d_out, n_samples, shared);
     }
 
     // NOTE: the getters of state and times return references to host mirrors which stay valid AND current across steps,
@@ -986,6 +1074,11 @@ taylor_adaptive_batch(std::vector<std::pair<expression, expression>>, std::vecto
 template <typename... KwArgs>
 taylor_adaptive_batch(std::vector<std::pair<expression, expression>>, std::initializer_list<double>, std::uint32_t,
                       KwArgs &&...) -> taylor_adaptive_batch<double>;
+template <typename... KwArgs>
+taylor_adaptive_batch(var_ode_sys, std::vector<double>, std::uint32_t, KwArgs &&...) -> taylor_adaptive_batch<double>;
+template <typename... KwArgs>
+taylor_adaptive_batch(var_ode_sys, std::initializer_list<double>, std::uint32_t, KwArgs &&...)
+    -> taylor_adaptive_batch<double>;
 
 // Human-readable summary (reference: taylor_adaptive_batch_stream_impl(), src/taylor_stream_ops.cpp:110-170): the same
 // fields and labels, plus the code generator that produced the device kernels.
@@ -1009,6 +1102,11 @@ inline std::ostream &operator<<(std::ostream &os, const taylor_adaptive_batch<T>
     oss << "Compact mode            : " << ta.get_compact_mode() << '\n';
     oss << "Taylor order            : " << ta.get_order() << '\n';
     oss << "Dimension               : " << ta.get_dim() << '\n';
+    if (ta.is_variational()) {
+        // (src/taylor_stream_ops.cpp: the two extra lines of a variational integrator.)
+        oss << "Variational order       : " << ta.get_vorder() << '\n';
+        oss << "N of original variables : " << ta.get_n_orig_sv() << '\n';
+    }
     oss << "Batch size              : " << ta.get_batch_size() << '\n';
     list("Time                    : ", ta.get_time());
     list("State                   : ", ta.get_state());

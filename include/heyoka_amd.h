@@ -148,6 +148,16 @@ hy_expr hy_expr_sum(const hy_expr *, size_t n);  /* sum(vector)           src/ma
 hy_expr hy_expr_prod(const hy_expr *, size_t n); /* prod(vector)          src/math/prod.cpp:913 */
 void hy_expr_free(hy_expr);
 char *hy_expr_str(hy_expr); /* caller frees with hy_free_str() */
+/* diff(e, x) (include/heyoka/expression.hpp, diff(const expression &, const expression &)): x a variable or par[i]. One rule
+ * per built-in function, memoised on shared nodes, zeros and ones folded by the operators; a function defined through a
+ * node rule (kepF, kepDE, hy_expr_custom) has no gradient: NULL + HY_ERR_NOT_IMPLEMENTED naming it. */
+hy_expr hy_expr_diff(hy_expr e, hy_expr x);
+/* Value of e on the HOST (libm; Newton iteration for kepE): variables names[i] = values[i], par[i] = pars[i], heyoka::time =
+ * time. HY_ERR_INVALID_ARGUMENT for a variable or parameter without a value, HY_ERR_NOT_IMPLEMENTED for a node-rule function. */
+int hy_expr_eval(hy_expr e, const char *const *names, const double *values, size_t n_vars, const double *pars, size_t n_pars,
+                 double time, double *out);
+/* Number of distinct function nodes (shared nodes counted once) below the n expressions: the size of their DAG. */
+size_t hy_expr_node_count(const hy_expr *, size_t n);
 
 /* ------------------------------------------------------------------------------------------------
  * ODE systems: std::vector<std::pair<expression, expression>> (prime(x) = rhs).
@@ -204,9 +214,30 @@ hy_expr hy_model_mascon_potential(hy_expr Gconst, const hy_expr *masses, size_t 
 /* The state variables of a system, in order (the lhs of each equation); out[hy_sys_size()] receives new
  * handles owned by the caller. */
 int hy_sys_get_vars(hy_sys, hy_expr *out);
+/* The right-hand sides, in the same order and under the same ownership rule. */
+int hy_sys_get_rhs(hy_sys, hy_expr *out);
 /* taylor_decompose_sys() (src/taylor_01.cpp:848-1008): one line per entry of the decomposition,
  * "u_i = ..." textual form with hidden dependencies. Caller frees with hy_free_str(). */
 char *hy_sys_decomposition_str(hy_sys);
+
+/* ------------------------------------------------------------------------------------------------
+ * var_ode_sys (include/heyoka/var_ode_sys.hpp:29-75, src/var_ode_sys.cpp:215-407): the system augmented with the
+ * equations of the derivatives of the state with respect to initial conditions and parameters, up to `order` >= 1.
+ * var_args_mask != 0: the var_args enumerator (1 vars, 2 params, 1|2 both); 0: the explicit list args[0..n_args) of state
+ * variables and par[i]. Time as an argument (mask bit 4, hy_expr_time()) is not implemented: HY_ERR_NOT_IMPLEMENTED.
+ * Equations: the original ones first, then one variable per (component, multi-index), sorted by total order, component,
+ * reverse-lexicographic multi-index, named "\xe2\x88\x82" + sparse index list + name as in the reference.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct hy_var_sys_s *hy_var_sys;
+hy_var_sys hy_var_sys_new(hy_sys sys, int var_args_mask, const hy_expr *args, size_t n_args, uint32_t order);
+void hy_var_sys_free(hy_var_sys);
+hy_sys hy_var_sys_get_sys(hy_var_sys);           /* get_sys(): a new handle, hy_sys_free() */
+uint32_t hy_var_sys_get_n_orig_sv(hy_var_sys);   /* get_n_orig_sv() */
+uint32_t hy_var_sys_get_order(hy_var_sys);       /* get_order() */
+size_t hy_var_sys_get_n_vargs(hy_var_sys);
+int hy_var_sys_get_vargs(hy_var_sys, hy_expr *out); /* get_vargs(): new handles */
+/* get_didx_range() in dense form: components[e] and multi_indices[e * n_vargs + a] for every equation e of get_sys(). */
+int hy_var_sys_get_didx(hy_var_sys, uint32_t *components, uint32_t *multi_indices);
 
 /* ------------------------------------------------------------------------------------------------
  * taylor_adaptive_batch<double> (include/heyoka/taylor.hpp:781-1121).
@@ -270,6 +301,43 @@ hy_tab hy_tab_create_with_events(hy_sys sys, const double *state, size_t n_state
                                  const hy_tab_config *cfg, const hy_t_event *t_events, size_t n_t_events,
                                  const hy_nt_event *nt_events, size_t n_nt_events);
 int hy_tab_with_events(hy_tab);
+/* The constructor over a variational system. n_state = (number of equations) * batch_size, or n_orig_sv * batch_size (or 0):
+ * the variational variables then start from 1 where a first-order derivative is taken with respect to its own state variable
+ * and from 0 elsewhere (src/detail/setup_variational_ics.cpp:49-121). Everything else - events, callbacks, grids, batch
+ * semantics - sees a system of hy_tab_get_dim() equations. The module of the Taylor map is compiled here as well. */
+hy_tab hy_tab_create_var(hy_var_sys vsys, const double *state, size_t n_state, uint32_t batch_size, const hy_tab_config *cfg,
+                         const hy_t_event *t_events, size_t n_t_events, const hy_nt_event *nt_events, size_t n_nt_events);
+int hy_tab_is_variational(hy_tab);          /* is_variational() */
+uint32_t hy_tab_get_n_orig_sv(hy_tab);      /* get_n_orig_sv(): the dimension for a non-variational integrator */
+/* get_vorder() / get_vargs(): HY_ERR_INVALID_ARGUMENT with the reference's message on a non-variational integrator. */
+int hy_tab_get_vorder(hy_tab, uint32_t *order);
+int hy_tab_get_n_vargs(hy_tab, size_t *n);
+int hy_tab_get_vargs(hy_tab, hy_expr *out);
+/* eval_taylor_map(in) (src/taylor_adaptive_batch.cpp:2415-2470): in[a * batch_size + sys], n = n_vargs * batch_size values
+ * (the reference's messages for other sizes); out (may be NULL) and hy_tab_get_tstate() receive out[i * batch_size + sys],
+ * i < n_orig_sv. One launch of the kernel hy_tmap over the device-resident state:
+ *     out_i = sum_alpha state_(i,alpha) * RN(1 / alpha!) * in^alpha,
+ * terms in equation order from the order-0 term, accumulated with fma, monomials by the graded schedule
+ * in^alpha = in^(alpha - e_j) * in_j with j the highest non-zero index of alpha. */
+int hy_tab_eval_taylor_map(hy_tab, const double *in, size_t n, double *out);
+int hy_tab_get_tstate(hy_tab, double *out);  /* get_tstate(): n_orig_sv * batch_size */
+/* MI355X extensions. The same evaluation on device buffers, asynchronous on the integrator's stream (get_tstate() is not
+ * touched); and the cloud form, kernel hy_tmap_cloud: n_samples displacement vectors per system in sample-fastest layouts,
+ * d_delta[(sys * n_vargs + a) * n_samples + m] - or ONE cloud for all systems, d_delta[a * n_samples + m], when shared_cloud
+ * != 0 - and d_out[(sys * n_orig_sv + i) * n_samples + m]. Every sample gets the bits hy_tab_eval_taylor_map() gives for
+ * the same displacement. The buffers are the caller's: d_in n_vargs * batch_size doubles, d_out n_orig_sv * batch_size; for
+ * the cloud d_delta (shared_cloud ? 1 : batch_size) * n_vargs * n_samples and d_out batch_size * n_orig_sv * n_samples.
+ * HY_ERR_NOT_IMPLEMENTED (every evaluation of the map and hy_tab_taylor_map_module()) when the integrator has no map: no
+ * variational arguments, or the coefficients of ONE output beyond the 64 KiB of LDS a workgroup can declare. */
+int hy_tab_eval_taylor_map_device(hy_tab, const double *d_in, double *d_out);
+int hy_tab_eval_taylor_map_cloud(hy_tab, const double *d_delta, double *d_out, uint64_t n_samples, int shared_cloud);
+/* Introspection hook (test suite): HIP source (hy_free_str()) and gfx950 code object (owned by the integrator) of the
+ * Taylor-map module of a variational integrator. Either output may be NULL. */
+int hy_tab_taylor_map_module(hy_tab, char **source, const char **data, size_t *size);
+/* The source of the module for (n_orig_sv, n_args, order) without an integrator. lds_bytes: LDS the cloud kernel may use per
+ * workgroup for coefficients (0: the default, 16 KiB) - beyond it the outputs are processed in groups; *note (may be NULL,
+ * hy_free_str()) receives the stage logger's line about the decision. */
+char *hy_taylor_map_source(uint32_t n_orig_sv, uint32_t n_args, uint32_t order, size_t lds_bytes, char **note);
 /* Accounting of the steps with events (bench.py's events leg). out8 = {steps with events, ms upload / buffers, ms stepper
  * (+ event jets), ms detection kernel, ms bookkeeping kernel + flags to the host, ms state update + records, regeneration
  * launches of the Taylor coefficients, systems which reported events}; the five phase times accumulate only while the
