@@ -1762,6 +1762,8 @@ bool match_pair_distance_event(const taylor_program &p, std::uint32_t u, pair_di
     return true;
 }
 
+// (hip_emit_cluster.cpp; behind it emit_cluster_v2() - hip_emit_cluster2*.cpp - and emit_cluster_v1(). The dispatch below reads
+// emitted_module::cluster_generation and emitted_module::block_v2_phase, never the prose of the notes.)
 emitted_module emit_cluster_or_empty(const taylor_program &, const emit_options &, std::string &why_not);
 emitted_module emit_cluster_multi_or_empty(const taylor_program &, const emit_options &, std::string &why_not);
 emitted_module emit_table(const taylor_program &, const emit_options &);
@@ -1867,18 +1869,9 @@ emitted_module emit_hip_module(const taylor_program &prog, const emit_options &o
             // sum / sub / negation trees, reactions as glue nodes of their own) miss the one-lane-per-pair kernel only
             // because of that: retry on the internal program with the accelerations flattened (linearise_accelerations()).
             // (Generations of the wave-cluster kernels, best first: one lane per pair, lane pairs, pipelined, first one.)
-            const auto kernel_rank = [](const emitted_module &em) {
-                if (em.source.empty()) {
-                    return 0;
-                }
-                for (const auto &[tag, r] : {std::pair{"cluster mode v5", 4}, std::pair{"cluster mode v3", 3}, std::pair{"cluster mode v2", 2}}) {
-                    if (em.notes.find(tag) != std::string::npos) {
-                        return r;
-                    }
-                }
-                return 1;
-            };
-            if (opts.dev.linearise && !opts.dev.cluster_v1 && opts.cluster_kernel != 1 && kernel_rank(m) < 4) {
+            // (emitted_module::cluster_generation: 5 > 3 > 2 > 1.)
+            const auto kernel_rank = [](const emitted_module &em) { return em.source.empty() ? 0 : em.cluster_generation; };
+            if (opts.dev.linearise && !opts.dev.cluster_v1 && opts.cluster_kernel != 1 && kernel_rank(m) < 5) {
                 taylor_program lin;
                 if (linearise_accelerations(prog, lin)) {
                     std::string w2;
@@ -2012,14 +2005,14 @@ emitted_module emit_hip_module(const taylor_program &prog, const emit_options &o
                 // (Distinct masses: the scalings of the pair products sit inside the clusters, which keeps the decomposition off
                 // the v2 cluster phase - rolled order loop, rows in registers, index-pair convolutions. externalise_scalings()
                 // gives the internal program the clusters of the equal-mass system, the scalings become glue nodes.)
-                if (opts.dev.linearise && b.notes.find("v2 cluster phase") == std::string::npos && !opts.exact_division) {
+                if (opts.dev.linearise && !b.block_v2_phase && !opts.exact_division) {
                     taylor_program ext;
                     if (externalise_scalings(prog, ext)) {
                         std::string wl;
                         auto o2 = opts;
                         o2.block_no_absorb = true;
                         auto b2 = emit_block(ext, o2, wl);
-                        if (!b2.source.empty() && b2.notes.find("v2 cluster phase") != std::string::npos) {
+                        if (!b2.source.empty() && b2.block_v2_phase) {
                             b2.notes += "; scalings of the pair products moved out of the clusters in the internal program (c (d "
                                         "r^-3) for d (c r^-3): equal to the decomposition to rounding)";
                             b2.internal_program = program_to_string(ext);

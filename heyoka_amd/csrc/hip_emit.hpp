@@ -81,7 +81,7 @@ enum class emit_mode { unrolled, cluster, table, block };
 //   HEYOKA_AMD_STAGED_WPS=1|2|4       staged table stepper: wavefronts per system (default: by the size of the tape)
 //   HEYOKA_AMD_EV_INLINE_MAX_NONLINEAR  budget of nonlinear nodes of the event equations inside the stepper
 //   HEYOKA_AMD_V5_PRIO, HEYOKA_AMD_V5_OPTS, HEYOKA_AMD_V5_PAD   one-lane-per-pair kernel: issue priorities, round-5 items
-//                                     switched off one by one (A/B harness), sensitivity padding (see hip_emit_cluster2.cpp)
+//                                     switched off one by one (A/B harness), sensitivity padding (see hip_emit_cluster2_gen.hpp)
 // (HEYOKA_AMD_EMIT_MODE, HEYOKA_AMD_ONE_LANE, HEYOKA_AMD_PAIR_SPLIT, HEYOKA_AMD_EVENTS_ON_CLUSTER map onto kwargs of the
 // integrator - taylor_adaptive_batch.cpp -; HEYOKA_AMD_HIPRTC_FLAGS, HEYOKA_AMD_SCRATCH_GIB, HEYOKA_AMD_GATHER_RCCL and
 // HEYOKA_AMD_EVENTS_TIMING belong to the runtime, not to code generation.)
@@ -173,6 +173,12 @@ struct emitted_module {
     // Statistics (logged like the reference logs decomposition sizes).
     std::uint64_t n_statements = 0;
     std::string notes;
+    // Which generation of the wave-cluster generators wrote the kernel: 0 = not a wave-cluster kernel, otherwise the numbers
+    // of emit_options::cluster_kernel - 1 (first generation, multi-class), 2 (pipelined), 3 (lane pairs), 5 (one lane per
+    // pair). The dispatch in emit_hip_module() reads this, never the prose of `notes`.
+    int cluster_generation = 0;
+    // Block mode: the cluster phase is the rolled "v2 cluster phase" (see hip_emit_block.cpp).
+    bool block_v2_phase = false;
     // Cluster mode: doubles of jet scratch needed per resident wave.
     std::uint64_t scratch_per_wave = 0;
     bool persistent = false;

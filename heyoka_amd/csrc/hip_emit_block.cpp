@@ -2192,6 +2192,7 @@ if (tid == 0u) {
         ret.compile_flags = "-mllvm -disable-machine-licm";
     }
     if (v2) {
+        ret.block_v2_phase = true;
         ret.notes += "; v2 cluster phase: rolled order loop, " + std::to_string(n_iter) + " rounds per lane, rows < "
                      + std::to_string(v2_M) + " of the tape members in registers, the " + std::to_string(v2_hand)
                      + " most recent rows handed over in registers";

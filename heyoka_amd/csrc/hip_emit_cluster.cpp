@@ -2335,6 +2335,7 @@ if (l == 0u && live) {
     ret.lanes_per_system = L;
     ret.lds_bytes = 0;
     ret.mode = emit_mode::cluster;
+    ret.cluster_generation = 1;
     ret.n_statements = e.n_stmt;
     ret.scratch_per_wave = jets_in_lds ? 0u : jet_doubles_per_wave;
     ret.persistent = true;
@@ -2359,6 +2360,8 @@ if (l == 0u && live) {
 
 //V2_PLACEHOLDER
 
+// (hip_emit_cluster2.cpp: the generator object cluster2_gen of hip_emit_cluster2_gen.hpp, with hip_emit_cluster2_layout.cpp and
+// hip_emit_cluster2_orders.cpp; sets emitted_module::cluster_generation to 2, 3 or 5.)
 emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts, std::string &why_not);
 
 // Returns a module with an empty source (and the reason in why_not) if cluster mode is not applicable.

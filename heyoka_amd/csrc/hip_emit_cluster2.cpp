@@ -12,63 +12,78 @@
 //     1-2 terms involving new coefficients remain on the critical path (ssa_emitter::node_partial /
 //     node_finish). Sums are FMA chains;
 //   * divisions by the (constant) order use the exact FMA-based sequence ssa_emitter::div_const().
+// The generator is the object cluster2_gen (hip_emit_cluster2_gen.hpp); this file holds its driver, the selection of the
+// variant and emit_cluster_v2(), the retry loop over the lanes per system.
 #include <algorithm>
-#include <array>
 #include <cstdio>
-#include <cstdlib>
 #include <functional>
-#include <map>
-#include <set>
-#include <tuple>
 
-#include "hip_emit_cluster_plan.hpp"
-#include "hip_emit_detail.hpp"
+#include "hip_emit_cluster2_gen.hpp"
 #include "logging.hpp"
 
-namespace heyoka_amd
+namespace heyoka_amd::cluster2_detail
 {
 
-namespace
+cluster2_gen::cluster2_gen(const taylor_program &p_, const emit_options &opts_, std::string &why_not_, bool allow_one_lane_,
+                           std::uint32_t min_lanes_)
+    : c2_emit(p_, opts_.order), p(p_), opts(opts_), why_not(why_not_), allow_one_lane(allow_one_lane_), min_lanes(min_lanes_),
+      n_eq(p_.n_eq), order(opts_.order)
 {
+    std::string s = opts.dev.v5_opts;
+    std::replace(s.begin(), s.end(), '+', ',');
+    for (std::size_t b = 0, en = 0; b <= s.size(); b = en + 1u) {
+        en = std::min(s.find(',', b), s.size());
+        v5_flags.insert(s.substr(b, en - b));
+    }
+}
 
-// (min_lanes: the smallest number of lanes per system of the one-lane-per-pair kernel - see emit_cluster_v2().)
-emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options &opts, std::string &why_not, bool allow_one_lane,
-                                    bool &one_lane_jets_in_lds, std::uint32_t min_lanes = 4)
+// The stages in the order the text is produced; a stage which refuses leaves the reason in why_not (empty until then:
+// the first stage assigns it) and the module empty.
+cluster2_attempt cluster2_gen::run()
 {
-    using cluster_detail::cluster_plan;
-    using cluster_detail::is_var;
-    using emit_detail::prelude;
-    using emit_detail::rhofac;
-    using emit_detail::ssa_emitter;
-
-    emitted_module ret;
-    // Experiment switches of this generator: ONE environment variable, HEYOKA_AMD_V5_OPTS, a comma-separated list of flags
-    // (profiles/experiments/ab.py compares variants inside one process). Every flag switches OFF one of the round-5 items:
-    //   nomsq     three accumulators for the half sums of squares (one per coordinate) instead of one;
-    //   nopack2   the final evaluation of a partially filled owner slot as a full two-series pass;
-    //   notailrd  the jet reads of the final evaluation behind the step size instead of ahead of the selector;
-    const auto v5_flag = [&opts](const char *name) {
-        if (opts.dev.v5_opts.empty()) {
-            return false;
+    static constexpr void (cluster2_gen::*const stages[])() = {
+        &cluster2_gen::plan_and_select_variant, &cluster2_gen::anchors_and_reaction_fusion, &cluster2_gen::layout_one_lane,
+        &cluster2_gen::lds_layout_and_lane_tables, &cluster2_gen::build_glue_rounds, &cluster2_gen::layout_jets_and_schedule,
+        &cluster2_gen::init_order_programs, &cluster2_gen::emit_step_body,
+        &cluster2_gen::text_helpers_and_constant_tables, &cluster2_gen::text_kernel_prologue, &cluster2_gen::text_event_equations,
+        &cluster2_gen::text_pickup, &cluster2_gen::text_selector, &cluster2_gen::text_event_exclusion,
+        &cluster2_gen::text_final_evaluation_and_update, &cluster2_gen::text_refill_and_tail, &cluster2_gen::finish};
+    for (const auto stage : stages) {
+        (this->*stage)();
+        if (!why_not.empty()) {
+            break;
         }
-        std::string s = std::string(",") + opts.dev.v5_opts + ",";
-        std::replace(s.begin(), s.end(), '+', ','); // ('+' separates flags where ',' separates variables: ab.py)
-        return s.find(std::string(",") + name + ",") != std::string::npos;
-    };
-    cluster_plan pl;
+    }
+    return std::move(res);
+}
+
+// The glue nodes are numbered after the cluster outputs (both pair kernels).
+void cluster2_gen::number_glue_slots(std::uint32_t ns)
+{
+    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
+        if (pl.cluster_of[u] == -1) {
+            pl.slot_of[u] = static_cast<int>(ns++);
+        }
+    }
+    pl.n_slots = ns;
+}
+
+// Stages 0 / 0b / 0c: the plan (cluster_detail::make_plan(), pair pattern), which of the three kernels serves it, the lanes
+// per system, the slab slots of the cluster outputs in lane order, the reactions fused into the sums. Reads p, opts,
+// allow_one_lane, min_lanes; leaves pl, pp, cu, the variant flags, the lane geometry (L, spw, bs, wpb, n_ext, n_out, n_cst)
+// and frx (with the nodes of the sum group reordered).
+void cluster2_gen::plan_and_select_variant()
+{
     // Parameter operands are per-lane values here (e.g. kw::masses = par[...]: the pair clusters differ only by the
     // indices of the parameters they read).
     cluster_detail::plan_limits plim;
     plim.generic_pars = true;
     why_not = cluster_detail::make_plan(p, opts.order, pl, plim);
     if (!why_not.empty()) {
-        return ret;
+        return;
     }
-    const auto cu = constant_uvars(p);
-
-    const auto n_eq = p.n_eq, order = opts.order;
-    const auto nc = static_cast<std::uint32_t>(pl.clusters.size());
-    const auto &t0 = pl.clusters[0];
+    cu = constant_uvars(p);
+    nc = static_cast<std::uint32_t>(pl.clusters.size());
 
     // ---- 0. Lane-pair variant ("v3"): point-mass pair clusters {d_0, d_1, d_2 = coordinate differences,
     // sum_sq(d_0, d_1, d_2), pow(sum_sq, alpha), [c * pow], d_i * pow, [c_i * (d_i * pow)]} are split over TWO lanes:
@@ -78,7 +93,6 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // issue slot of the FP64 pipe (profiles/ubench/issue_rate.hip), with two they overlap with the other wavefront's
     // arithmetic. The two lanes run ONE instruction stream: the chains are matched so that the same FMA is useful
     // work on both lanes with different register contents (see emit_pair_order below).
-    cluster_detail::pair_pattern pp;
     cluster_detail::detect_pair_pattern(p, pl, pp);
     const bool pp_shape_ok = pp.ok;
     {
@@ -88,7 +102,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         // clamped to zero (a nan from the selector of a non-finite state survives the clamp), fixed by forcing h = 0.
         pp.ok = ok && 2u * nc <= 64u && p.n_par == 0u && (opts.cluster_kernel == 0 || opts.cluster_kernel >= 3);
     }
-    const bool m4 = opts.event_stepper;
+    m4 = opts.event_stepper;
     // ---- 0b. One lane per pair, two wavefronts per SIMD ("v5"): the lane-pair split halves the histories a lane keeps
     // (4 x 20 doubles) so that the kernel fits in 256 registers, but every piece of work outside the convolution
     // chains - the role union of the finishing operations, the glue round, the serial tail of the step - is then paid
@@ -100,7 +114,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // state variables of 32 systems per CU do not fit in LDS (199 KB): only the velocity-type variables (the ones
     // defined by a glue node) are stored, the coefficients of the position-type ones (x' = v) are re-derived in the final
     // evaluation as x^[k] = v^[k-1] * RN(1 / k) - the very operation which produced them.
-    const bool one_lane = [&]() {
+    one_lane = [&]() {
         if (!allow_one_lane) {
             return false;
         }
@@ -114,9 +128,9 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     if (one_lane) {
         pp.ok = false;
     }
-    const bool pair_split = pp.ok;
+    pair_split = pp.ok;
     // (Shared by the two pair-pattern kernels: fused reactions, merged schedule, reciprocal-based divisions.)
-    const bool pairk = pair_split || one_lane;
+    pairk = pair_split || one_lane;
     if (pair_split) {
         pl.L = 2;
         while (pl.L < 2u * nc) {
@@ -140,12 +154,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             }, 2u * nc);
             number([&](std::uint32_t c) { return pl.clusters[c][static_cast<std::uint32_t>(pp.rx[1])]; }, nc);
         }
-        for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-            if (pl.cluster_of[u] == -1) {
-                pl.slot_of[u] = static_cast<int>(ns++);
-            }
-        }
-        pl.n_slots = ns;
+        number_glue_slots(ns);
     }
     if (one_lane) {
         pl.L = min_lanes;
@@ -169,21 +178,17 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
                 pl.slot_of[pl.clusters[c][static_cast<std::uint32_t>(pp.rx[i])]] = static_cast<int>(ns++);
             }
         }
-        for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-            if (pl.cluster_of[u] == -1) {
-                pl.slot_of[u] = static_cast<int>(ns++);
-            }
-        }
-        pl.n_slots = ns;
+        number_glue_slots(ns);
     }
-    const auto L = pl.L, spw = pl.spw;
+    L = pl.L, spw = pl.spw;
     // (Lane pairs / one lane per pair: 512 threads = two wavefronts per SIMD.)
-    const std::uint32_t bs = pairk ? 512u : 256u;
-    const std::uint32_t wpb = bs / 64u;
-    const auto n_ext = static_cast<std::uint32_t>(pl.ext_u[0].size());
-    const auto n_out = static_cast<std::uint32_t>(pl.out_pos.size());
-    const auto n_cst = static_cast<std::uint32_t>(pl.cst_pos.size());
+    bs = pairk ? 512u : 256u;
+    wpb = bs / 64u;
+    n_ext = static_cast<std::uint32_t>(pl.ext_u[0].size());
+    n_out = static_cast<std::uint32_t>(pl.out_pos.size());
+    n_cst = static_cast<std::uint32_t>(pl.cst_pos.size());
 
+    variant = one_lane ? cluster2_variant::one_lane : (pair_split ? cluster2_variant::lane_pair : cluster2_variant::pipelined);
     // ---- 0c. One lane per pair: reactions fused into the acceleration sums ("frx", round 5). The sensitivity experiment
     // (profiles/r05_sensitivity_marginal_costs.log) prices an LDS store at ~30 cycles of the issuing wavefront's time, five
     // FMAs; 3 of the 8 stores of an order are the reactions c * (d_i * sa), values which differ from the direct products
@@ -194,7 +199,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // Registers are what this costs (five coefficient doubles per lane through the orders), so the coefficients exist only
     // once: the nodes of the sum group are reordered so that the sums made of direct products alone (the first body of every
     // pair it takes part in) come last - the rounds after the first are then plain sums without coefficients.
-    bool frx = false;
+    frx = false;
     if (one_lane && !m4 && pp.rx[0] >= 0 && pl.groups.size() == 1u && !v5_flag("nofrx")) {
         auto &nodes = pl.groups[0].nodes;
         std::map<std::uint32_t, bool> is_rx_out; // cluster output -> is it a reaction?
@@ -232,7 +237,12 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             }
         }
     }
+}
 
+// Stage 1, first part. Reads the plan, the pair pattern and frx; leaves att, grp_natt, the slab slots of the state variables
+// renumbered in owner order, rx_fused, rx_src, fuse_rx, frx (final) and glue_read.
+void cluster2_gen::anchors_and_reaction_fusion()
+{
     // ---- 1. Anchor every state variable to the glue node at the root of its rhs chain. ----
     // anchor[i] = glue u variable, depth[i] >= 1.
     std::vector<int> anchor(n_eq, -1);
@@ -243,13 +253,13 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         for (;;) {
             if (!seen.insert(cur).second) {
                 why_not = "cyclic chain of state-variable definitions";
-                return ret;
+                return;
             }
             const auto &def = p.sv_defs[cur];
             ++d;
             if (def.type != operand::kind::uvar) {
                 why_not = "a state variable is defined by a constant or a parameter";
-                return ret;
+                return;
             }
             if (def.idx < n_eq) {
                 cur = def.idx;
@@ -257,7 +267,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             }
             if (pl.cluster_of[def.idx] != -1) {
                 why_not = "a state variable is defined directly by a cluster member";
-                return ret;
+                return;
             }
             anchor[i] = static_cast<int>(def.idx);
             depth[i] = d;
@@ -265,7 +275,6 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         }
     }
     // att[u] = state variables anchored at glue node u, sorted by depth.
-    std::map<std::uint32_t, std::vector<std::uint32_t>> att;
     for (std::uint32_t i = 0; i < n_eq; ++i) {
         att[static_cast<std::uint32_t>(anchor[i])].push_back(i);
     }
@@ -275,18 +284,18 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             // Chain shape: depths 1, 2, 3, ... each defined by the previous one (or by the anchor).
             if (depth[v[j]] != j + 1u) {
                 why_not = "branching state-variable chains";
-                return ret;
+                return;
             }
             const auto &def = p.sv_defs[v[j]];
             const auto expect = (j == 0u) ? u : v[j - 1u];
             if (def.idx != expect) {
                 why_not = "branching state-variable chains";
-                return ret;
+                return;
             }
         }
     }
     // All the nodes of a glue group must carry the same number of attached variables.
-    std::vector<std::uint32_t> grp_natt(pl.groups.size(), 0);
+    grp_natt.assign(pl.groups.size(), 0);
     for (std::size_t g = 0; g < pl.groups.size(); ++g) {
         const auto &nodes = pl.groups[g].nodes;
         const auto it0 = att.find(nodes[0]);
@@ -296,7 +305,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             const auto n = it == att.end() ? 0u : static_cast<std::uint32_t>(it->second.size());
             if (n != n0) {
                 why_not = "glue nodes of one group with different state-variable chains";
-                return ret;
+                return;
             }
         }
         grp_natt[g] = n0;
@@ -319,7 +328,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         }
         if (next != n_eq) {
             why_not = "internal error: state-variable slots";
-            return ret;
+            return;
         }
     }
 
@@ -328,9 +337,9 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // and multiply it by a per-lane coefficient (c, or 1.0 where the sum reads the direct product itself: exact, so the
     // rounding sequence of every term is the one of the separate node). Two LDS stores less per order and lane.
     // rx_fused[u] = 1 for the fused members; rx_src[u] = the product they scale.
-    std::vector<char> rx_fused(p.n_u, 0);
-    std::vector<std::uint32_t> rx_src(p.n_u, 0);
-    bool fuse_rx = false;
+    rx_fused.assign(p.n_u, 0);
+    rx_src.assign(p.n_u, 0);
+    fuse_rx = false;
     if (pairk && pp.rx[0] >= 0) {
         // (One-lane pair kernel: the reactions are computed and exported by the pair lane - the slab of a system is
         // single-buffered there and has room for them - so that the sums need no per-lane coefficients: 20 registers.)
@@ -370,7 +379,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     }
     frx = frx && fuse_rx;
     // A glue node / state variable needs a slab slot only if somebody reads it through the slab.
-    std::vector<char> glue_read(p.n_u, 0);
+    glue_read.assign(p.n_u, 0);
     for (const auto &n : p.nodes) {
         for (const auto &o : n.args) {
             if (is_var(o)) {
@@ -378,27 +387,25 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             }
         }
     }
-    std::vector<std::uint32_t> lane_pr, lane_rx; // one-lane pair kernel: output slot triples of the lanes
-    bool wide_rd = false;                        // ... wide-read layout: slots arranged by consumer (see below)
-    // ... velocity exchange: the pair lanes take the coordinate differences from the velocity jets, d^[k] = (v_a^[k-1] - v_b^[k-1])
-    // RN(1 / k), and no position coefficient is published (see below). vx_col[l] = first jet column of the two bodies of lane l.
-    bool vexch = false;
-    std::vector<std::array<std::uint32_t, 2>> vx_col;
-    std::vector<std::array<std::uint32_t, 3>> wide_pr, wide_rx; // ... its output slots, per lane and coordinate
-    std::uint32_t slab_stride_opt = 0;
-    std::uint64_t bank_cost = 0;
+}
+
+// Stage 1, one-lane pair kernel only: the slab of a system. Reads glue_read, the fusion flags and the stages before it;
+// leaves bk_in_slab, wide_rd, vexch, vx_col, the slab compacted to the slots which are read through it, the lane permutations
+// lane_pr / lane_rx (or wide_pr / wide_rx), slab_stride_opt and bank_cost of the bank-model search, pl.slot_of, pl.n_slots.
+void cluster2_gen::layout_one_lane()
+{
     // One-lane pair kernel: the bookkeeping block of a system (16 doubles parked between the tails of two steps) sits at the
     // end of its slab instead of in an array of its own - its address is the slab pointer + a constant, and the register
     // which held it (spilled: two scratch reloads per step) is gone: +0.7 %, profiles/r05_ab_bookkeeping_in_slab.log (a
     // laundered system index in the retire block, against hoisted address arithmetic, measured nothing).
-    const bool bk_in_slab = one_lane && !v5_flag("nobkslab");
+    bk_in_slab = one_lane && !v5_flag("nobkslab");
     if (one_lane) {
         // 32 systems per CU: the slab only keeps the slots which are read through it (positions, products, glue nodes
         // with readers): 63 instead of 144 for the outer Solar System.
         for (std::size_t g = 0; g < pl.groups.size(); ++g) {
             if (grp_natt[g] > 2u) {
                 why_not = "one-lane pair kernel: state-variable chains longer than two";
-                return ret;
+                return;
             }
         }
         // ---- Wide-read layout (round 5). A wavefront pays ~7 cycles of its own time for every LDS instruction it issues
@@ -414,17 +421,11 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         // distance between the slabs of two systems comes out of a scan with the bank model of the guide (reads in the lane
         // groups of each instruction width).
         wide_rd = !v5_flag("nowide") && pp.rx[0] >= 0 && pl.groups.size() == 1u;
-        std::vector<std::array<std::uint32_t, 3>> bodies; // position variables (x, y, z) of every body
-        std::vector<std::uint32_t> node_coord, node_rank;   // per node of the glue group
-        std::uint32_t n_rank = 0, n_args = 0;
         if (wide_rd) {
             std::map<std::uint32_t, std::pair<std::uint32_t, std::uint32_t>> pos_of; // position variable -> (body, coordinate)
             for (std::uint32_t c = 0; c < nc && wide_rd; ++c) {
                 for (std::uint32_t sd = 0; sd < 2u; ++sd) {
-                    std::array<std::uint32_t, 3> tr{};
-                    for (std::uint32_t i = 0; i < 3u; ++i) {
-                        tr[i] = pl.ext_u[c][pp.de[i][sd]];
-                    }
+                    const auto tr = body_vars(c, sd);
                     auto it = std::find(bodies.begin(), bodies.end(), tr);
                     if (it == bodies.end()) {
                         bodies.push_back(tr);
@@ -542,10 +543,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
                 for (std::uint32_t l = 0; l < pl.L; ++l) {
                     const auto c = l < nc ? l : 0u;
                     for (std::uint32_t sd = 0; sd < 2u; ++sd) {
-                        std::array<std::uint32_t, 3> tr{};
-                        for (std::uint32_t i = 0; i < 3u; ++i) {
-                            tr[i] = pl.ext_u[c][pp.de[i][sd]];
-                        }
+                        const auto tr = body_vars(c, sd);
                         vx_col[l][sd] = body_col[static_cast<std::size_t>(std::find(bodies.begin(), bodies.end(), tr) - bodies.begin())];
                     }
                 }
@@ -740,475 +738,38 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         }
         bank_cost = best;
         pl.n_slots = ns;
-
         if (wide_rd) {
-            const auto W = (n_args + 2u) & ~1u; // slots of an operand array (>= one spare slot, even)
-            const auto nb = static_cast<std::uint32_t>(bodies.size());
-            const auto &grp = pl.groups[0];
-            // Address lists of the LDS instructions of a round (doubles, relative to the slab of the system), per lane of a
-            // system; filled for a given layout by addr_lists().
-            struct lds_op {
-                int width; // 16: ds_read_b128, 8: ds_read_b64, -8: ds_write_b64
-                std::vector<std::uint32_t> addr;
-            };
-            std::vector<std::uint32_t> perm(n_rank);
-            for (std::uint32_t r = 0; r < n_rank; ++r) {
-                perm[r] = r;
-            }
-            // (Velocity exchange: no position slots.)
-            const auto pos_sz = vexch ? 0u : 4u * nb;
-            std::uint32_t Dd = W * n_rank, pos_base = 0, op_base = pos_sz;
-            // Position of operand a of the sums of rank r inside a coordinate block: arr_pos[r][a]. Default: arrays of W slots
-            // one after the other; replaced below by a placement without store conflicts where one exists.
-            std::vector<std::vector<std::uint32_t>> arr_pos(n_rank, std::vector<std::uint32_t>(n_args));
-            for (std::uint32_t r = 0; r < n_rank; ++r) {
-                for (std::uint32_t a = 0; a < n_args; ++a) {
-                    arr_pos[r][a] = W * r + a;
-                }
-            }
-            std::uint32_t dummy_pos[2] = {W - 1u, 2u * W - 1u}; // (spare slots of the arrays of rank 0 / rank 1)
-            std::uint32_t blk_used = W * n_rank;                 // (slots of a coordinate block)
-            const auto op_slot = [&](std::uint32_t coord, std::uint32_t rank, std::uint32_t a) {
-                return op_base + Dd * coord + arr_pos[rank][a];
-            };
-            const auto out_slot = [&](std::uint32_t u) {
-                // (u: an exported cluster output: the slot of the operand position which reads it.)
-                for (std::size_t j = 0; j < grp.nodes.size(); ++j) {
-                    const auto &nd = p.nodes[grp.nodes[j] - n_eq];
-                    for (std::uint32_t a = 0; a < n_args; ++a) {
-                        if (nd.args[a].idx == u) {
-                            return op_slot(node_coord[j], node_rank[j], a);
-                        }
-                    }
-                }
-                return 0u;
-            };
-            // (Dummy slots of the idle lanes: the spare slot of the arrays of rank 0 (products) and rank 1 (reactions).)
-            const auto dummy_pr = [&](std::uint32_t i) { return op_base + Dd * i + dummy_pos[0]; };
-            const auto dummy_rx = [&](std::uint32_t i) { return op_base + Dd * i + dummy_pos[1]; };
-            // Which operand position reads the outputs of every cluster (independent of the layout parameters).
-            std::vector<std::array<std::uint32_t, 3>> pr_ref(nc), rx_ref(nc); // (node index j, argument) packed: j * 8 + a
-            for (std::uint32_t c = 0; c < nc; ++c) {
-                for (std::uint32_t i = 0; i < 3u; ++i) {
-                    for (int kind = 0; kind < 2; ++kind) {
-                        const auto u = pl.clusters[c][kind == 0 ? pp.pr[i] : static_cast<std::uint32_t>(pp.rx[i])];
-                        std::uint32_t ref = ~0u;
-                        for (std::size_t j = 0; j < grp.nodes.size(); ++j) {
-                            const auto &nd = p.nodes[grp.nodes[j] - n_eq];
-                            for (std::uint32_t a = 0; a < n_args; ++a) {
-                                if (nd.args[a].idx == u) {
-                                    ref = static_cast<std::uint32_t>(j) * 8u + a;
-                                }
-                            }
-                        }
-                        (kind == 0 ? pr_ref : rx_ref)[c][i] = ref;
-                    }
-                }
-            }
-            // (The three stores of a lane must differ by the block distance: same rank and argument for the three coordinates.)
-            for (std::uint32_t c = 0; c < nc && wide_rd; ++c) {
-                for (const auto *ref : {&pr_ref, &rx_ref}) {
-                    const auto r0 = (*ref)[c][0];
-                    for (std::uint32_t i = 0; i < 3u; ++i) {
-                        const auto ri = (*ref)[c][i];
-                        if (ri == ~0u || r0 == ~0u) {
-                            wide_rd = wide_rd && ri == r0; // (unread outputs: all three or none)
-                            continue;
-                        }
-                        wide_rd = wide_rd && node_coord[ri / 8u] == i && node_rank[ri / 8u] == node_rank[r0 / 8u] && ri % 8u == r0 % 8u;
-                    }
-                }
-            }
-            const auto ref_slot = [&](std::uint32_t ref) { return op_slot(node_coord[ref / 8u], node_rank[ref / 8u], ref % 8u); };
-            const auto addr_lists = [&]() {
-                std::vector<lds_op> ops;
-                // Position reads of the pair lanes: per side a ds_read_b128 (x, y) and a ds_read_b64 (z).
-                for (std::uint32_t sd = 0; sd < (vexch ? 0u : 2u); ++sd) {
-                    lds_op o16{16, std::vector<std::uint32_t>(pl.L)}, o8{8, std::vector<std::uint32_t>(pl.L)};
-                    for (std::uint32_t l = 0; l < pl.L; ++l) {
-                        const auto c = l < nc ? l : 0u;
-                        std::array<std::uint32_t, 3> tr{};
-                        for (std::uint32_t i = 0; i < 3u; ++i) {
-                            tr[i] = pl.ext_u[c][pp.de[i][sd]];
-                        }
-                        const auto b = static_cast<std::uint32_t>(std::find(bodies.begin(), bodies.end(), tr) - bodies.begin());
-                        o16.addr[l] = pos_base + 4u * b;
-                        o8.addr[l] = pos_base + 4u * b + 2u;
-                    }
-                    ops.push_back(std::move(o16));
-                    ops.push_back(std::move(o8));
-                }
-                // Operand reads of the glue rounds.
-                const auto n_nodes = static_cast<std::uint32_t>(grp.nodes.size());
-                for (std::uint32_t r = 0; r * pl.L < n_nodes; ++r) {
-                    for (std::uint32_t a = 0; a < n_args; a += 2u) {
-                        lds_op o{a + 1u < n_args ? 16 : 8, std::vector<std::uint32_t>(pl.L)};
-                        for (std::uint32_t l = 0; l < pl.L; ++l) {
-                            const auto j = r * pl.L + l < n_nodes ? r * pl.L + l : r * pl.L;
-                            o.addr[l] = op_slot(node_coord[j], node_rank[j], a);
-                        }
-                        ops.push_back(std::move(o));
-                    }
-                    // The position coefficients which the round publishes.
-                    if (vexch) {
-                        continue;
-                    }
-                    lds_op ow{-8, std::vector<std::uint32_t>(pl.L)};
-                    for (std::uint32_t l = 0; l < pl.L; ++l) {
-                        if (r * pl.L + l >= n_nodes) {
-                            ow.addr[l] = pos_sz + 2u * Dd + blk_used; // (the dummy area)
-                            continue;
-                        }
-                        const auto j = r * pl.L + l;
-                        // (The position variable attached to the node: second member of its chain.)
-                        const auto &ch = att.at(grp.nodes[j]);
-                        std::uint32_t slot = 0;
-                        for (const auto var : ch) {
-                            for (std::uint32_t b = 0; b < nb; ++b) {
-                                for (std::uint32_t i = 0; i < 3u; ++i) {
-                                    if (bodies[b][i] == var) {
-                                        slot = pos_base + 4u * b + i;
-                                    }
-                                }
-                            }
-                        }
-                        ow.addr[l] = slot;
-                    }
-                    ops.push_back(std::move(ow));
-                }
-                // Stores of the products and of the reactions.
-                for (int kind = 0; kind < 2; ++kind) {
-                    for (std::uint32_t i = 0; i < 3u; ++i) {
-                        lds_op o{-8, std::vector<std::uint32_t>(pl.L)};
-                        for (std::uint32_t l = 0; l < pl.L; ++l) {
-                            const auto ref = l < nc ? (kind == 0 ? pr_ref : rx_ref)[l][i] : ~0u;
-                            o.addr[l] = ref != ~0u ? ref_slot(ref) : (kind == 0 ? dummy_pr(i) : dummy_rx(i));
-                        }
-                        ops.push_back(std::move(o));
-                    }
-                }
-                return ops;
-            };
-            // Bank model (MI355X_MICROARCH.md, LDS): lane groups per instruction width, banks of 4 bytes; identical addresses
-            // broadcast, every further distinct address on a busy bank costs the group one more LDS cycle.
-            static const std::vector<std::vector<std::uint32_t>> grp128 = [] {
-                std::vector<std::vector<std::uint32_t>> g(4);
-                const std::uint32_t r0[] = {0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27};
-                const std::uint32_t r1[] = {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31};
-                for (const auto x : r0) {
-                    g[0].push_back(x);
-                    g[2].push_back(x + 32u);
-                }
-                for (const auto x : r1) {
-                    g[1].push_back(x);
-                    g[3].push_back(x + 32u);
-                }
-                return g;
-            }();
-            const auto wcost = [&](const std::vector<lds_op> &ops, std::uint32_t stride) {
-                std::uint64_t tot = 0;
-                const auto spw_ = 64u / pl.L;
-                const auto lane_addr = [&](const lds_op &o, std::uint32_t lane) {
-                    return ((lane / pl.L) % spw_) * stride + o.addr[lane % pl.L];
-                };
-                for (const auto &o : ops) {
-                    const auto n_banks = o.width < 0 ? 32u : 64u;
-                    const auto dwords = o.width == 16 ? 4u : 2u;
-                    std::vector<std::vector<std::uint32_t>> groups;
-                    if (o.width == 16) {
-                        groups = grp128;
-                    } else if (o.width == 8) {
-                        groups.assign(2, {});
-                        for (std::uint32_t l = 0; l < 64u; ++l) {
-                            groups[l / 32u].push_back(l);
-                        }
-                    } else {
-                        groups.assign(4, {});
-                        for (std::uint32_t l = 0; l < 64u; ++l) {
-                            groups[l / 16u].push_back(l);
-                        }
-                    }
-                    for (const auto &g : groups) {
-                        std::map<std::uint32_t, std::set<std::uint32_t>> banks;
-                        for (const auto lane : g) {
-                            const auto a = lane_addr(o, lane);
-                            for (std::uint32_t d = 0; d < dwords; ++d) {
-                                banks[(2u * a + d) % n_banks].insert(a);
-                            }
-                        }
-                        std::size_t mx = 1;
-                        for (const auto &[b, st_] : banks) {
-                            (void)b;
-                            mx = std::max(mx, st_.size());
-                        }
-                        tot += (mx - 1u) * (o.width < 0 ? 2u : 1u);
-                    }
-                }
-                return tot;
-            };
-            if (wide_rd) {
-                // Placement of the operand arrays inside a coordinate block. A ds_write_b64 is serviced in four groups of 16
-                // lanes - one system each - over 16 pairs of banks: the 15 pair lanes + 1 idle lane of a system write 16
-                // slots, and the store is conflict free iff those slots are distinct modulo 16. With arrays [t0 .. t4, -] back
-                // to back no order of the bodies achieves that for the products AND the reactions (the operand positions a
-                // sum reads as reactions are the first ones, as products the last ones), and 34 % of the LDS cycles of the
-                // kernel were bank conflicts (profiles/r05_outer_ss_sq_counters.json, first collection). The arrays keep
-                // the two 16-byte pairs (t0, t1), (t2, t3) adjacent - read with two ds_read_b128 from ONE table register - and
-                // let the fifth operand sit anywhere (a second table register): a depth-first search over (array base, place
-                // of the fifth operand) per rank finds a placement in which the slots of every product store and of every
-                // reaction store are distinct modulo 16 (outer Solar System: a block of 34 slots).
-                const auto BLK = 8u * n_rank;
-                bool placed = false;
-                if (!v5_flag("nostoreplace") && n_args >= 2u && n_args <= 5u) {
-                    // Which operand positions of a rank are written by the product store / the reaction store.
-                    std::vector<std::vector<char>> is_rx(n_rank, std::vector<char>(n_args, 0));
-                    std::vector<std::vector<char>> is_wr(n_rank, std::vector<char>(n_args, 0));
-                    for (std::uint32_t c = 0; c < nc; ++c) {
-                        for (int kind = 0; kind < 2; ++kind) {
-                            const auto ref = (kind == 0 ? pr_ref : rx_ref)[c][0];
-                            if (ref != ~0u) {
-                                is_rx[node_rank[ref / 8u]][ref % 8u] = static_cast<char>(kind);
-                                is_wr[node_rank[ref / 8u]][ref % 8u] = 1;
-                            }
-                        }
-                    }
-                    std::vector<std::vector<std::uint32_t>> cur(n_rank, std::vector<std::uint32_t>(n_args));
-                    std::vector<char> used(BLK, 0);
-                    std::uint64_t n_visit = 0;
-                    const std::function<bool(std::uint32_t, std::uint32_t, std::uint32_t)> dfs = [&](std::uint32_t r, std::uint32_t pm,
-                                                                                                 std::uint32_t rm) -> bool {
-                        if (r == n_rank) {
-                            // The stores of the idle lanes: a free slot on the one residue each store leaves free.
-                            std::uint32_t dz[2] = {~0u, ~0u};
-                            for (std::uint32_t z = 0; z < BLK; ++z) {
-                                if (used[z] != 0) {
-                                    continue;
-                                }
-                                if (dz[0] == ~0u && (pm & (1u << (z % 16u))) == 0u) {
-                                    dz[0] = z;
-                                } else if (dz[1] == ~0u && (rm & (1u << (z % 16u))) == 0u) {
-                                    dz[1] = z;
-                                }
-                            }
-                            if (dz[0] == ~0u || dz[1] == ~0u) {
-                                return false;
-                            }
-                            dummy_pos[0] = dz[0];
-                            dummy_pos[1] = dz[1];
-                            return true;
-                        }
-                        const auto n_pair = n_args & ~1u; // operands read in 16-byte pairs
-                        for (std::uint32_t e_ = 0; e_ + n_pair <= BLK; e_ += 2u) {
-                            for (std::uint32_t f_ = 0; f_ < (n_args % 2u == 1u ? BLK : 1u); ++f_) {
-                                if (++n_visit > 4000000u) {
-                                    return false;
-                                }
-                                std::vector<std::uint32_t> ps(n_args);
-                                bool ok = true;
-                                for (std::uint32_t a_ = 0; a_ < n_args; ++a_) {
-                                    ps[a_] = a_ < n_pair ? e_ + a_ : f_;
-                                    ok = ok && used[ps[a_]] == 0 && !(a_ >= n_pair && f_ >= e_ && f_ < e_ + n_pair);
-                                }
-                                if (!ok) {
-                                    continue;
-                                }
-                                std::uint32_t pm2 = pm, rm2 = rm;
-                                for (std::uint32_t a_ = 0; a_ < n_args && ok; ++a_) {
-                                    if (is_wr[r][a_] == 0) {
-                                        continue;
-                                    }
-                                    auto &m_ = is_rx[r][a_] != 0 ? rm2 : pm2;
-                                    const auto bit = 1u << (ps[a_] % 16u);
-                                    ok = (m_ & bit) == 0u;
-                                    m_ |= bit;
-                                }
-                                if (!ok) {
-                                    continue;
-                                }
-                                for (const auto x : ps) {
-                                    used[x] = 1;
-                                }
-                                cur[r] = ps;
-                                if (dfs(r + 1u, pm2, rm2)) {
-                                    return true;
-                                }
-                                for (const auto x : ps) {
-                                    used[x] = 0;
-                                }
-                            }
-                        }
-                        return false;
-                    };
-                    if (pl.L == 16u && dfs(0, 0, 0)) {
-                        arr_pos = cur;
-                        placed = true;
-                    }
-                }
-                if (placed) {
-                    blk_used = std::max(dummy_pos[0], dummy_pos[1]) + 1u;
-                    for (const auto &v : arr_pos) {
-                        for (const auto x : v) {
-                            blk_used = std::max(blk_used, x + 1u);
-                        }
-                    }
-                    blk_used = (blk_used + 1u) & ~1u;
-                }
-                std::uint64_t best_c = ~std::uint64_t(0);
-                auto best_perm = perm;
-                std::uint32_t best_D = Dd, best_stride = 0;
-                // (+ 2: the dummy area behind the arrays - idle lanes of a partially filled glue round publish there.)
-                const auto total_for = [&](std::uint32_t D_) { return pos_sz + 2u * D_ + blk_used + 2u + (bk_in_slab ? 16u : 0u); };
-                // The distance between the coordinate blocks and between the slabs of two systems: scanned with the bank model
-                // (reads in the lane groups of each instruction width; the stores are settled by the placement above).
-                for (std::uint32_t D_ = blk_used; D_ <= blk_used + 6u; D_ += 2u) {
-                    Dd = D_;
-                    const auto ops = addr_lists();
-                    const auto tot = total_for(D_);
-                    for (std::uint32_t st_ = (tot + 1u) & ~1u; st_ < ((tot + 1u) & ~1u) + 32u; st_ += 2u) {
-                        const auto c = wcost(ops, st_);
-                        if (c < best_c) {
-                            best_c = c;
-                            best_D = D_;
-                            best_stride = st_;
-                        }
-                    }
-                }
-                perm = best_perm;
-                Dd = best_D;
-                slab_stride_opt = best_stride;
-                bank_cost = best_c;
-                if (v5_flag("bankdbg")) {
-                    const auto ops = addr_lists();
-                    std::fprintf(stderr, "wide layout: D = %u, stride = %u, cost = %llu, perm =", Dd, best_stride,
-                                 static_cast<unsigned long long>(best_c));
-                    for (const auto x : perm) {
-                        std::fprintf(stderr, " %u", x);
-                    }
-                    std::fprintf(stderr, "\n");
-                    for (const auto &o : ops) {
-                        std::fprintf(stderr, "  width %d cost %llu addr:", o.width,
-                                     static_cast<unsigned long long>(wcost(std::vector<lds_op>{o}, best_stride)));
-                        for (const auto x : o.addr) {
-                            std::fprintf(stderr, " %u", x);
-                        }
-                        std::fprintf(stderr, "\n");
-                    }
-                }
-                // The slots.
-                std::fill(pl.slot_of.begin(), pl.slot_of.end(), -1);
-                for (std::uint32_t b = 0; b < nb && !vexch; ++b) {
-                    for (std::uint32_t i = 0; i < 3u; ++i) {
-                        pl.slot_of[bodies[b][i]] = static_cast<int>(pos_base + 4u * b + i);
-                    }
-                }
-                wide_pr.assign(pl.L, {});
-                wide_rx.assign(pl.L, {});
-                for (std::uint32_t l = 0; l < pl.L; ++l) {
-                    for (std::uint32_t i = 0; i < 3u; ++i) {
-                        const auto rp = l < nc ? pr_ref[l][i] : ~0u, rr = l < nc ? rx_ref[l][i] : ~0u;
-                        wide_pr[l][i] = rp != ~0u ? ref_slot(rp) : dummy_pr(i);
-                        wide_rx[l][i] = rr != ~0u ? ref_slot(rr) : dummy_rx(i);
-                        if (l < nc && rp != ~0u) {
-                            pl.slot_of[pl.clusters[l][pp.pr[i]]] = static_cast<int>(wide_pr[l][i]);
-                        }
-                        if (l < nc && rr != ~0u) {
-                            pl.slot_of[pl.clusters[l][static_cast<std::uint32_t>(pp.rx[i])]] = static_cast<int>(wide_rx[l][i]);
-                        }
-                    }
-                }
-                pl.n_slots = total_for(Dd) - 2u - (bk_in_slab ? 16u : 0u);
-                (void)out_slot;
-            }
+            place_wide_read_slots();
         }
     }
+}
 
+// Stages 2 / 3 up to the glue rounds. Reads pl.n_slots, the slots and the layout decisions; leaves dummy_base, n_slots_tot,
+// buf_stride, slab_stride, frx_regs, the division modes of the emitter and the lane tables of the variant: pt (lane pairs),
+// st1 (one lane per pair), or ext_tbl / out_tbl / cst_tbl / lane_par_tbls with the operand names they give (pipelined).
+void cluster2_gen::lds_layout_and_lane_tables()
+{
     // ---- 2. LDS layout: every slot double-buffered by order parity. ----
     const std::uint32_t max_round_outputs = wide_rd ? 2u : std::max<std::uint32_t>(n_out, one_lane ? 6u : 4u);
-    const auto dummy_base = pl.n_slots;
-    const auto n_slots_tot = pl.n_slots + max_round_outputs;
+    dummy_base = pl.n_slots;
+    n_slots_tot = pl.n_slots + max_round_outputs;
     // One-lane pair kernel: ONE buffer. A system never spans wavefronts and the LDS instructions of a wavefront complete
     // in order, so a round may overwrite what it has read as long as its reads come first in the instruction stream -
     // which is how the merged schedule is emitted: reads of x^[k] and of the products of order k-1, then the stores of
     // the products of order k and of x^[k+1] (the stores may alias the loads as far as the compiler knows: it keeps
     // their order).
-    const auto buf_stride = one_lane ? 0u : n_slots_tot; // doubles between the two parity buffers
+    buf_stride = one_lane ? 0u : n_slots_tot; // doubles between the two parity buffers
     // (One buffer; the stride comes out of the bank-conflict search above.)
-    const auto slab_stride = one_lane ? std::max(slab_stride_opt, n_slots_tot + (bk_in_slab ? 16u : 0u))
+    slab_stride = one_lane ? std::max(slab_stride_opt, n_slots_tot + (bk_in_slab ? 16u : 0u))
                                       : ((2u * n_slots_tot) | 1u); // doubles per system
-
-    // ---- 3. Tables. ----
-    std::vector<std::vector<std::uint32_t>> utbl;
-    std::vector<std::vector<double>> dtbl;
-    // NOTE: tables of slab slots and tables of state-variable indices are kept apart (the slot tables are
-    // renumbered by the bank-conflict optimiser below).
-    std::vector<char> utbl_is_slot;
-    // utexpr[t]: how the kernel refers to the per-lane value of table t - a register loaded at the top of the kernel
-    // ("ut<t>"), or (one-lane pair kernel, where every register counts) an earlier table plus a constant when the two
-    // differ by the same amount on every lane (the three coordinates of a body, the three products of a pair: the
-    // constant folds into the offset field of the LDS instruction).
-    std::vector<std::string> utexpr;
-    const auto add_utbl = [&](std::vector<std::uint32_t> v, bool is_slot = true) {
-        // Deduplicate identical tables.
-        for (std::size_t t = 0; t < utbl.size(); ++t) {
-            if (utbl[t] == v && (utbl_is_slot[t] != 0) == is_slot) {
-                return t;
-            }
-        }
-        std::string ex = "ut" + std::to_string(utbl.size());
-        for (std::size_t t = 0; one_lane && is_slot && t < utbl.size(); ++t) {
-            if (utbl_is_slot[t] == 0 || utexpr[t] != "ut" + std::to_string(t)) {
-                continue;
-            }
-            const auto d = static_cast<std::int64_t>(v[0]) - static_cast<std::int64_t>(utbl[t][0]);
-            bool affine = true;
-            for (std::size_t l2 = 0; l2 < v.size(); ++l2) {
-                affine = affine && (static_cast<std::int64_t>(v[l2]) - static_cast<std::int64_t>(utbl[t][l2]) == d);
-            }
-            if (affine) {
-                ex = "(ut" + std::to_string(t) + (d >= 0 ? " + " : " - ") + std::to_string(d >= 0 ? d : -d) + "u)";
-                break;
-            }
-        }
-        utexpr.push_back(std::move(ex));
-        utbl.push_back(std::move(v));
-        utbl_is_slot.push_back(is_slot ? 1 : 0);
-        return utbl.size() - 1u;
-    };
-    const auto add_dtbl = [&](std::vector<double> v) {
-        dtbl.push_back(std::move(v));
-        return dtbl.size() - 1u;
-    };
-    const auto utname = [&](std::size_t t) { return utexpr[t]; };
-    // (One-lane pair kernel: the per-lane constants live in LDS and are read where they are used - one address register
-    // for all of them instead of two registers each.)
-    const auto dtname = [&](std::size_t t) {
-        return one_lane ? ("dtl[" + std::to_string(t * L) + "]") : ("dt" + std::to_string(t));
-    };
     // (One-lane pair kernel, fused reactions: the coefficients of the sums are loaded once per step - registers through the
     // orders, free again in the tail of the step; "frxlds" among HEYOKA_AMD_V5_OPTS reads them from LDS at every use.)
-    const bool frx_regs = frx && !v5_flag("frxlds");
-    const auto coefname = [&](std::size_t t) { return frx_regs ? ("frc" + std::to_string(t)) : dtname(t); };
-
-    ssa_emitter e(p, order);
-    auto &os = e.os;
+    frx_regs = frx && !v5_flag("frxlds");
     // Lane-pair kernel: x^[k+1] = f^[k] * RN(1 / (k + 1)) - one multiplication, within 1 ulp of the quotient - instead of
     // the exact 3-operation sequence (60 VALU instructions per step, +2.1 % system-steps/s; the strict-contraction parity
     // test passes its 1e4 / 1e5 eps bounds with it). kw::exact_division restores the correctly-rounded quotient.
     e.recip_div = pairk && !opts.exact_division;
     e.enable_pow_rcp(!opts.exact_division);
-
-    // Lane-pair variant: lane l = 2 * pair + role (role 0 = A: d_0, d_1; role 1 = B: d_2 and the pow); the lanes
-    // beyond the last pair replicate pair 0 and write to dummy slots.
-    struct pair_tables {
-        std::size_t s0 = 0, s1 = 0, p0 = 0, p1 = 0, os = 0, op = 0, rs = 0, rp = 0, csc = 0, crs = 0, crp = 0;
-    } pt;
-    // Slab slot through which a product pr travels (its own, or - when only its reaction was exported - that one's).
-    const auto pr_slot = [&](std::uint32_t pr_u, std::uint32_t rx_u, std::uint32_t dflt) {
-        if (pl.slot_of[pr_u] >= 0) {
-            return static_cast<std::uint32_t>(pl.slot_of[pr_u]);
-        }
-        return (fuse_rx && pl.slot_of[rx_u] >= 0) ? static_cast<std::uint32_t>(pl.slot_of[rx_u]) : dflt;
-    };
     if (pair_split) {
         const auto slot_or = [&](std::uint32_t u, std::uint32_t dflt) {
             return pl.slot_of[u] >= 0 ? static_cast<std::uint32_t>(pl.slot_of[u]) : dflt;
@@ -1262,10 +823,6 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             pt.csc = add_dtbl(std::move(csc));
         }
     }
-    // One-lane pair kernel: lane l = pair l (the lanes beyond the last pair replicate pair 0 and write to dummy slots).
-    struct single_tables {
-        std::size_t s[3][2] = {}, o[3] = {}, r[3] = {}, csc = 0, crs = 0;
-    } st1;
     if (one_lane) {
         std::vector<double> csc(L, 1.), crs(L, 0.);
         for (std::uint32_t i = 0; i < 3u; ++i) {
@@ -1293,7 +850,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
                     const auto cv = p.nodes[ru - n_eq].args[0].value;
                     if (i > 0u && cv != crs[l]) {
                         why_not = "one-lane pair kernel: the reaction coefficients of a pair differ between the coordinates";
-                        return ret;
+                        return;
                     }
                     crs[l] = cv;
                 }
@@ -1315,7 +872,7 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             st1.crs = add_dtbl(std::move(crs));
         }
     }
-    std::vector<std::size_t> ext_tbl(n_ext), out_tbl(n_out), cst_tbl(n_cst);
+    ext_tbl.assign(n_ext, 0), out_tbl.assign(n_out, 0), cst_tbl.assign(n_cst, 0);
     for (std::uint32_t x = 0; !pairk && x < n_ext; ++x) {
         std::vector<std::uint32_t> v(L);
         for (std::uint32_t l = 0; l < L; ++l) {
@@ -1337,53 +894,23 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         }
         cst_tbl[x] = add_dtbl(std::move(v));
         const auto [q, a] = pl.cst_pos[x];
-        e.numpar_override[&p.nodes[t0[q] - n_eq].args[a]] = "ccst" + std::to_string(x);
+        e.numpar_override[&p.nodes[t0()[q] - n_eq].args[a]] = "ccst" + std::to_string(x);
     }
-    // Per-lane parameters: tables of parameter indices; the values are loaded when a group of systems is picked up.
-    std::vector<std::size_t> lane_par_tbls;
-    const auto lane_par = [&](std::vector<std::uint32_t> idx) {
-        const auto t = add_utbl(std::move(idx), false);
-        if (std::find(lane_par_tbls.begin(), lane_par_tbls.end(), t) == lane_par_tbls.end()) {
-            lane_par_tbls.push_back(t);
-        }
-        return "lp" + std::to_string(t);
-    };
     for (std::size_t x = 0; !pairk && x < pl.par_pos.size(); ++x) {
         std::vector<std::uint32_t> v(L);
         for (std::uint32_t l = 0; l < L; ++l) {
             v[l] = pl.par_idx[l < nc ? l : 0u][x];
         }
         const auto [q, a] = pl.par_pos[x];
-        e.numpar_override[&p.nodes[t0[q] - n_eq].args[a]] = lane_par(std::move(v));
+        e.numpar_override[&p.nodes[t0()[q] - n_eq].args[a]] = lane_par(std::move(v));
     }
+}
 
-    // Glue rounds (+ the owner slots of the attached state variables).
-    struct owner_slot {
-        std::size_t out_tbl = 0;  // slab slot of the state variable
-        std::size_t var_tbl = 0;  // state-variable index (for the global state array)
-        std::uint32_t col = 0;    // owner slot id
-        std::uint32_t cbase = 0;  // first jet column of the slot (columns are compressed: one per valid lane)
-        std::uint32_t n_valid = 0;
-        std::vector<std::string> xname; // SSA names of the coefficients, by order
-        bool slab_needed = true;        // is one of the variables of the slot read through the slab?
-        // One-lane pair kernel: the second variable of a chain (x' = v) keeps no jet column: its coefficients are
-        // re-derived from the column of the first one (parent) in the final evaluation; cbase then counts the
-        // order-0 entries of the derived variables (their current values).
-        bool derived = false;
-        std::uint32_t parent = 0; // owner slot id of the variable it is derived from
-    };
-    struct glue_round {
-        std::vector<std::size_t> arg_tbl;
-        std::size_t out_tbl = 0;
-        std::uint32_t n_valid = 0; // lanes l < n_valid own a real node
-        bool exported = true;
-        std::vector<owner_slot> owners;
-        std::vector<std::string> par_name; // per-lane parameter value names, by argument (empty: none)
-        std::vector<std::string> c0name;   // names of the constant operands read at order 0, by argument
-        std::vector<std::size_t> coef_tbl; // reaction fusion: per-lane coefficient tables, by argument (empty: not fused)
-    };
-    std::vector<std::vector<glue_round>> rounds(pl.groups.size());
-    std::uint32_t n_own = 0, n_col_acc = 0, n_dcol_acc = 0;
+// Reads the plan, att, the slots and the fusion flags; leaves rounds (with their tables and owner slots), n_own and the
+// numbers of jet columns n_col / n_dcol.
+void cluster2_gen::build_glue_rounds()
+{
+    rounds.assign(pl.groups.size(), {});
     for (std::size_t g = 0; g < pl.groups.size(); ++g) {
         const auto &grp = pl.groups[g];
         const auto n_nodes = static_cast<std::uint32_t>(grp.nodes.size());
@@ -1464,11 +991,11 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
                 if (one_lane && a >= 1u) {
                     ow.derived = true;
                     ow.parent = gr.owners[a - 1u].col;
-                    ow.cbase = n_dcol_acc;
-                    n_dcol_acc += gr.n_valid;
+                    ow.cbase = n_dcol;
+                    n_dcol += gr.n_valid;
                 } else {
-                    ow.cbase = n_col_acc;
-                    n_col_acc += gr.n_valid;
+                    ow.cbase = n_col;
+                    n_col += gr.n_valid;
                 }
                 ow.xname.resize(order + 1u);
                 ow.slab_needed = false;
@@ -1484,46 +1011,34 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     }
     if (n_own == 0u) {
         why_not = "no state variable could be attached to a glue round";
-        return ret;
+        return;
     }
-    // Columns of the state-variable jets: one per state variable (owner slots are compressed: only the valid lanes
-    // of a slot own a column) plus one dummy column per system which absorbs the stores of the idle lanes of a
-    // partially filled slot - they replicate the node of a valid lane, so every statement of the step body is
-    // unconditional (no exec-mask manipulation inside the step loop).
-    const auto n_col = n_col_acc;
-    // (One-lane pair kernel: no dummy column - the idle lanes of a partially filled slot store to the entry they
-    // replicate - and a row is laid out [owner slot][system][lane]: the 32 lanes which a ds_read_b64 services together
-    // (two systems) then touch 32 consecutive doubles, i.e. every bank once.)
-    const auto n_colp = one_lane ? n_col : n_col + 1u;
-    // (One-lane pair kernel: current values of the derived variables, [system of the wave][entry] + one dummy entry.)
-    const auto n_dcol = n_dcol_acc;
-    const auto n_dcolp = one_lane ? n_dcol : n_dcol + 1u;
-    const auto n_hslots = (n_col + L - 1u) / L; // lane slots of the final Horner / compensated evaluation
-    // Position of an owner slot inside a row of the jets (one-lane pair kernel): rows are [owner slot][system][lane] - the 32
-    // lanes which a ds_read_b64 services together touch 32 consecutive doubles - or, with the velocity exchange,
-    // [system][column] - the three coordinates of a body adjacent. jet_off: first entry of the slot for the first system
-    // of the wavefront, jet_sys: distance between two systems.
-    const auto jet_off = [&](const owner_slot &ow) -> std::uint64_t {
-        return vexch ? ow.cbase : static_cast<std::uint64_t>(spw) * ow.cbase;
-    };
-    const auto jet_sys = [&](const owner_slot &ow) -> std::uint32_t { return vexch ? (ow.derived ? n_dcol : n_col) : ow.n_valid; };
+}
+
+// Reads rounds, the columns, the geometry and slab_stride; leaves the layout of the jets (n_colp, n_dcolp, n_hslots,
+// jet_rows_doubles, jet_doubles_per_wave), jet_lds, compact_tc, pk_tbl (three more tables per packed owner slot), merged.
+void cluster2_gen::layout_jets_and_schedule()
+{
+    n_colp = one_lane ? n_col : n_col + 1u;
+    n_dcolp = one_lane ? n_dcol : n_dcol + 1u;
+    n_hslots = (n_col + L - 1u) / L; // lane slots of the final Horner / compensated evaluation
     // Jets of the state variables: [order][system of the wave][column], per wave. Kept in LDS when the
     // block's slab + jets fit in the 160 KB of a CU (the kernel occupies a whole CU anyway: 512 registers
     // per lane), otherwise in a per-wave global scratch.
-    const auto jet_rows_doubles = static_cast<std::uint64_t>(order + 1u) * spw * n_colp;
-    const auto jet_doubles_per_wave = jet_rows_doubles + (one_lane ? static_cast<std::uint64_t>(spw) * n_dcolp : 0u);
+    jet_rows_doubles = static_cast<std::uint64_t>(order + 1u) * spw * n_colp;
+    jet_doubles_per_wave = jet_rows_doubles + (one_lane ? static_cast<std::uint64_t>(spw) * n_dcolp : 0u);
     const auto lds_doubles_slab = static_cast<std::uint64_t>(wpb) * spw * slab_stride;
     // (Mode 4: plus the source table of the cooperative store of the Taylor coefficients, 4 bytes per row.)
     const auto lds_tc_table_bytes = m4 ? static_cast<std::uint64_t>(n_eq) * (order + 1u) * 8u : 0u;
-    const bool jet_lds = (lds_doubles_slab + wpb * jet_doubles_per_wave) * 8u + lds_tc_table_bytes <= 160u * 1024u;
+    jet_lds = (lds_doubles_slab + wpb * jet_doubles_per_wave) * 8u + lds_tc_table_bytes <= 160u * 1024u;
     if (vexch && (!jet_lds || n_dcol != n_col)) {
         why_not = "one-lane pair kernel: the velocity exchange needs the jets in LDS and one position per velocity";
-        return ret;
+        res.more_lanes_cure = true;
+        return;
     }
     // Stepper with events: compact set of Taylor coefficients (see emitted_module::compact_tc) through the cooperative
     // store of the LDS-resident jets. HEYOKA_AMD_COMPACT_TC=0 switches it off (A/B measurements).
-    std::size_t n_tc_rows = 0; // rows of the mode-4 store (set where its source table is emitted)
-    const bool compact_tc = [&]() {
+    compact_tc = [&]() {
         if (!m4 || !jet_lds) {
             return false;
         }
@@ -1548,398 +1063,54 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
         }
         return any;
     }();
-
-    // Final evaluation of a partially filled owner slot with a derived variable (x' = v; 18 velocity columns on 16 lanes
-    // leave 2): ONE series per lane - the lanes [0, n) sum the velocity columns, the lanes [n, 2 n) the series derived from
-    // them, whose coefficient k is row k - 1 of the same column times RN(1 / k). Both kinds run the same statements: where
-    // the lane's current value lives, where row k of its series starts and which row of the factor table (ones / RN(1 / k))
-    // it reads are per-lane table entries (pk_tbl[owner slot] = the three tables).
-    const auto pack_tail_slot = [&](const owner_slot &ow, const owner_slot *dv) {
-        return one_lane && jet_lds && !m4 && opts.high_accuracy && dv != nullptr && !ow.derived && 2u * ow.n_valid <= L
-               && !v5_flag("nopack2");
-    };
-    std::map<std::uint32_t, std::array<std::size_t, 3>> pk_tbl;
-    for (const auto &rg : rounds) {
-        for (const auto &gr : rg) {
-            for (const auto &ow : gr.owners) {
-                for (const auto &o2 : gr.owners) {
-                    if (!(o2.derived && o2.parent == ow.col && pack_tail_slot(ow, &o2))) {
-                        continue;
-                    }
-                    const auto nv = ow.n_valid;
-                    const auto kst = static_cast<std::uint64_t>(spw) * n_colp;
-                    std::vector<std::uint32_t> tv(L), tj(L), tf(L);
-                    for (std::uint32_t l = 0; l < L; ++l) {
-                        const bool isx = l >= nv && l < 2u * nv;
-                        const auto c = isx ? l - nv : (l < nv ? l : 0u);
-                        tv[l] = static_cast<std::uint32_t>((isx ? jet_rows_doubles + jet_off(o2) : jet_off(ow)) + c);
-                        tj[l] = static_cast<std::uint32_t>(jet_off(ow) + c + (isx ? 0u : kst));
-                        tf[l] = isx ? order + 1u : 0u;
-                    }
-                    pk_tbl[ow.col] = {add_utbl(std::move(tv), false), add_utbl(std::move(tj), false), add_utbl(std::move(tf), false)};
-                }
+    for_each_owner([&](auto &gr, auto &ow) {
+        for (const auto &o2 : gr.owners) {
+            if (!(o2.derived && o2.parent == ow.col && pack_tail_slot(ow, &o2))) {
+                continue;
             }
+            const auto nv = ow.n_valid;
+            const auto kst = static_cast<std::uint64_t>(spw) * n_colp;
+            std::vector<std::uint32_t> tv(L), tj(L), tf(L);
+            for (std::uint32_t l = 0; l < L; ++l) {
+                const bool isx = l >= nv && l < 2u * nv;
+                const auto c = isx ? l - nv : (l < nv ? l : 0u);
+                tv[l] = static_cast<std::uint32_t>((isx ? jet_rows_doubles + jet_off(o2) : jet_off(ow)) + c);
+                tj[l] = static_cast<std::uint32_t>(jet_off(ow) + c + (isx ? 0u : kst));
+                tf[l] = isx ? order + 1u : 0u;
+            }
+            pk_tbl[ow.col] = {add_utbl(std::move(tv), false), add_utbl(std::move(tj), false), add_utbl(std::move(tf), false)};
         }
-    }
+    });
 
     // Merged schedule (lane-pair variant, one glue level after the clusters): round k = cluster(k) + glue(k-1),
     // one LDS synchronisation per order instead of two.
-    const bool merged = [&]() {
-        if (!pairk || pl.cluster_level != 1u || pl.max_level != 2u) {
-            return false;
-        }
-        for (const auto &g : pl.groups) {
-            if (g.level != 2u) {
-                return false;
-            }
-        }
-        return true;
-    }();
+    merged = pairk && pl.cluster_level == 1u && pl.max_level == 2u
+             && std::all_of(pl.groups.begin(), pl.groups.end(), [](const auto &g) { return g.level == 2u; });
     if (one_lane && !merged) {
         why_not = "one-lane pair kernel: the merged schedule does not apply";
-        return ret;
+        return;
     }
+}
 
-    // ---- 4. Emission helpers. ----
-    const auto slabk = [&](std::uint32_t k, const std::string &tbl) {
-        // Parity buffer of order k.
-        return (k % 2u == 0u || buf_stride == 0u) ? ("slab[" + tbl + "]")
-                                                  : ("slab[" + tbl + " + " + std::to_string(buf_stride) + "u]");
-    };
-    const auto jet_at = [&](std::uint32_t k, std::uint32_t col) {
-        return "jc" + std::to_string(col) + "[" + std::to_string(static_cast<std::uint64_t>(k) * spw * n_colp) + "]";
-    };
-    const auto sync = [&]() { os << "HY_WSYNC();\n"; };
-    // Where the current value (order 0) of the variables of an owner slot lives: read side (the idle lanes of a partially
-    // filled slot read the entry of a valid lane) and write side (... and write to the dummy entry).
-    const auto row0_r = [&](const owner_slot &ow) {
-        return (ow.derived ? "x0r" : "jr") + std::to_string(ow.col) + "[0]";
-    };
-    const auto row0_w = [&](const owner_slot &ow) {
-        return (ow.derived ? "x0c" : "jc") + std::to_string(ow.col) + "[0]";
-    };
-
-    // Owner-slot bookkeeping when a new coefficient of a state variable is produced.
-    const auto publish_sv = [&](owner_slot &ow, std::uint32_t k, const std::string &name) {
-        ow.xname[k] = name;
-        if (ow.slab_needed) {
-            os << slabk(k, utname(ow.out_tbl)) << " = " << name << ";\n";
-        }
-        if (k != 0u && !ow.derived) {
-            // (The order-0 row of the jets *is* the current state: written by the update of the previous step.)
-            os << jet_at(k, ow.col) << " = " << name << ";\n";
-        }
-        // NOTE: the idle lanes of a partially filled slot hold a copy of a valid lane's coefficient: harmless in a maximum.
-        const char *acc = (k == 0u) ? "m0" : (k == order ? "mo" : (k == order - 1u ? "mom1" : nullptr));
-        if (acc != nullptr) {
-            os << acc << " = hy_nmax(" << acc << ", fabs(" << name << "));\n";
-        }
-    };
-
-    // A 16-byte LDS read of two adjacent slots (wide-read layout: the table entries are even, the slab is 16-byte aligned).
-    std::uint32_t n_wide = 0;
-    const auto wide_read = [&](const std::string &tbl) {
-        const auto nm = "w" + std::to_string(n_wide++);
-        os << "const hy_d2 " << nm << " = *reinterpret_cast<const hy_d2 *>(slab + " << tbl << ");\n";
-        ++e.n_stmt;
-        return nm;
-    };
-    // A glue round is emitted in two halves: the LDS reads of the operands, and the computation (node rule,
-    // export, fused state-variable recursions). In overlap mode independent FMA work is placed in between.
-    const auto emit_glue_reads = [&](std::size_t g, std::uint32_t r, std::uint32_t k) {
-        const auto &grp = pl.groups[g];
-        auto &gr = rounds[g][r];
-        const auto &n0 = p.nodes[grp.nodes[0] - n_eq];
-        std::vector<std::string> names(n0.args.size());
-        for (std::size_t a = 0; a < n0.args.size(); ++a) {
-            if (wide_rd && a + 1u < n0.args.size() && a % 2u == 0u) {
-                // (Operands a, a + 1 of the sum: adjacent slots of the node's operand array.)
-                const auto w = wide_read(utname(gr.arg_tbl[a]));
-                names[a] = w + ".x";
-                names[a + 1u] = w + ".y";
-                ++a;
-                continue;
-            }
-            if (is_var(n0.args[a])) {
-                names[a] = e.def(slabk(k, utname(gr.arg_tbl[a])));
-            }
-        }
-        return names;
-    };
-    const auto emit_glue_compute = [&](std::size_t g, std::uint32_t r, std::uint32_t k,
-                                       const std::vector<std::string> &names) {
-        const auto &grp = pl.groups[g];
-        auto &gr = rounds[g][r];
-        const auto rep = grp.nodes[0];
-        const auto &n0 = p.nodes[rep - n_eq];
-        const auto saved = e.numpar_override;
-        std::vector<std::pair<std::uint32_t, std::string>> saved_vals, saved_vals0;
-        std::string fused_val;
-        if (!gr.coef_tbl.empty()) {
-            // Sum of scaled products, pairwise like the sum rule: ((t0 + t1) + (t2 + t3)) + ..., t_i = c_i * p_i, the
-            // first product of every pair fused into the addition.
-            std::vector<std::string> terms;
-            for (std::size_t a = 0; a + 1u < names.size(); a += 2u) {
-                const auto m = e.def(ssa_emitter::mul(coefname(gr.coef_tbl[a + 1u]), names[a + 1u]));
-                terms.push_back(e.def("__builtin_fma(" + coefname(gr.coef_tbl[a]) + ", " + names[a] + ", " + m + ")"));
-            }
-            const bool odd = names.size() % 2u == 1u;
-            while (terms.size() > 1u) {
-                std::vector<std::string> nt;
-                for (std::size_t i = 0; i + 1u < terms.size(); i += 2u) {
-                    nt.push_back(e.def(terms[i] + " + " + terms[i + 1u]));
-                }
-                if (terms.size() % 2u == 1u) {
-                    nt.push_back(terms.back());
-                }
-                terms = std::move(nt);
-            }
-            if (odd) {
-                const auto a = names.size() - 1u;
-                fused_val = terms.empty() ? e.def(ssa_emitter::mul(coefname(gr.coef_tbl[a]), names[a]))
-                                          : e.def("__builtin_fma(" + coefname(gr.coef_tbl[a]) + ", " + names[a] + ", " + terms[0] + ")");
-            } else {
-                fused_val = terms[0];
-            }
-        }
-        for (std::size_t a = 0; fused_val.empty() && a < n0.args.size(); ++a) {
-            const auto &o = n0.args[a];
-            if (is_var(o)) {
-                saved_vals.emplace_back(o.idx, e.val(o.idx, k));
-                e.val(o.idx, k) = names[a];
-                // Constant operand: the linear rule of ssa_emitter::node() uses the value read at order 0.
-                if (cu[o.idx] != 0) {
-                    if (k == 0u) {
-                        gr.c0name.resize(n0.args.size());
-                        gr.c0name[a] = names[a];
-                    } else {
-                        saved_vals0.emplace_back(o.idx, e.val(o.idx, 0));
-                        e.val(o.idx, 0) = gr.c0name.at(a);
-                    }
-                }
-            } else if (o.type == operand::kind::num) {
-                e.numpar_override[&o] = dtname(gr.arg_tbl[a]);
-            } else if (a < gr.par_name.size() && !gr.par_name[a].empty()) {
-                e.numpar_override[&o] = gr.par_name[a];
-            }
-        }
-        if (n0.kind == func_kind::prod && n0.args[0].type == operand::kind::num && n0.args[0].value == -1.) {
-            e.numpar_override.erase(&n0.args[0]);
-        }
-        if (fused_val.empty()) {
-            e.node(rep - n_eq, k);
-        }
-        const auto gval = fused_val.empty() ? e.val(rep, k) : fused_val;
-        // NOTE: constant nodes are exported at every order too (zeros beyond order 0): a reader whose template position
-        // pairs the constant with a variable in another cluster reads it at every order.
-        if (gr.exported) {
-            os << slabk(k, utname(gr.out_tbl)) << " = " << gval << ";\n";
-        }
-        for (auto it = saved_vals.rbegin(); it != saved_vals.rend(); ++it) {
-            e.val(it->first, k) = it->second;
-        }
-        for (auto it = saved_vals0.rbegin(); it != saved_vals0.rend(); ++it) {
-            e.val(it->first, 0) = it->second;
-        }
-        e.numpar_override = saved;
-
-        // Fused state-variable recursion: x^[k+1] = src^[k] / (k + 1). In the merged schedule the a-th variable of
-        // the chain runs a orders ahead (x^[k+1+a] from the coefficient of order k + a of its predecessor, which
-        // the same lane has just produced): a position is then known one exchange earlier than the acceleration
-        // of the same order, which is what lets cluster(k+1) and glue(k) share one round.
-        for (std::size_t a = 0; a < gr.owners.size(); ++a) {
-            const auto ord = k + 1u + (merged ? static_cast<std::uint32_t>(a) : 0u);
-            if (ord > order) {
-                continue;
-            }
-            const auto src = (a == 0u) ? gval : gr.owners[a - 1u].xname[ord - 1u];
-            const auto x = e.div_const(src, ord);
-            publish_sv(gr.owners[a], ord, x);
-        }
-    };
-    const auto emit_glue_round = [&](std::size_t g, std::uint32_t r, std::uint32_t k) {
-        emit_glue_compute(g, r, k, emit_glue_reads(g, r, k));
-    };
-
-    // NOTE: the history chains of order k can be emitted in several parts: the first one at the end of
-    // order k - 1 (it overlaps the glue exchange), the others at the beginning of the cluster phase of
-    // order k. Measured on gfx950 (outer-SS, 1 048 576 systems): 18.11 ms per launch for 1, 2 and 3 parts
-    // - the chains only touch registers, so the compiler's scheduler already moves them across the
-    // compiler-only HY_WSYNC barrier. Hence the default of a single part.
-    const std::uint32_t n_parts = 1;
-    std::vector<std::uint32_t> t0_ids;
-    for (const auto u : t0) {
+// The state of the order programs. Reads the variant, opts and the plan; leaves t0_ids, the (empty) coefficient histories
+// of the pair programs, the padding counts and switches of the one-lane program, and ext_const.
+void cluster2_gen::init_order_programs()
+{
+    for (const auto u : t0()) {
         t0_ids.push_back(u - n_eq);
     }
-
-    // Explicit overlap of the LDS exchange latency (the workgroup runs one wavefront per SIMD, nobody else
-    // hides it): in both exchange regions of an order the LDS reads are issued first, then - fenced by
-    // scheduling barriers - a chunk of history-chain FMAs which do not depend on them, then the dependent
-    // computation. The chunks are (ssa_emitter::emit_partials_sel): in the cluster region of order k the second
-    // half of the early terms of order k + 1; in the last glue region of order k the late terms of order k + 1
-    // and the first half of the early terms of order k + 2.
-    const bool overlap = true, fence2 = true;
-    const auto sched_fence = [&]() { os << "__builtin_amdgcn_sched_barrier(0);\n"; };
-    using psel = ssa_emitter::part_sel;
-
-    // ---- Lane-pair cluster program ----
-    // Coefficient histories of a lane (SSA names by order), role A | role B:
-    //   aS: d_0 | d_2          aP: d_1 | b = sum of squares          aR: sa = (scaled) pow, both lanes
-    //   aRp: d_1 (a copy) | -(alpha + 1) j sa_j
-    // Convolution chains of order k (same FMA stream on both lanes), history part = indices 1 .. k-1:
-    //   c1 = sum aP[k-j] aR[j]   (A: d_1 * sa,  B: S1 = sum b[k-j] sa[j] of the pow recurrence)
-    //   c2 = sum aP[k-j] aRp[j]  (A: the order-k coefficient of d_1^2, B: S2 = sum b[k-j] j sa[j])
-    //   c3 = sum aS[k-j] aR[j]   (d_0 * sa | d_2 * sa)
-    //   c4 = sum_{j <= jmax} aS[k-j] aS[j] (+ the middle square): d_0^2 | d_2^2
-    // The pow recurrence (src/math/pow.cpp:517-549) k b_0 a_k = sum_{j<k} (k alpha - j (alpha + 1)) b_{k-j} a_j is linear
-    // in a: it is run directly on sa = c a, as alpha k S1 - (alpha + 1) S2.
-    // Per order the two lanes exchange (DPP quad_perm [1,0,3,2], no LDS): the partial sums of squares, then sa_k.
-    std::vector<std::string> aP(order + 1u), aR(order + 1u), aRp(order + 1u), aS(order + 1u);
-    std::string hc1, hc2, hc3, hc4, hmid;
-    const bool has_rx = pp.rx[0] >= 0;
-    std::string rb1;   // 1 / b_0 (lane B)
+    aP.assign(order + 1u, {}), aR.assign(order + 1u, {}), aRp.assign(order + 1u, {}), aS.assign(order + 1u, {});
+    has_rx = pp.rx[0] >= 0;
     // Normalised pow recurrence (default): lane B keeps b_k / b_0 (k >= 1) instead of b_k, one multiplication by
     // RN(1 / b_0) folded into the FMA which forms the lane's aP[k]; the recurrence k b_0 a_k = sum(...) then needs no
     // division: a_k = alpha S1 - (alpha + 1) S2 / k on the normalised sums. The new coefficient goes to both lanes of
     // the pair with one DPP broadcast from the odd lane. kw::exact_division: the quotient by b_0 with a Markstein
     // correction, within 1.5 ulp of the reference's single division.
-    const bool pow_norm = !opts.exact_division;
-    std::string ap0x2; // 2 aP[0]
-    const auto emit_pair_reads = [&](std::uint32_t k) {
-        const auto rd = [&](std::size_t t) { return e.def(slabk(k, utname(t))); };
-        return std::vector<std::string>{rd(pt.s0), rd(pt.s1), rd(pt.p0), rd(pt.p1)};
-    };
-    const auto emit_pair_compute = [&](std::uint32_t k, const std::vector<std::string> &rdv) {
-        using emit_detail::ssa_emitter;
-        const auto &es0 = rdv[0], &es1 = rdv[1], &ep0 = rdv[2], &ep1 = rdv[3];
-        aS[k] = e.def(es0 + " - " + es1);
-        const auto dP = e.def(ep0 + " - " + ep1);
-        std::string sqS, sqy;
-        if (k == 0u) {
-            sqS = e.def(ssa_emitter::mul(aS[0], aS[0]));
-            sqy = e.def(ssa_emitter::mul(dP, dP));
-        } else {
-            const auto acc4 = e.chain(hc4, aS[k], aS[0]);
-            sqS = (k % 2u == 0u) ? e.def("__builtin_fma(2.0, " + acc4 + ", " + hmid + ")") : e.def(acc4 + " + " + acc4);
-            // (A: 2 d_1[k] d_1[0] on top of the symmetric history sum; ap0x2 = 2 aP[0].)
-            sqy = e.chain(hc2, dP, ap0x2);
-        }
-        // NOTE: role-dependent values are formed arithmetically with the lane constants fA / fB (1.0 on the lanes of
-        // the role, 0.0 on the others) instead of selects (two v_cndmask per double): lane B reads the same slot twice
-        // for the second difference, so that its dP is an exact zero.
-        const auto mine = e.def("__builtin_fma(fA, " + sqy + ", " + sqS + ")");
-        const auto oth = e.def("hy_swap1(" + mine + ")");
-        const auto r2 = e.def(mine + " + " + oth);
-        aP[k] = e.def("__builtin_fma(" + std::string((pow_norm && k >= 1u) ? "rb1n" : "fB") + ", " + r2 + ", " + dP + ")");
-        std::string c1a;
-        if (k == 0u) {
-            // NOTE: the sum of squares is the same on both lanes: each of them evaluates the pow itself.
-            const auto a0 = e.pow_eval(r2, pp.ex);
-            aR[0] = pp.sc >= 0 ? e.def(ssa_emitter::mul(dtname(pt.csc), a0)) : a0;
-            // (Zero on lane A: its quotient below is then an exact zero and sa_k = own + partner's.)
-            rb1 = e.def("isB ? (1.0 / " + aP[0] + ") : 0.0");
-            if (pow_norm) {
-                os << "const double rb1n = " << rb1 << ";\n";
-            }
-            ap0x2 = e.def(aP[0] + " + " + aP[0]);
-        } else {
-            c1a = e.chain(hc1, aP[k], aR[0]);
-            // NOTE: lane B keeps -(alpha + 1) j sa_j in aRp, so that its c2 chain is -(alpha + 1) S2 right away.
-            std::string num;
-            if (pow_norm) {
-                const auto m = e.def(ssa_emitter::mul(fp_literal(pp.ex), c1a));
-                const auto sab = hc2.empty() ? m
-                                             : e.def("__builtin_fma(" + hc2 + ", " + fp_literal(1. / static_cast<double>(k)) + ", " + m + ")");
-                // (Masked to the B lanes: the value doubles as the operand of aRp below.)
-                const auto t = e.def(ssa_emitter::mul("fB", sab));
-                aR[k] = e.def("hy_dpp<0xF5>(" + t + ")");
-                if (k + 2u <= order) {
-                    aRp[k] = e.def("__builtin_fma(" + fp_literal(-(pp.ex + 1.) * static_cast<double>(k)) + ", " + t + ", " + dP + ")");
-                }
-            } else {
-            if (hc2.empty()) {
-                num = e.def(ssa_emitter::mul(fp_literal(pp.ex * static_cast<double>(k)), c1a));
-            } else {
-                num = e.def(fp_literal(pp.ex * static_cast<double>(k)) + " * " + c1a + " + " + hc2);
-            }
-            // Division by k * b_0 (src/math/pow.cpp:546-549) without a division sequence on the critical path:
-            // n = num * RN(1 / k), q0 = n * r with r = RN(1 / b_0); residual rem = n - b_0 * q0 (exact, FMA);
-            // q = q0 + rem * r (Markstein: the correctly-rounded n / b_0 unless r is off by more than an ulp in a
-            // halfway case; n itself carries the rounding of the scaling by 1 / k, so q is within 1.5 ulp of the
-            // quotient num / (k b_0) the reference rounds once).
-            const auto nk = (k == 1u) ? num : e.def(ssa_emitter::mul(num, fp_literal(1. / static_cast<double>(k))));
-            const auto q0 = e.def(ssa_emitter::mul(nk, rb1));
-            const auto rem = e.def("__builtin_fma(-" + aP[0] + ", " + q0 + ", " + nk + ")");
-            const auto sab = e.def("__builtin_fma(" + rem + ", " + rb1 + ", " + q0 + ")");
-            const auto sao = e.def("hy_swap1(" + sab + ")");
-            aR[k] = e.def(sab + " + " + sao);
-            }
-        }
-        if (!pow_norm && k >= 1u && k + 2u <= order) {
-            const auto t = e.def(ssa_emitter::mul("fB", aR[k]));
-            aRp[k] = e.def("__builtin_fma(" + fp_literal(-(pp.ex + 1.) * static_cast<double>(k)) + ", " + t + ", " + dP + ")");
-        }
-        std::string prS, prP;
-        if (k == 0u) {
-            prS = e.def(ssa_emitter::mul(aS[0], aR[0]));
-            prP = e.def(ssa_emitter::mul(aP[0], aR[0]));
-        } else {
-            prS = e.chain(e.chain(hc3, aS[k], aR[0]), aS[0], aR[k]);
-            prP = e.chain(c1a, aP[0], aR[k]);
-        }
-        os << slabk(k, utname(pt.os)) << " = " << prS << ";\n";
-        os << slabk(k, utname(pt.op)) << " = " << prP << ";\n";
-        if (has_rx && !fuse_rx) {
-            const auto rS = e.def(ssa_emitter::mul(dtname(pt.crs), prS));
-            const auto rP = e.def(ssa_emitter::mul(dtname(pt.crp), prP));
-            os << slabk(k, utname(pt.rs)) << " = " << rS << ";\n";
-            os << slabk(k, utname(pt.rp)) << " = " << rP << ";\n";
-        }
-        // History parts of order K = k + 1 (indices 1 .. k), the four chains interleaved term by term.
-        hc1.clear();
-        hc2.clear();
-        hc3.clear();
-        hc4.clear();
-        hmid.clear();
-        const auto K = k + 1u;
-        if (K < order && K >= 2u) {
-            const auto jmax = (K % 2u == 1u) ? (K - 1u) / 2u : (K - 2u) / 2u;
-            for (std::uint32_t j = 1; j < K; ++j) {
-                hc1 = e.chain(hc1, aP[K - j], aR[j]);
-                hc2 = e.chain(hc2, aP[K - j], aRp[j]);
-                hc3 = e.chain(hc3, aS[K - j], aR[j]);
-                if (j <= jmax) {
-                    hc4 = e.chain(hc4, aS[K - j], aS[j]);
-                }
-            }
-            if (K % 2u == 0u) {
-                hmid = e.def(ssa_emitter::mul(aS[K / 2u], aS[K / 2u]));
-            }
-        }
-    };
-
-    const auto emit_pair_order = [&](std::uint32_t k) { emit_pair_compute(k, emit_pair_reads(k)); };
-
-    // ---- One-lane pair program ("v5") ----
-    // Histories of a lane (SSA names by order): sD[i] = d_i (i = 0, 1, 2), sB = b_k / b_0 (k >= 1; b = sum of squares),
-    // sA = sa = (scaled) pow. Chains of order k, history part = indices 1 .. k-1:
-    //   q_i = sum_{j <= jmax} d_i[k-j] d_i[j]                      (half of the symmetric sum of d_i^2, see below)
-    //   T   = sum_j sB[k-j] sA[j]                                  (S1 of the pow recurrence)
-    //   U   = sum of the suffix sums of T's terms = sum_j j sB[k-j] sA[j]   (S2; terms taken in the order j = k-1 .. 1)
-    //   c_i = sum_j d_i[k-j] sA[j]                                 (d_i * sa)
-    // b_k = 2 (q_0 + q_1 + q_2) (+ the middle squares at even orders): the factor 2 is exact, so the HALF sum
-    // bh = (q_0 + 0.5 mid_0) + ... is formed instead and the doubling is folded into the normalisation constant
-    // rb2 = 2 RN(1 / b_0). a_k = alpha (T + sB[k] a_0) - ((alpha + 1) / k) U (src/math/pow.cpp:517-549 divided by k b_0).
-    std::vector<std::string> sD[3], sB(order + 1u), sA(order + 1u);
+    pow_norm = !opts.exact_division;
+    sB.assign(order + 1u, {}), sA.assign(order + 1u, {});
     for (auto &v : sD) {
         v.resize(order + 1u);
     }
-    std::string hq[3], hm[3], hcx[3], hT, hU, pow_pre;
-    // (Tried in round 5 and removed: the stores of a round spread over the convolution chains which follow it instead of a
-    // burst at the end of the dependent section - the eight wavefronts of a CU queue on one LDS store path -: -1.6 %,
-    // profiles/r05_ab_spread_stores.log; the early chain terms of order k + 1 interleaved with the dependent operations of
-    // round k: -1 %, profiles/r05_ab_interleaved_early_terms.log.)
-    const auto emit_store = [&](const std::string &stmt) { os << stmt; };
     // Sensitivity experiment (profiles/experiments/sensitivity.py): HEYOKA_AMD_V5_PAD = "chain:dep:st:ld:salu" adds that many
     // dummy instructions of each kind to every order - independent FMAs in the chain section, dependent FMAs, LDS stores
     // and LDS reads in the dependent section, scalar no-ops - without touching the results: the slope of the step time
@@ -1947,248 +1118,38 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // (A sixth field: that many per-lane doubles kept live through the step, each used by one dependent FMA per order - what
     // per-lane coefficients of the acceleration sums would cost in registers; "norx" among HEYOKA_AMD_V5_OPTS drops the
     // reaction products and their stores - WRONG results, timing only: what fusing them into the sums could gain.)
-    unsigned pad_chain = 0, pad_dep = 0, pad_st = 0, pad_ld = 0, pad_salu = 0, pad_regs = 0;
     if (!opts.dev.v5_pad.empty()) {
         std::sscanf(opts.dev.v5_pad.c_str(), "%u:%u:%u:%u:%u:%u", &pad_chain, &pad_dep, &pad_st, &pad_ld, &pad_salu, &pad_regs);
     }
-    const bool any_pad = (pad_chain | pad_dep | pad_st | pad_ld | pad_salu | pad_regs) != 0u;
-    const bool exp_norx = v5_flag("norx");
+    any_pad = (pad_chain | pad_dep | pad_st | pad_ld | pad_salu | pad_regs) != 0u;
+    exp_norx = v5_flag("norx");
     // One accumulator for the half sum of squares bh_k = sum_i (sum_j d_i[k-j] d_i[j] + 1/2 d_i[k/2]^2): the three chains
     // of the coordinates run into each other - two additions per order and two multiply-adds per even order less, two
     // accumulators less. (The reference adds the three squares pairwise, src/detail/sum_sq.cpp:120-245: same terms, other
     // rounding order - inside the stated tolerances like the suffix sums of the pow recurrence.)
-    const bool merged_sq = !v5_flag("nomsq");
-    //   nosc      the selector's logarithm / exponential with literal polynomial constants (hy_sel_log(), exp()).
-    const bool sel_scalar = one_lane && !v5_flag("nosc");
+    merged_sq = !v5_flag("nomsq");
+    sel_scalar = one_lane && !v5_flag("nosc");
     // Issue priority (s_setprio): raised between the LDS exchange and the end of the finishing operations of a round - the
     // dependent chain which decides how soon the next exchange can start - and lowered for the convolution chains, so
     // that the wavefront which is in its critical section wins the VALU over the one streaming FMAs.
     // Measured (outer Solar System, 1 048 576 systems, A/B harness): 7.02e8 -> 7.15e8 system-steps/s; on by default,
     // HEYOKA_AMD_V5_PRIO=0 switches it off, =2 also keeps the serial tail of the step at the high priority.
-    const int prio_mode = opts.dev.v5_prio;
-    const bool prio_switch = prio_mode != 0;
-    const auto emit_single_reads = [&](std::uint32_t k) {
-        std::vector<std::string> r(6);
-        if (vexch) {
-            // The velocity coefficients of order k - 1 of the two bodies (row k - 1 of the jets; order 0: their current
-            // positions, behind the rows).
-            const auto row = k == 0u ? jet_rows_doubles : static_cast<std::uint64_t>(k - 1u) * spw * n_colp;
-            for (std::uint32_t i = 0; i < 3u; ++i) {
-                for (std::uint32_t sd = 0; sd < 2u; ++sd) {
-                    r[2u * i + sd] = e.def("jetq[" + utname(st1.s[i][sd]) + " + " + std::to_string(row) + "u]");
-                }
-            }
-            return r;
-        }
-        if (wide_rd) {
-            // (x, y) of the two bodies with one ds_read_b128 each, then the two z.
-            for (std::uint32_t sd = 0; sd < 2u; ++sd) {
-                const auto w = wide_read(utname(st1.s[0][sd]));
-                r[0u + sd] = w + ".x";
-                r[2u + sd] = w + ".y";
-            }
-            for (std::uint32_t sd = 0; sd < 2u; ++sd) {
-                r[4u + sd] = e.def(slabk(k, utname(st1.s[2][sd])));
-            }
-            return r;
-        }
-        for (std::uint32_t i = 0; i < 3u; ++i) {
-            r[2u * i] = e.def(slabk(k, utname(st1.s[i][0])));
-            r[2u * i + 1u] = e.def(slabk(k, utname(st1.s[i][1])));
-        }
-        return r;
-    };
-    const auto emit_single_compute = [&](std::uint32_t k, const std::vector<std::string> &rdv) {
-        using emit_detail::ssa_emitter;
-        for (std::uint32_t i = 0; i < 3u; ++i) {
-            sD[i][k] = e.def(rdv[2u * i] + " - " + rdv[2u * i + 1u]);
-            if (vexch && k >= 2u) {
-                // (d^[k] = (v_a^[k-1] - v_b^[k-1]) RN(1 / k).)
-                sD[i][k] = e.def(ssa_emitter::mul(sD[i][k], fp_literal(1. / static_cast<double>(k))));
-            }
-        }
-        std::string pr[3];
-        if (k == 0u) {
-            // (Products rounded one by one, summed pairwise like the reference's sum_sq: src/detail/sum_sq.cpp:120-245.)
-            std::string sq[3];
-            for (std::uint32_t i = 0; i < 3u; ++i) {
-                sq[i] = e.def(ssa_emitter::mul(sD[i][0], sD[i][0]));
-            }
-            const auto s01 = e.def(sq[0] + " + " + sq[1]);
-            const auto r2 = e.def(s01 + " + " + sq[2]);
-            sB[0] = r2;
-            const auto a0 = e.pow_eval(r2, pp.ex);
-            sA[0] = pp.sc >= 0 ? e.def(ssa_emitter::mul(dtname(st1.csc), a0)) : a0;
-            const auto rb = e.def("1.0 / " + r2);
-            os << "const double rb2 = " << rb << " + " << rb << ";\n";
-            os << "const double arbA = " << fp_literal(pp.ex) << " * (rb2 * " << sA[0] << ");\n";
-            for (std::uint32_t i = 0; i < 3u; ++i) {
-                pr[i] = e.def(ssa_emitter::mul(sD[i][0], sA[0]));
-            }
-        } else {
-            // The dependent chain from the exchange to the stores decides how soon the next round can start, so
-            // everything which does not need an order-k input was folded into the history accumulators at the end of the
-            // previous round (the middle squares into hq, alpha T - ((alpha + 1) / k) U into pow_pre): what is left is
-            // sub -> fma -> add -> add -> fma (sa_k) -> fma (products) -> mul (reactions).
-            std::string bh;
-            if (merged_sq) {
-                bh = hq[0];
-                for (std::uint32_t i = 0; i < 3u; ++i) {
-                    bh = e.chain(bh, sD[i][k], sD[i][0]);
-                }
-            } else {
-                std::string q[3];
-                for (std::uint32_t i = 0; i < 3u; ++i) {
-                    q[i] = e.chain(hq[i], sD[i][k], sD[i][0]);
-                }
-                const auto q01 = e.def(q[0] + " + " + q[1]);
-                bh = e.def(q01 + " + " + q[2]);
-            }
-            // sa_k = alpha (T + (b_k / b_0) sa_0) - ((alpha + 1) / k) U with b_k / b_0 = rb2 bh: alpha rb2 sa_0 is a constant
-            // of the step (arbA).
-            sA[k] = pow_pre.empty() ? e.def(ssa_emitter::mul(bh, "arbA")) : e.def("__builtin_fma(" + bh + ", arbA, " + pow_pre + ")");
-            sB[k] = e.def(ssa_emitter::mul("rb2", bh));
-            for (std::uint32_t i = 0; i < 3u; ++i) {
-                pr[i] = e.chain(e.chain(hcx[i], sD[i][k], sA[0]), sD[i][0], sA[k]);
-            }
-        }
-        for (std::uint32_t i = 0; i < 3u; ++i) {
-            emit_store(slabk(k, utname(st1.o[i])) + " = " + pr[i] + ";\n");
-        }
-        for (std::uint32_t i = 0; pp.rx[0] >= 0 && !fuse_rx && i < 3u && !exp_norx; ++i) {
-            // (The reaction on the second body of the pair: c * (d_i * sa), src/model/nbody.cpp:113-130.)
-            const auto rxv = e.def(ssa_emitter::mul("crs_r", pr[i]));
-            emit_store(slabk(k, utname(st1.r[i])) + " = " + rxv + ";\n");
-        }
-        if (any_pad && k >= 1u) {
-            for (unsigned i = 0; i < pad_dep; ++i) {
-                os << "asm volatile(\"v_fma_f64 %0, %0, %0, %0\" : \"+v\"(hy_pad0));\n";
-            }
-            for (unsigned i = 0; i < pad_regs; ++i) {
-                os << "asm volatile(\"v_fma_f64 %0, %1, %0, %0\" : \"+v\"(hy_pad0) : \"v\"(hy_rp" << i << "));\n";
-            }
-            // (Written-out LDS stores of the first product to its own slot once more: same value, same address. The
-            // compiler's lgkmcnt bookkeeping stays conservative: LDS operations complete in order.)
-            for (unsigned i = 0; i < pad_st % 100u; ++i) {
-                os << "asm volatile(\"ds_write_b64 %0, %1\" ::\"v\"((unsigned)(unsigned long long)&" << slabk(k, utname(st1.o[0]))
-                   << "), \"v\"(" << pr[0] << ") : \"memory\");\n";
-            }
-            // (pad_st >= 100: 16-byte stores - the first product and its neighbour in the array written back as a pair.)
-            for (unsigned i = 0; i < pad_st / 100u; ++i) {
-                os << "{\nhy_d2 hy_pv;\nhy_pv.x = " << pr[0] << ";\nhy_pv.y = " << pr[0] << ";\n"
-                   << "asm volatile(\"ds_write_b128 %0, %1\" ::\"v\"((unsigned)(unsigned long long)(slab + (" << dummy_base
-                   << "u & ~1u))), \"v\"(hy_pv) : \"memory\");\n}\n";
-            }
-            // (LDS reads of the velocity coefficients of the previous order once more, summed into a dummy: the reads of
-            // this round cannot be shared with them - the wave barrier between the rounds is a memory clobber.)
-            for (unsigned i = 0; vexch && k >= 2u && i < pad_ld && i < 6u; ++i) {
-                os << "hy_pad4 = hy_pad4 + jetq[" << utname(st1.s[i % 3u][i / 3u]) << " + "
-                   << static_cast<std::uint64_t>(k - 2u) * spw * n_colp << "u];\n";
-            }
-            for (unsigned i = 0; i < pad_salu; ++i) {
-                os << "asm volatile(\"s_nop 0\");\n";
-            }
-        }
-        if (prio_switch) {
-            // (End of the latency-critical part of the round: the chains below are bulk work.)
-            os << "__builtin_amdgcn_s_setprio(0);\n";
-        }
-        if (any_pad && k >= 1u) {
-            for (unsigned i = 0; i < pad_chain; ++i) {
-                os << "asm volatile(\"v_fma_f64 %0, %0, %0, %0\" : \"+v\"(hy_pad" << (1u + i % 4u) << "));\n";
-            }
-        }
-    };
-    const auto emit_single_history = [&](std::uint32_t k) {
-        using emit_detail::ssa_emitter;
-        // History parts of order K = k + 1 (terms without an order-K operand) and the T / U chains of the pow recurrence,
-        // whose first term is the newest one.
-        for (std::uint32_t i = 0; i < 3u; ++i) {
-            hq[i].clear();
-            hm[i].clear();
-            hcx[i].clear();
-        }
-        hT.clear();
-        hU.clear();
-        const auto K = k + 1u;
-        if (K < order && K >= 2u) {
-            const auto jmax = (K % 2u == 1u) ? (K - 1u) / 2u : (K - 2u) / 2u;
-            for (std::uint32_t j = 1; j < K; ++j) {
-                // (T / U take their terms in the order j = K-1 .. 1: the first term enters U K-1 times, the last one once.)
-                const auto jd = K - j;
-                hT = e.chain(hT, sB[K - jd], sA[jd]);
-                hU = hU.empty() ? hT : e.def(hU + " + " + hT);
-                for (std::uint32_t i = 0; i < 3u; ++i) {
-                    hcx[i] = e.chain(hcx[i], sD[i][K - j], sA[j]);
-                    if (j <= jmax) {
-                        auto &acc = hq[merged_sq ? 0u : i];
-                        acc = e.chain(acc, sD[i][K - j], sD[i][j]);
-                    }
-                }
-            }
-            if (K % 2u == 0u) {
-                for (std::uint32_t i = 0; i < 3u; ++i) {
-                    if (merged_sq) {
-                        // (One running sum of the three middle squares.)
-                        hm[0] = e.chain(i == 0u ? std::string{} : hm[0], sD[i][K / 2u], sD[i][K / 2u]);
-                    } else {
-                        hm[i] = e.def(ssa_emitter::mul(sD[i][K / 2u], sD[i][K / 2u]));
-                    }
-                }
-            }
-            // Off the critical path of round K: the middle squares join the half sums, the two sums of the pow
-            // recurrence are combined.
-            if (K % 2u == 0u) {
-                for (std::uint32_t i = 0; i < (merged_sq ? 1u : 3u); ++i) {
-                    hq[i] = hq[i].empty() ? e.def(ssa_emitter::mul("0.5", hm[i]))
-                                          : e.def("__builtin_fma(0.5, " + hm[i] + ", " + hq[i] + ")");
-                }
-            }
-            const auto t1 = e.def(ssa_emitter::mul(fp_literal(-(pp.ex + 1.) / static_cast<double>(K)), hU));
-            pow_pre = e.def("__builtin_fma(" + fp_literal(pp.ex) + ", " + hT + ", " + t1 + ")");
-        } else {
-            pow_pre.clear();
-        }
-    };
+    prio_mode = opts.dev.v5_prio;
+    prio_switch = prio_mode != 0;
     // External inputs which are constant u variables in EVERY cluster (isomorphic clusters may pair a constant with a
     // variable: the heliocentric alias x_i - 0 and the pair difference x_j - x_i of model::np1body).
-    std::vector<char> ext_const(n_ext, 1);
+    ext_const.assign(n_ext, 1);
     for (std::uint32_t x = 0; x < n_ext; ++x) {
         for (std::size_t c = 0; c < nc; ++c) {
             ext_const[x] = (ext_const[x] != 0 && cu[pl.ext_u[c][x]] != 0) ? 1 : 0;
         }
     }
-    const auto emit_cluster = [&](std::uint32_t k) {
-        if (pair_split) {
-            emit_pair_order(k);
-            return;
-        }
-        for (std::uint32_t part = 1; part < n_parts; ++part) {
-            e.emit_partials(t0_ids, k, part, n_parts);
-        }
-        for (std::uint32_t x = 0; x < n_ext; ++x) {
-            if (ext_const[x] != 0 && k > 0u) {
-                // A constant input of every cluster (e.g. -par[i]): read once, at order 0.
-                e.val(pl.ext_u[0][x], k) = "0.0";
-                continue;
-            }
-            e.val(pl.ext_u[0][x], k) = e.def(slabk(k, utname(ext_tbl[x])));
-        }
-        if (overlap) {
-            sched_fence();
-            e.emit_partials_sel(t0_ids, k + 1u, psel::early_b);
-            if (fence2) {
-                sched_fence();
-            }
-        }
-        for (const auto u : t0) {
-            e.node_finish(u - n_eq, k);
-        }
-        for (std::uint32_t x = 0; x < n_out; ++x) {
-            os << slabk(k, utname(out_tbl[x])) << " = " << e.val(t0[pl.out_pos[x]], k) << ";\n";
-        }
-    };
+}
 
+// Reads everything before it; leaves the statements of one step in body (and os empty), the SSA names of the coefficients
+// in the owner slots (publish_sv) and in the histories, and e.n_stmt.
+void cluster2_gen::emit_step_body()
+{
     // ===================== step body =====================
     os << "double m0 = 0.0, mo = 0.0, mom1 = 0.0;\n";
     if (frx_regs) {
@@ -2208,14 +1169,10 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
             os << "double hy_rp" << i << " = lds_fac[(threadIdx.x + " << i << "u) % 40u];\n";
         }
     }
-    for (auto &rg : rounds) {
-        for (auto &gr : rg) {
-            for (auto &ow : gr.owners) {
-                os << "const double xs" << ow.col << " = " << row0_r(ow) << ";\n";
-                publish_sv(ow, 0, "xs" + std::to_string(ow.col));
-            }
-        }
-    }
+    for_each_owner([&](auto &, auto &ow) {
+        os << "const double xs" << ow.col << " = " << row0_r(ow) << ";\n";
+        publish_sv(ow, 0, "xs" + std::to_string(ow.col));
+    });
     // (One-lane pair kernel, single-buffered slab: the order-1 coefficients go to the slab once the order-0 ones have
     // been read, i.e. after the reads of round 0.)
     std::vector<std::tuple<owner_slot *, std::uint32_t, std::string>> deferred_pub;
@@ -2335,10 +1292,15 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     if (one_lane && !opts.dev.v5_pad.empty()) {
         os << "asm volatile(\"\" ::\"v\"(hy_pad4));\n";
     }
-    const auto body = os.str();
+    body = os.str();
     os.str("");
     os.clear();
+}
 
+// Reads the variant, the tables, rounds and the jet layout; leaves the defines, the prelude, the __device__ helpers of the
+// variant and the __constant__ tables in src, and n_tc_rows (refusals: overflows of the table entries).
+void cluster2_gen::text_helpers_and_constant_tables()
+{
     // NOTE: a local search over slot permutations minimising the LDS bank conflicts of the gather-type reads
     // was tried and removed: it lowered SQ_LDS_BANK_CONFLICT by 9 % with no change in kernel time. A
     // microbenchmark on gfx950 shows why: a single wavefront issues one ds_read_b64 per 6.6 clk whatever the
@@ -2346,7 +1308,6 @@ emitted_module emit_cluster_v2_impl(const taylor_program &p, const emit_options 
     // (34.6 clk); the cost of the LDS traffic here is the issue slots of its ~620 instructions per step.
 
     // ===================== module text =====================
-    std::ostringstream src;
     src << "#define SPW " << spw << "u\n#define HY_WPB " << wpb << "u\n";
     src << "#define HY_M4 " << (m4 ? 1 : 0) << "\n";
     // (The stepper with events is a specialisation of its own and always runs in mode 4: a compile-time constant there - the
@@ -2491,7 +1452,7 @@ __device__ __forceinline__ double hy_swap1(double x)
         for (const auto x : v) {
             if (x > 65535u) {
                 why_not = "slot / variable index overflow in the lane tables";
-                return ret;
+                return;
             }
             src << x << ",";
         }
@@ -2500,16 +1461,12 @@ __device__ __forceinline__ double hy_swap1(double x)
     {
         // Jet column of every state variable.
         std::vector<std::uint32_t> col_of(n_eq, 0);
-        for (const auto &rg : rounds) {
-            for (const auto &gr : rg) {
-                for (const auto &ow : gr.owners) {
-                    const auto &vv = utbl[ow.var_tbl];
-                    for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
-                        col_of[vv[l2]] = ow.cbase + l2;
-                    }
-                }
+        for_each_owner([&](auto &, auto &ow) {
+            const auto &vv = utbl[ow.var_tbl];
+            for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
+                col_of[vv[l2]] = ow.cbase + l2;
             }
-        }
+        });
         if (m4) {
             // Source table of the cooperative store of the Taylor coefficients (mode 4): per stored row its index in a.tc
             // (variable * (order + 1) + k), the offset of its value for the first system of a wavefront inside the jets of
@@ -2521,24 +1478,20 @@ __device__ __forceinline__ double hy_swap1(double x)
             std::vector<tc_entry> tc_src;
             if (one_lane) {
                 // (Velocity-type jets [row][owner slot][system][lane]; current values of the derived variables behind them.)
-                for (const auto &rg : rounds) {
-                    for (const auto &gr : rg) {
-                        for (const auto &ow : gr.owners) {
-                            const auto &vv = utbl[ow.var_tbl];
-                            for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
-                                const std::uint64_t var = vv[l2];
-                                if (ow.derived) {
-                                    tc_src.push_back({var * (order + 1u), jet_rows_doubles + jet_off(ow) + l2, jet_sys(ow)});
-                                } else {
-                                    for (std::uint32_t k = 0; k <= order; ++k) {
-                                        tc_src.push_back({var * (order + 1u) + k,
-                                                          static_cast<std::uint64_t>(k) * spw * n_colp + jet_off(ow) + l2, jet_sys(ow)});
-                                    }
-                                }
+                for_each_owner([&](auto &, auto &ow) {
+                    const auto &vv = utbl[ow.var_tbl];
+                    for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
+                        const std::uint64_t var = vv[l2];
+                        if (ow.derived) {
+                            tc_src.push_back({var * (order + 1u), jet_rows_doubles + jet_off(ow) + l2, jet_sys(ow)});
+                        } else {
+                            for (std::uint32_t k = 0; k <= order; ++k) {
+                                tc_src.push_back({var * (order + 1u) + k,
+                                                  static_cast<std::uint64_t>(k) * spw * n_colp + jet_off(ow) + l2, jet_sys(ow)});
                             }
                         }
                     }
-                }
+                });
             } else {
                 for (std::uint32_t var = 0; var < n_eq; ++var) {
                     const auto &sd = p.sv_defs[var];
@@ -2554,7 +1507,7 @@ __device__ __forceinline__ double hy_swap1(double x)
             for (const auto &t : tc_src) {
                 if (t.row >= (1ull << 20) || t.off >= (1ull << 20) || t.stride >= (1ull << 20)) {
                     why_not = "mode 4: index overflow in the source table of the Taylor coefficients";
-                    return ret;
+                    return;
                 }
                 src << (t.row | (t.off << 20) | (t.stride << 40)) << "ull,";
             }
@@ -2578,7 +1531,11 @@ __device__ __forceinline__ double hy_swap1(double x)
         }
     }
     src << "};\n";
+}
 
+// Reads the layout and the tables; leaves the kernel head: LDS arrays, lane tables in registers, jet pointers.
+void cluster2_gen::text_kernel_prologue()
+{
     src << "extern \"C\" __global__ void __launch_bounds__(" << bs << ") hy_taylor(const hy_kargs a)\n{\n";
     src << "__shared__ " << (wide_rd ? "__attribute__((aligned(16))) " : "") << "double lds_slab["
         << static_cast<std::uint64_t>(wpb) * spw * slab_stride << "];\n";
@@ -2596,12 +1553,11 @@ __device__ __forceinline__ double hy_swap1(double x)
             src << "__shared__ double lds_bk[" << wpb * spw * 16u << "];\ndouble *const bk = lds_bk + (wib * " << spw << "u + q) * 16u;\n";
         }
     }
-    const bool vexch_decl = vexch;
     src << "const u64 gwave = (u64)blockIdx.x * " << wpb << "u + wib;\n";
     if (jet_lds) {
         src << "__shared__ double lds_jet[" << wpb * jet_doubles_per_wave << "];\n";
         src << "double *const jetw = lds_jet + wib * " << jet_doubles_per_wave << "u;\n";
-        if (vexch_decl) {
+        if (vexch) {
             // (The rows of the system of this lane: [system][column].)
             src << "const double *const jetq = jetw + q * " << n_col << "u;\n";
         }
@@ -2649,50 +1605,47 @@ __device__ __forceinline__ double hy_swap1(double x)
     for (std::uint32_t x = 0; !pairk && x < n_cst; ++x) {
         src << "const double ccst" << x << " = dt" << cst_tbl[x] << ";\n";
     }
-    for (const auto &rg : rounds) {
-        for (const auto &gr : rg) {
-            for (const auto &ow : gr.owners) {
-                src << "const bool ovalid" << ow.col << " = l < " << gr.n_valid << "u;\n";
-                if (ow.derived) {
-                    // (Current values of the derived variables: after the jet rows of the wavefront. One pointer for
-                    // reading and writing: the idle lanes of a partially filled slot replicate the work of lane 0 bit by
-                    // bit and store the same values to the same entry.)
-                    src << "double *const x0c" << ow.col << " = jetw + " << jet_rows_doubles + jet_off(ow) << "u + q * " << jet_sys(ow)
-                        << "u + (ovalid" << ow.col << " ? l : 0u);\n";
-                    src << "const double *const x0r" << ow.col << " = x0c" << ow.col << ";\n";
-                    continue;
-                }
-                if (one_lane) {
-                    src << "double *const jc" << ow.col << " = jetw + " << jet_off(ow) << "u + q * " << jet_sys(ow) << "u + (ovalid"
-                        << ow.col << " ? l : 0u);\n";
-                    src << "const double *const jr" << ow.col << " = jc" << ow.col << ";\n";
-                    continue;
-                }
-                src << "double *const jc" << ow.col << " = jetw + q * " << n_colp << "u + (ovalid" << ow.col << " ? "
-                    << ow.cbase << "u + l : " << n_col << "u);\n";
-                // The current state (order-0 row) is read from the column of the replicated variable by the idle lanes.
-                src << "const double *const jr" << ow.col << " = jetw + q * " << n_colp << "u + " << ow.cbase
-                    << "u + (ovalid" << ow.col << " ? l : 0u);\n";
-            }
+    for_each_owner([&](auto &gr, auto &ow) {
+        src << "const bool ovalid" << ow.col << " = l < " << gr.n_valid << "u;\n";
+        if (ow.derived) {
+            // (Current values of the derived variables: after the jet rows of the wavefront. One pointer for
+            // reading and writing: the idle lanes of a partially filled slot replicate the work of lane 0 bit by
+            // bit and store the same values to the same entry.)
+            src << "double *const x0c" << ow.col << " = jetw + " << jet_rows_doubles + jet_off(ow) << "u + q * " << jet_sys(ow)
+                << "u + (ovalid" << ow.col << " ? l : 0u);\n";
+            src << "const double *const x0r" << ow.col << " = x0c" << ow.col << ";\n";
+            return;
         }
-    }
+        if (one_lane) {
+            src << "double *const jc" << ow.col << " = jetw + " << jet_off(ow) << "u + q * " << jet_sys(ow) << "u + (ovalid"
+                << ow.col << " ? l : 0u);\n";
+            src << "const double *const jr" << ow.col << " = jc" << ow.col << ";\n";
+            return;
+        }
+        src << "double *const jc" << ow.col << " = jetw + q * " << n_colp << "u + (ovalid" << ow.col << " ? "
+            << ow.cbase << "u + l : " << n_col << "u);\n";
+        // The current state (order-0 row) is read from the column of the replicated variable by the idle lanes.
+        src << "const double *const jr" << ow.col << " = jetw + q * " << n_colp << "u + " << ow.cbase
+            << "u + (ovalid" << ow.col << " ? l : 0u);\n";
+    });
     // Lane slots of the final evaluation: slot h, lane l <-> jet column h * L + l (dummy column beyond the last one).
     for (std::uint32_t h = 0; !one_lane && h < n_hslots; ++h) {
         src << "double *const hc" << h << " = jetw + q * " << n_colp << "u + ((" << h * L << "u + l < " << n_col << "u) ? "
             << h * L << "u + l : " << n_col << "u);\n";
     }
+}
+
+// The event-equation section of mode 4. Reads opts.ev_prog, rounds and the jet layout; leaves ev_inline, ev_code, ev_coeffs,
+// pe_lane_ev / pe_lane_sign and the per-lane offsets of the leaf positions in src.
+void cluster2_gen::text_event_equations()
+{
     // Event equations inside the stepper (emit_options::ev_prog; one-lane-per-pair kernel): their jets from the jets of the
     // state variables in LDS - every lane of a system runs the same statements; the terms of a sum of isomorphic terms
     // (a squared distance, a radial velocity) are evaluated side by side, term c by lane c (ev_lane_hooks) -, the three
     // norms extended to them, then the ordinary selector, final evaluation and state update of this kernel. What is left
     // to the kernels behind the stepper: event detection on a.ev_tc, times / outcomes / records (hy_ev_post). The
     // statements are generated here (their per-lane offsets are declared ahead of the work loop) and pasted into the tail.
-    bool ev_inline = false;
-    // (lane -> (event, constant) of the close-encounter events which the lane of a pair contributes itself.)
-    std::map<std::uint32_t, std::pair<std::uint32_t, double>> pe_lane_ev;
-    std::map<std::uint32_t, double> pe_lane_sign; // (-1: the event equation is c - |r_i - r_j|^2)
-    std::string ev_code;
-    std::vector<std::vector<std::string>> ev_coeffs;
+    ev_inline = false;
     const bool packed_tail_ev = L >= 4u;
     if (m4 && one_lane && jet_lds && packed_tail_ev && opts.ev_prog != nullptr && !opts.exact_division && slab_stride >= n_own * L
         && opts.dev.events_in_stepper) {
@@ -2703,28 +1656,24 @@ __device__ __forceinline__ double hy_swap1(double x)
             std::uint32_t parent = 0;
         };
         std::vector<sv_loc> loc(n_eq);
-        for (const auto &rg : rounds) {
-            for (const auto &gr : rg) {
-                for (const auto &ow : gr.owners) {
-                    const auto &vv = utbl[ow.var_tbl];
-                    for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
-                        auto &lc = loc[vv[l2]];
-                        lc.stride = jet_sys(ow);
-                        if (ow.derived) {
-                            lc.derived = true;
-                            lc.off = jet_rows_doubles + jet_off(ow) + l2;
-                            for (const auto &o2 : gr.owners) {
-                                if (o2.col == ow.parent) {
-                                    lc.parent = utbl[o2.var_tbl][l2];
-                                }
-                            }
-                        } else {
-                            lc.off = jet_off(ow) + l2;
+        for_each_owner([&](auto &gr, auto &ow) {
+            const auto &vv = utbl[ow.var_tbl];
+            for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
+                auto &lc = loc[vv[l2]];
+                lc.stride = jet_sys(ow);
+                if (ow.derived) {
+                    lc.derived = true;
+                    lc.off = jet_rows_doubles + jet_off(ow) + l2;
+                    for (const auto &o2 : gr.owners) {
+                        if (o2.col == ow.parent) {
+                            lc.parent = utbl[o2.var_tbl][l2];
                         }
                     }
+                } else {
+                    lc.off = jet_off(ow) + l2;
                 }
             }
-        }
+        });
         const auto rowst = static_cast<std::uint64_t>(spw) * n_colp;
         const std::function<std::string(std::uint32_t, std::uint32_t)> sv = [&](std::uint32_t i, std::uint32_t k) -> std::string {
             const auto &lc = loc[i];
@@ -2852,6 +1801,11 @@ __device__ __forceinline__ double hy_swap1(double x)
             }
         }
     }
+}
+
+// Reads rounds and body; leaves the work loop up to and including the step body in src, and bk_lds.
+void cluster2_gen::text_pickup()
+{
     src << R"HIP(
 // Work distribution. Propagation (steps per system differ): a device-side queue, one group of systems at a time (taking
 // chunks of 8 groups per atomic costs 1 % there: consecutive groups no longer run at the same time on neighbouring
@@ -2888,13 +1842,9 @@ double t_hi = a.time_hi[s], t_lo = a.time_lo[s];
     for (const auto t : lane_par_tbls) {
         src << "const double lp" << t << " = a.pars[(u64)" << utname(t) << " * N + s];\n";
     }
-    for (const auto &rg : rounds) {
-        for (const auto &gr : rg) {
-            for (const auto &ow : gr.owners) {
-                src << row0_w(ow) << " = a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s];\n";
-            }
-        }
-    }
+    for_each_owner([&](auto &, auto &ow) {
+        src << row0_w(ow) << " = a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s];\n";
+    });
     src << "HY_WSYNC();\n" << (jet_lds ? "" : "__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, \"wavefront\");\n");
     src << R"HIP(
 hy_df tfin, rem;
@@ -2944,48 +1894,23 @@ const bool hy_tc_only = HY_M4 && ((a.pad & 2) != 0);
     // a tail, read back at the beginning of the next one - instead of being spilled to scratch by the register
     // allocator, whose reloads are scattered over the tail and each wait for a round trip through the vector memory
     // path. Every lane of a system holds the same values and stores them to the same address.
-    const bool bk_lds = one_lane;
-    const char *bk_fields_d[] = {"t_hi", "t_lo", "tfin.hi", "tfin.lo", "rem.hi", "rem.lo", "mdt", "step_lim", "min_h", "max_h", "last_h", "thr"};
-    // (which = 0: every field; 1: the fields a step changes; 2: the others - final time and limits, which only change when a
-    // system is picked up: an LDS store is the most expensive instruction of the kernel.)
-    const auto bk_store = [&](int which = 0) {
-        std::uint32_t f = 0;
-        for (const auto *nm : bk_fields_d) {
-            const std::string n_ = nm;
-            const bool constant = n_ == "tfin.hi" || n_ == "tfin.lo" || n_ == "mdt" || n_ == "step_lim" || n_ == "thr";
-            if (which == 0 || (which == 1) != constant) {
-                src << "bk[" << f << "] = " << nm << ";\n";
-            }
-            ++f;
-        }
-        if (which == 2) {
-            return;
-        }
-        src << "bk[" << f++ << "] = __longlong_as_double((long long)n_steps);\n";
-        src << "bk[" << f++ << "] = __longlong_as_double((long long)iter);\n";
-        src << "bk[" << f++ << "] = __longlong_as_double((long long)outcome);\n";
-        src << "bk[" << f++ << "] = __longlong_as_double((long long)((t_dir ? 1 : 0) | (nf_seen != 0 ? 2 : 0) | (gfin ? 4 : 0)));\n";
-    };
-    const auto bk_load = [&]() {
-        std::uint32_t f = 0;
-        for (const auto *nm : bk_fields_d) {
-            src << nm << " = bk[" << f++ << "];\n";
-        }
-        src << "n_steps = (u64)__double_as_longlong(bk[" << f++ << "]);\n";
-        src << "iter = (u64)__double_as_longlong(bk[" << f++ << "]);\n";
-        src << "outcome = (i64)__double_as_longlong(bk[" << f++ << "]);\n";
-        src << "{\nconst long long fl = __double_as_longlong(bk[" << f++ << "]);\nt_dir = (fl & 1) != 0;\nnf_seen = (fl & 2) != 0 ? 1 : 0;\ngfin = (fl & 4) != 0;\n}\n";
-    };
+    bk_lds = one_lane;
     if (bk_lds) {
         bk_store();
         src << "HY_WSYNC();\n";
     }
     src << "for (;;) {\n";
     src << body;
+}
+
+// The step-size selector. Reads pe_lane_ev, the histories of the one-lane program, ev_code, rounds and pk_tbl; leaves the
+// norms reduced over the lanes (with the event equations folded in), pe_g, tail_passes (with the jet reads issued ahead of
+// the selector), kstride and the step size h.
+void cluster2_gen::text_selector()
+{
     // Close-encounter events on the lanes of their pairs (pe_lane_ev): g^[0] = b_0 + c, g^[k] = (b_k / b_0) b_0 from the
     // history of the pow recurrence, g^[p] from one more convolution; folded into the three norms of the lane BEFORE the
     // reduction over the lanes (masked: a lane without an event contributes nothing).
-    std::vector<std::string> pe_g;
     if (!pe_lane_ev.empty()) {
         src << "HY_WSYNC();\n";
         std::string dK[3];
@@ -3029,17 +1954,16 @@ const bool hy_tc_only = HY_M4 && ((a.pad & 2) != 0);
     // the logarithm of the selector is then evaluated once, on the packed lanes (hy_sel_log above).
     const bool packed_tail = L >= 4u;
     const auto red_ex = [&](std::uint32_t m, const char *v) -> std::string {
-        const bool dpp_ok = true;
-        if (dpp_ok && m == 1u) {
+        if (m == 1u) {
             return std::string("hy_dpp<0xB1>(") + v + ")";
         }
-        if (dpp_ok && m == 2u) {
+        if (m == 2u) {
             return std::string("hy_dpp<0x4E>(") + v + ")";
         }
-        if (dpp_ok && m == 4u && L % 16u == 0u) {
+        if (m == 4u && L % 16u == 0u) {
             return std::string("hy_dpp<0x124>(") + v + ")";
         }
-        if (dpp_ok && m == 8u && L % 16u == 0u) {
+        if (m == 8u && L % 16u == 0u) {
             return std::string("hy_dpp<0x128>(") + v + ")";
         }
         return std::string("__shfl_xor(") + v + ", " + std::to_string(m) + ", 64)";
@@ -3094,38 +2018,23 @@ const bool hy_tc_only = HY_M4 && ((a.pad & 2) != 0);
     }
     // NOTE: rho = exp(log(x) / order) (hy_root): the minimum of the two estimates is taken on the exponents (exp is
     // monotone and keeps NaNs: the same selection as min(rho_o, rho_om1), src/taylor_02.cpp:1050-1072, one exp less).
-    // The passes of the final evaluation of the one-lane kernel, in order: one per variable with a jet column (ow), with the
-    // variable derived from it (dv: x' = v, at most one - chains of length <= 2); `packed` = the partially filled owner
-    // slot which runs one series per lane. rows / facs: the names of the jet rows (and of the factors RN(1 / k) of a packed
-    // pass) where their LDS reads have been issued ahead of the selector - empty otherwise.
-    struct tail_pass {
-        const owner_slot *ow, *dv;
-        bool packed;
-        std::vector<std::string> rows, facs;
-    };
-    std::vector<tail_pass> tail_passes;
-    for (const auto &rg : rounds) {
-        for (const auto &gr : rg) {
-            for (const auto &ow : gr.owners) {
-                if (!one_lane || ow.derived) {
-                    continue;
-                }
-                const owner_slot *dv = nullptr;
-                for (const auto &o2 : gr.owners) {
-                    if (o2.derived && o2.parent == ow.col) {
-                        dv = &o2;
-                    }
-                }
-                tail_passes.push_back({&ow, dv, dv != nullptr && pk_tbl.count(ow.col) != 0u, {}, {}});
+    for_each_owner([&](auto &gr, auto &ow) {
+        if (!one_lane || ow.derived) {
+            return;
+        }
+        const owner_slot *dv = nullptr;
+        for (const auto &o2 : gr.owners) {
+            if (o2.derived && o2.parent == ow.col) {
+                dv = &o2;
             }
         }
-    }
+        tail_passes.push_back({&ow, dv, dv != nullptr && pk_tbl.count(ow.col) != 0u, {}, {}});
+    });
     // (Doubles between two rows of a jet column.)
-    const auto kstride = static_cast<std::uint64_t>(spw) * n_colp;
+    kstride = static_cast<std::uint64_t>(spw) * n_colp;
     // The jet reads of the final evaluation (one-lane kernel, jets in LDS, compensated sums): issued HERE, ahead of the
     // selector's log / exp chain, which covers their latency - the history registers are dead in the tail, so the 20 rows
     // of a pass fit. "notailrd" among HEYOKA_AMD_V5_OPTS leaves them behind the step size, where the series consume them.
-    std::uint32_t n_trd = 0, n_trd_used = 0;
     if (one_lane && !m4 && jet_lds && opts.high_accuracy && packed_tail && !v5_flag("notailrd")) {
         src << "// (Jet reads of the final evaluation issued ahead of the selector.)\n";
         const auto hoist = [&](const std::string &ex) {
@@ -3154,14 +2063,6 @@ const bool hy_tc_only = HY_M4 && ((a.pad & 2) != 0);
         }
         src << "__builtin_amdgcn_sched_barrier(0);\n";
     }
-    // (A value the final evaluation reads: the name it was given above, or the read itself.)
-    const auto tail_val = [&n_trd_used](const std::vector<std::string> &names, std::uint32_t k, const std::string &ex) {
-        if (names.empty()) {
-            return ex;
-        }
-        ++n_trd_used;
-        return names.at(k);
-    };
     if (packed_tail) {
         // log(num / m) = log(num) - log(m): no quotients (0 -> +inf, inf -> -inf, inf - inf -> nan as for the quotient).
         src << "const double nw = (hy_q0 & (nv <= 1.0)) ? 1.0 : nv;\n";
@@ -3201,6 +2102,11 @@ lim = fin ? 0.0 : lim;
     // the double-length time, the remaining time, the state and the step counters then reproduce themselves bit by bit,
     // and only the values which a zero-length step would overwrite need a select below (last_h, outcome).
     src << "h = fin ? 0.0 : h;\n";
+}
+
+// Reads ev_coeffs and pe_g; leaves the exclusion test and the stores of the event jets (event equations inside the stepper).
+void cluster2_gen::text_event_exclusion()
+{
     if (ev_inline) {
         // On-demand Taylor coefficients. Behind a step with events nothing reads the coefficients of the state variables
         // unless an event is detected (its callback may ask for dense output) or the caller asks for them. The stepper
@@ -3241,11 +2147,7 @@ lim = fin ? 0.0 : lim;
         };
         src << "if (__builtin_amdgcn_ballot_w64(maybe0 | pe_m0) != 0ull) {\n";
         src << "bool maybe = false, maybe_te = false;\nconst double lo_h = (h < 0.0) ? h : 0.0, hi_h = (h < 0.0) ? 0.0 : h;\n";
-        for (std::size_t ci = 0; ci < ev_coeffs.size(); ++ci) {
-            const auto &c = ev_coeffs[ci];
-            if (c.empty()) {
-                continue;
-            }
+        const auto enclosure = [&](const std::vector<std::string> &c) {
             src << "{\ndouble lo = " << c[order] << ", hi = lo, mm = fabs(lo);\n";
             for (std::uint32_t i = 1; i <= order; ++i) {
                 src << "{\nconst double p0 = lo * lo_h, p1 = lo * hi_h, p2 = hi * lo_h, p3 = hi * hi_h;\n"
@@ -3253,18 +2155,19 @@ lim = fin ? 0.0 : lim;
                     << "lo = mn + " << c[order - i] << ";\nhi = mx + " << c[order - i] << ";\n"
                     << "mm = fmax(mm, fmax(fabs(lo), fabs(hi)));\n}\n";
             }
+        };
+        for (std::size_t ci = 0; ci < ev_coeffs.size(); ++ci) {
+            const auto &c = ev_coeffs[ci];
+            if (c.empty()) {
+                continue;
+            }
+            enclosure(c);
             src << "const bool excl = (((lo > 0.0) & (hi > 0.0)) | ((lo < 0.0) & (hi < 0.0))) & (fmin(fabs(lo), fabs(hi)) > 1e-8 * mm);\n"
                 << "maybe = maybe | !excl;\n" << (ci < opts.n_t_events ? "maybe_te = maybe_te | !excl;\n" : "") << "}\n";
         }
         src << "bool pe_m = false;\n";
         if (!pe_g.empty()) {
-            src << "{\ndouble lo = " << pe_g[order] << ", hi = lo, mm = fabs(lo);\n";
-            for (std::uint32_t i = 1; i <= order; ++i) {
-                src << "{\nconst double p0 = lo * lo_h, p1 = lo * hi_h, p2 = hi * lo_h, p3 = hi * hi_h;\n"
-                    << "const double mn = fmin(fmin(p0, p1), fmin(p2, p3)), mx = fmax(fmax(p0, p1), fmax(p2, p3));\n"
-                    << "lo = mn + " << pe_g[order - i] << ";\nhi = mx + " << pe_g[order - i] << ";\n"
-                    << "mm = fmax(mm, fmax(fabs(lo), fabs(hi)));\n}\n";
-            }
+            enclosure(pe_g);
             src << "const bool excl = (((lo > 0.0) & (hi > 0.0)) | ((lo < 0.0) & (hi < 0.0))) & (fmin(fabs(lo), fabs(hi)) > 1e-8 * mm);\n"
                 << "pe_m = pe_m0 & !excl;\n}\n";
         }
@@ -3291,10 +2194,13 @@ lim = fin ? 0.0 : lim;
             src << "a.ev_tc[(pe_row + " << k << "u) * N + s] = " << pe_g[k] << ";\n";
         }
         src << "}\n";
-    } else if (ev_inline) {
-        src << "if (!hy_tc_only) a.sel_norms[s] = 1.0;\n";
     }
+}
 
+// Reads tail_passes and rounds; leaves the final evaluation of the series, the new time, the Taylor coefficients on
+// request, the state update and the bookkeeping of the step.
+void cluster2_gen::text_final_evaluation_and_update()
+{
     src << "asm volatile(\"\" ::: \"memory\");\n";
     // NOTE: with the jets in global scratch the lanes exchange them through memory: wavefront-scope fences.
     const char *jet_fence = jet_lds ? "" : "__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, \"wavefront\");\n";
@@ -3479,23 +2385,19 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
     } else {
         src << (jet_lds ? "if (a.tc != nullptr && !HY_M4) {\n" : "if (a.tc != nullptr) {\n");
     }
-    for (const auto &rg : rounds) {
-        for (const auto &gr : rg) {
-            for (const auto &ow : gr.owners) {
-                if (ow.derived) {
-                    src << "{\nconst double *c = jr" << ow.parent << ";\ndouble *tcp = a.tc + ((u64)hy_utbl[" << ow.var_tbl * L
-                        << "u + l] * " << (order + 1u) << "u) * N + s;\n*tcp = " << row0_r(ow) << ";\ntcp += N;\n"
-                        << "#pragma nounroll\nfor (unsigned k = 1; k <= " << order << "u; ++k) {\n*tcp = c[(u64)(k - 1u) * "
-                        << kstride << "u] * hy_rk[k];\ntcp += N;\n}\n}\n";
-                    continue;
-                }
-                src << "{\nconst double *c = jr" << ow.col << ";\ndouble *tcp = a.tc + ((u64)hy_utbl[" << ow.var_tbl * L
-                    << "u + l] * " << (order + 1u) << "u) * N + s;\n"
-                    << "#pragma nounroll\nfor (unsigned k = 0; k <= " << order << "u; ++k) {\n*tcp = c[(u64)k * "
-                    << kstride << "u];\ntcp += N;\n}\n}\n";
-            }
+    for_each_owner([&](auto &, auto &ow) {
+        if (ow.derived) {
+            src << "{\nconst double *c = jr" << ow.parent << ";\ndouble *tcp = a.tc + ((u64)hy_utbl[" << ow.var_tbl * L
+                << "u + l] * " << (order + 1u) << "u) * N + s;\n*tcp = " << row0_r(ow) << ";\ntcp += N;\n"
+                << "#pragma nounroll\nfor (unsigned k = 1; k <= " << order << "u; ++k) {\n*tcp = c[(u64)(k - 1u) * "
+                << kstride << "u] * hy_rk[k];\ntcp += N;\n}\n}\n";
+            return;
         }
-    }
+        src << "{\nconst double *c = jr" << ow.col << ";\ndouble *tcp = a.tc + ((u64)hy_utbl[" << ow.var_tbl * L
+            << "u + l] * " << (order + 1u) << "u) * N + s;\n"
+            << "#pragma nounroll\nfor (unsigned k = 0; k <= " << order << "u; ++k) {\n*tcp = c[(u64)k * "
+            << kstride << "u];\ntcp += N;\n}\n}\n";
+    });
     src << "}\n";
     // The new state becomes the order-0 row of the jets (read back by the owner lanes at the top of the next step).
     src << "HY_WSYNC();\n" << jet_fence;
@@ -3540,6 +2442,12 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
     fin = fin | done;
 }
 )HIP";
+}
+
+// Reads rounds and the variant; leaves the per-system refill, the end of the step loop, the cooperative store of mode 4
+// and the final stores of a group of systems.
+void cluster2_gen::text_refill_and_tail()
+{
     // Per-system refill (propagations through the device-side work queue): the step loop is left by the whole wavefront at
     // once, so a system which reaches its final time early idles - zero-length steps - until the slowest of the SPW
     // systems of its wavefront is done. With heterogeneous step counts (per-lane final times T * U(0.5, 1.5): 37 .. 127 steps
@@ -3553,14 +2461,10 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
     if (refill) {
         src << "if (!hy_static && !hy_queue_empty && __builtin_amdgcn_ballot_w64(fin) != 0ull) {\n";
         // 1. Retire.
-        for (const auto &rg : rounds) {
-            for (const auto &gr : rg) {
-                for (const auto &ow : gr.owners) {
-                    src << "if (fin && ovalid" << ow.col << " && live) a.state[(u64)hy_utbl[" << ow.var_tbl * L
-                        << "u + l] * N + s] = " << row0_w(ow) << ";\n";
-                }
-            }
-        }
+        for_each_owner([&](auto &, auto &ow) {
+            src << "if (fin && ovalid" << ow.col << " && live) a.state[(u64)hy_utbl[" << ow.var_tbl * L
+                << "u + l] * N + s] = " << row0_w(ow) << ";\n";
+        });
         src << R"HIP(
 if (fin && l == 0u && live) {
     a.time_hi[s] = t_hi;
@@ -3593,13 +2497,9 @@ if (got) {
     t_hi = a.time_hi[s];
     t_lo = a.time_lo[s];
 )HIP";
-        for (const auto &rg : rounds) {
-            for (const auto &gr : rg) {
-                for (const auto &ow : gr.owners) {
-                    src << row0_w(ow) << " = a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s];\n";
-                }
-            }
-        }
+        for_each_owner([&](auto &, auto &ow) {
+            src << row0_w(ow) << " = a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s];\n";
+        });
         src << R"HIP(
     tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[s] : a.tfin_s_hi;
     tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[s] : a.tfin_s_lo;
@@ -3658,19 +2558,15 @@ if (nf_seen != 0 && l == 0u && live) atomicAdd(a.counters, 1u);
     }
     src << R"HIP(
 )HIP";
-    for (const auto &rg : rounds) {
-        for (const auto &gr : rg) {
-            for (const auto &ow : gr.owners) {
-                if (m4 && !ev_inline) {
-                    // (The stepper with events leaves the state, the time and the step size to the kernels behind it -
-                    // unless it evaluates the event equations itself: then the state is final here.)
-                    continue;
-                }
-                src << "if (ovalid" << ow.col << " && live && !hy_tc_only) a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s] = "
-                    << (ev_inline ? ("slab[" + std::to_string(ow.col * L) + "u + l]") : row0_w(ow)) << ";\n";
-            }
+    for_each_owner([&](auto &, auto &ow) {
+        if (m4 && !ev_inline) {
+            // (The stepper with events leaves the state, the time and the step size to the kernels behind it -
+            // unless it evaluates the event equations itself: then the state is final here.)
+            return;
         }
-    }
+        src << "if (ovalid" << ow.col << " && live && !hy_tc_only) a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s] = "
+            << (ev_inline ? ("slab[" + std::to_string(ow.col * L) + "u + l]") : row0_w(ow)) << ";\n";
+    });
     src << R"HIP(
 if (l == 0u && live && !hy_tc_only) {
     if (!HY_M4) {
@@ -3693,48 +2589,55 @@ if (l == 0u && live && !hy_tc_only) {
 }
 }
 )HIP";
+}
 
-    ret.source = src.str();
-    ret.kernel_name = "hy_taylor";
-    ret.dout_name = "hy_dout";
-    ret.block_size = bs;
-    ret.lanes_per_system = L;
-    ret.lds_bytes = 0;
-    ret.mode = emit_mode::cluster;
-    ret.n_statements = e.n_stmt;
-    ret.scratch_per_wave = jet_lds ? 0u : jet_doubles_per_wave;
-    ret.persistent = true;
+// Leaves the emitted_module and the typed verdict in res.
+void cluster2_gen::finish()
+{
+    res.mod.source = src.str();
+    res.mod.kernel_name = "hy_taylor";
+    res.mod.dout_name = "hy_dout";
+    res.mod.block_size = bs;
+    res.mod.lanes_per_system = L;
+    res.mod.lds_bytes = 0;
+    res.mod.mode = emit_mode::cluster;
+    res.mod.n_statements = e.n_stmt;
+    res.mod.scratch_per_wave = jet_lds ? 0u : jet_doubles_per_wave;
+    res.mod.persistent = true;
     if (pairk) {
         // NOTE: MachineLICM hoists the materialisation of ~50 fp64 literals (1 / k, the polynomial constants of the
         // step-size selector) out of the step loop into SGPR pairs: pointers and masks are then spilled to VGPR lanes and
         // come back through 186 v_readlane_b32 per step (VALU issue slots). Without it: 20, and 7 % fewer VALU
         // instructions in the loop (measured: +2 % system-steps/s, profiles/experiments/run17.sh).
-        ret.compile_flags = "-mllvm -disable-machine-licm";
+        res.mod.compile_flags = "-mllvm -disable-machine-licm";
         if (one_lane) {
             // NOTE: no merging of LDS accesses: on gfx950 a ds_read2_b64 is serviced at half the rate of two ds_read_b64
             // (8 against 2 x 2 LDS cycles per wavefront) and this kernel is within 25 % of the LDS throughput.
-            ret.compile_flags += " -Xclang -target-feature -Xclang -load-store-opt -mllvm -amdgpu-load-store-vectorizer=0";
+            res.mod.compile_flags += " -Xclang -target-feature -Xclang -load-store-opt -mllvm -amdgpu-load-store-vectorizer=0";
         }
     }
-    ret.tc_optional = true;
-    ret.cluster_mode4 = m4;
-    ret.events_in_stepper = ev_inline;
-    ret.compact_tc = compact_tc;
-    ret.tc_by_threshold = one_lane && jet_lds && !m4;
-    ret.grid_multi_step = ret.tc_by_threshold;
-    one_lane_jets_in_lds = one_lane && jet_lds;
-    ret.notes = std::string(one_lane ? "cluster mode v5 (one lane per pair, 2 wavefronts per SIMD): "
+    res.mod.tc_optional = true;
+    res.mod.cluster_mode4 = m4;
+    res.mod.events_in_stepper = ev_inline;
+    res.mod.compact_tc = compact_tc;
+    res.mod.tc_by_threshold = one_lane && jet_lds && !m4;
+    res.mod.grid_multi_step = res.mod.tc_by_threshold;
+    res.jets_in_lds = one_lane && jet_lds;
+    res.variant = variant;
+    res.mod.cluster_generation = one_lane ? 5 : (pair_split ? 3 : 2);
+    res.mod.notes = std::string(one_lane ? "cluster mode v5 (one lane per pair, 2 wavefronts per SIMD): "
                                      : (pair_split ? "cluster mode v3 (lane pairs, 2 wavefronts per SIMD): " : "cluster mode v2 (pipelined): "))
-                + std::to_string(nc) + " clusters of " + std::to_string(t0.size())
+                + std::to_string(nc) + " clusters of " + std::to_string(t0().size())
                 + " nodes, L=" + std::to_string(L) + ", " + std::to_string(pl.n_slots) + " LDS slots x2, "
                 + std::to_string(n_own) + " state-variable owner slots, " + std::to_string(utbl.size())
                 + " slot tables, jets in " + (jet_lds ? "LDS" : "global scratch")
                 + (one_lane ? ", slab layout: " + std::to_string(bank_cost) + " conflict cycles per step in the model" : std::string{})
                 + (ev_inline ? "; event equations, final step size and state update inside the stepper" : "");
-    return ret;
 }
 
-} // namespace
+} // namespace heyoka_amd::cluster2_detail
+namespace heyoka_amd
+{
 
 emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts, std::string &why_not)
 {
@@ -3744,28 +2647,26 @@ emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts
     // fit in its LDS - and the lane-pair kernel with the jets in global scratch which used to serve them spills 176 / 116
     // registers. More lanes per system than pairs (idle lanes replicate pair 0 and write to dummy slots, like the 16th lane
     // of the outer Solar System) bring the systems per CU down to what fits: the second and third attempts.
-    bool in_lds = false;
     std::string why1;
     const bool try_one_lane = opts.cluster_kernel == 0 || opts.cluster_kernel == 5;
     for (const std::uint32_t min_lanes : {4u, 8u, 16u}) {
         why1.clear();
-        auto ret = emit_cluster_v2_impl(p, opts, why1, try_one_lane, in_lds, min_lanes);
-        const bool is_v5 = ret.notes.find("cluster mode v5") != std::string::npos;
+        auto at = cluster2_detail::cluster2_gen(p, opts, why1, try_one_lane, min_lanes).run();
+        const bool is_v5 = why1.empty() && at.variant == cluster2_detail::cluster2_variant::one_lane, in_lds = at.jets_in_lds;
         if (try_one_lane) {
             detail::log_message(log_level::debug, "one-lane-per-pair kernel, at least " + std::to_string(min_lanes) + " lanes per system: "
                                               + (!why1.empty() ? why1 : (!is_v5 ? "not applicable" : (in_lds ? "accepted" : "the jets of the systems of a CU do not fit in its LDS"))));
         }
         if (why1.empty() && (in_lds || !is_v5)) {
             why_not.clear();
-            return ret;
+            return std::move(at.mod);
         }
         // (Another attempt only for the reasons which more lanes per system cure.)
-        const bool lds_reason = why1.find("needs the jets in LDS") != std::string::npos;
-        if (!try_one_lane || (!why1.empty() && !lds_reason) || (why1.empty() && !is_v5)) {
+        if (!try_one_lane || (!why1.empty() && !at.more_lanes_cure) || (why1.empty() && !is_v5)) {
             break;
         }
     }
-    return emit_cluster_v2_impl(p, opts, why_not, false, in_lds);
+    return cluster2_detail::cluster2_gen(p, opts, why_not, false, 4u).run().mod;
 }
 
 } // namespace heyoka_amd
