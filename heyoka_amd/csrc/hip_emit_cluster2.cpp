@@ -200,6 +200,7 @@ void cluster2_gen::plan_and_select_variant()
     // once: the nodes of the sum group are reordered so that the sums made of direct products alone (the first body of every
     // pair it takes part in) come last - the rounds after the first are then plain sums without coefficients.
     frx = false;
+    lane_sum = false;
     if (one_lane && !m4 && pp.rx[0] >= 0 && pl.groups.size() == 1u && !v5_flag("nofrx")) {
         auto &nodes = pl.groups[0].nodes;
         std::map<std::uint32_t, bool> is_rx_out; // cluster output -> is it a reaction?
@@ -232,10 +233,37 @@ void cluster2_gen::plan_and_select_variant()
             // Every round after the first must consist of plain sums.
             frx = first.size() <= pl.L && !last.empty();
             if (frx) {
+                const auto n_first = static_cast<std::uint32_t>(first.size());
                 first.insert(first.end(), last.begin(), last.end());
                 nodes = std::move(first);
+                // (The plain sums by a reduction over the lanes of the first round where the plan allows it.)
+                if (!v5_flag("nolanesum")) {
+                    plan_lane_sums(n_first);
+                }
             }
         }
+    }
+}
+
+// Renumber the slab slots of the state variables in owner order (group, round, chain position, lane), so
+// that the lanes publishing new coefficients write consecutive slots (distinct LDS banks).
+void cluster2_gen::renumber_sv_slots()
+{
+    std::uint32_t next = 0;
+    for (std::size_t g = 0; g < pl.groups.size(); ++g) {
+        const auto &nodes = pl.groups[g].nodes;
+        for (std::uint32_t r = 0; r < n_rounds_of(g); ++r) {
+            for (std::uint32_t a = 0; a < grp_natt[g]; ++a) {
+                for (std::uint32_t l = 0; l < L; ++l) {
+                    if (const auto [j, valid] = round_node(g, r, l); valid) {
+                        pl.slot_of[att.at(nodes[j])[a]] = static_cast<int>(next++);
+                    }
+                }
+            }
+        }
+    }
+    if (next != n_eq) {
+        why_not = "internal error: state-variable slots";
     }
 }
 
@@ -311,25 +339,9 @@ void cluster2_gen::anchors_and_reaction_fusion()
         grp_natt[g] = n0;
     }
 
-    // Renumber the slab slots of the state variables in owner order (group, round, chain position, lane), so
-    // that the lanes publishing new coefficients write consecutive slots (distinct LDS banks).
-    {
-        std::uint32_t next = 0;
-        for (std::size_t g = 0; g < pl.groups.size(); ++g) {
-            const auto &nodes = pl.groups[g].nodes;
-            const auto n_nodes = static_cast<std::uint32_t>(nodes.size());
-            for (std::uint32_t r = 0; r * L < n_nodes; ++r) {
-                for (std::uint32_t a = 0; a < grp_natt[g]; ++a) {
-                    for (std::uint32_t l = 0; l < L && r * L + l < n_nodes; ++l) {
-                        pl.slot_of[att.at(nodes[r * L + l])[a]] = static_cast<int>(next++);
-                    }
-                }
-            }
-        }
-        if (next != n_eq) {
-            why_not = "internal error: state-variable slots";
-            return;
-        }
+    renumber_sv_slots();
+    if (!why_not.empty()) {
+        return;
     }
 
     // Reaction fusion (lane-pair variant): the members c * pr of a cluster (the reaction on the second body of the pair)
@@ -378,6 +390,14 @@ void cluster2_gen::anchors_and_reaction_fusion()
         }
     }
     frx = frx && fuse_rx;
+    if (lane_sum && !frx) {
+        // (Without the fused reactions: the rounds, and the slots numbered after them above, as they were.)
+        lane_sum = false;
+        renumber_sv_slots();
+        if (!why_not.empty()) {
+            return;
+        }
+    }
     // A glue node / state variable needs a slab slot only if somebody reads it through the slab.
     glue_read.assign(p.n_u, 0);
     for (const auto &n : p.nodes) {
@@ -554,6 +574,12 @@ void cluster2_gen::layout_one_lane()
         const bool wide_an = wide_rd;
         wide_rd = wide_rd && !frx;
         vexch = vexch && wide_an;
+        if (lane_sum && !vexch) {
+            // (The lane-reduced sums address the jets by column, [system][column]: the layout of the velocity exchange.
+            // Without it: the rounds, and the slots numbered after them, as they were.)
+            lane_sum = false;
+            renumber_sv_slots();
+        }
         std::vector<int> remap(pl.n_slots, -1);
         std::uint32_t ns = 0;
         const auto keep = [&](std::uint32_t u) {
@@ -633,17 +659,17 @@ void cluster2_gen::layout_one_lane()
             }
         }
         for (const auto &grp : pl.groups) {
-            const auto n_nodes = static_cast<std::uint32_t>(grp.nodes.size());
+            const auto g = static_cast<std::size_t>(&grp - pl.groups.data());
             const auto &n0 = p.nodes[grp.nodes[0] - n_eq];
-            for (std::uint32_t r = 0; r * pl.L < n_nodes; ++r) {
+            // (A lane-reduced round reads nothing.)
+            for (std::uint32_t r = 0; r < (lane_sum && g == 0u ? 1u : n_rounds_of(g)); ++r) {
                 for (std::size_t a = 0; a < n0.args.size(); ++a) {
                     if (!is_var(n0.args[a])) {
                         continue;
                     }
                     std::vector<std::uint32_t> v(pl.L);
                     for (std::uint32_t l = 0; l < pl.L; ++l) {
-                        const auto j = r * pl.L + l;
-                        v[l] = p.nodes[grp.nodes[j < n_nodes ? j : r * pl.L] - n_eq].args[a].idx;
+                        v[l] = p.nodes[grp.nodes[round_node(g, r, l).first] - n_eq].args[a].idx;
                         if (fuse_rx && rx_fused[v[l]] != 0) {
                             v[l] = rx_src[v[l]];
                         }
@@ -913,23 +939,28 @@ void cluster2_gen::build_glue_rounds()
     rounds.assign(pl.groups.size(), {});
     for (std::size_t g = 0; g < pl.groups.size(); ++g) {
         const auto &grp = pl.groups[g];
-        const auto n_nodes = static_cast<std::uint32_t>(grp.nodes.size());
-        const auto n_rounds = (n_nodes + L - 1u) / L;
+        const auto n_rounds = n_rounds_of(g);
         const auto &n0 = p.nodes[grp.nodes[0] - n_eq];
         for (std::uint32_t r = 0; r < n_rounds; ++r) {
             glue_round gr;
-            gr.n_valid = std::min(L, n_nodes - r * L);
-            const auto node_of = [&](std::uint32_t l) {
-                const auto j = r * L + l;
-                return grp.nodes[j < n_nodes ? j : r * L];
-            };
+            const bool mapped = lane_sum && g == 0u;
+            // (Which lanes own a node of the round.)
+            std::uint32_t valid_mask = 0;
+            for (std::uint32_t l = 0; l < L; ++l) {
+                valid_mask |= round_node(g, r, l).second ? (1u << l) : 0u;
+            }
+            const auto is_valid = [&](std::uint32_t l) { return (valid_mask >> l & 1u) != 0u; };
+            gr.n_valid = static_cast<std::uint32_t>(__builtin_popcount(valid_mask));
+            // (Lane-reduced round: the sums come out of the registers of the first round, see emit_glue_compute().)
+            gr.reduced = mapped && r == 1u;
+            const auto node_of = [&](std::uint32_t l) { return grp.nodes[round_node(g, r, l).first]; };
             bool round_fused = false;
             for (std::uint32_t l = 0; fuse_rx && l < L; ++l) {
                 for (const auto &o : p.nodes[node_of(l) - n_eq].args) {
                     round_fused = round_fused || (is_var(o) && rx_fused[o.idx] != 0);
                 }
             }
-            for (std::size_t a = 0; a < n0.args.size(); ++a) {
+            for (std::size_t a = 0; a < n0.args.size() && !gr.reduced; ++a) {
                 if (is_var(n0.args[a]) && round_fused) {
                     std::vector<std::uint32_t> v(L);
                     std::vector<double> cf(L, 1.);
@@ -970,9 +1001,9 @@ void cluster2_gen::build_glue_rounds()
             bool any_read = false;
             std::vector<std::uint32_t> v(L);
             for (std::uint32_t l = 0; l < L; ++l) {
-                const auto j = r * L + l;
-                v[l] = (j < n_nodes && pl.slot_of[grp.nodes[j]] >= 0) ? static_cast<std::uint32_t>(pl.slot_of[grp.nodes[j]]) : dummy_base;
-                any_read = any_read || (j < n_nodes && glue_read[grp.nodes[j]] != 0);
+                const auto u = node_of(l);
+                v[l] = (is_valid(l) && pl.slot_of[u] >= 0) ? static_cast<std::uint32_t>(pl.slot_of[u]) : dummy_base;
+                any_read = any_read || (is_valid(l) && glue_read[u] != 0);
             }
             gr.exported = any_read;
             gr.out_tbl = add_utbl(std::move(v));
@@ -981,8 +1012,20 @@ void cluster2_gen::build_glue_rounds()
                 std::vector<std::uint32_t> vs(L), vv(L);
                 for (std::uint32_t l = 0; l < L; ++l) {
                     const auto var = att.at(node_of(l))[a];
-                    vs[l] = (r * L + l < n_nodes && pl.slot_of[var] >= 0) ? static_cast<std::uint32_t>(pl.slot_of[var]) : dummy_base;
+                    vs[l] = (is_valid(l) && pl.slot_of[var] >= 0) ? static_cast<std::uint32_t>(pl.slot_of[var]) : dummy_base;
                     vv[l] = var;
+                }
+                if (mapped) {
+                    // (Jet column of a node = its index in the group: the columns stay in the order of the nodes, whichever
+                    // lane computes them.)
+                    std::vector<std::uint32_t> vc(L);
+                    for (std::uint32_t l = 0; l < L; ++l) {
+                        vc[l] = round_node(g, r, l).first;
+                    }
+                    ow.mapped = true;
+                    ow.reduced = gr.reduced;
+                    ow.col_tbl = add_utbl(std::move(vc), false);
+                    ow.valid_mask = valid_mask;
                 }
                 ow.out_tbl = add_utbl(std::move(vs));
                 ow.var_tbl = add_utbl(std::move(vv), false);
@@ -999,8 +1042,8 @@ void cluster2_gen::build_glue_rounds()
                 }
                 ow.xname.resize(order + 1u);
                 ow.slab_needed = false;
-                for (std::uint32_t l = 0; l < L && r * L + l < n_nodes; ++l) {
-                    ow.slab_needed = ow.slab_needed || glue_read[att.at(grp.nodes[r * L + l])[a]] != 0;
+                for (std::uint32_t l = 0; l < L; ++l) {
+                    ow.slab_needed = ow.slab_needed || (is_valid(l) && glue_read[att.at(node_of(l))[a]] != 0);
                 }
                 // (Velocity exchange: nobody reads a position coefficient - the compiler drops the unused ones.)
                 ow.slab_needed = ow.slab_needed && !vexch;
@@ -1223,8 +1266,17 @@ void cluster2_gen::emit_step_body()
             if (k < order) {
                 sched_fence();
             }
-            for (const auto &[g, r, names] : pend) {
-                emit_glue_compute(g, r, k - 1u, names);
+            if (lane_sum && k >= 1u) {
+                // The lane-reduced round first: its terms are one operand of the first round, and its lanes without a sum
+                // store their partial sums to a jet column of the FIRST round (ls_park), which the store of that round - the
+                // next LDS instruction of the wavefront to that address: they complete in order - overwrites with the
+                // coefficient. (The jets have no spare column, and a select of the address would cost every order.)
+                emit_glue_compute(0, 1, k - 1u, {std::get<2>(pend[0]).at(ls_pos)});
+                emit_glue_compute(0, 0, k - 1u, std::get<2>(pend[0]));
+            } else {
+                for (const auto &[g, r, names] : pend) {
+                    emit_glue_compute(g, r, k - 1u, names);
+                }
             }
             if (k < order) {
                 emit_single_compute(k, prd);
@@ -1463,7 +1515,12 @@ __device__ __forceinline__ double hy_swap1(double x)
         std::vector<std::uint32_t> col_of(n_eq, 0);
         for_each_owner([&](auto &, auto &ow) {
             const auto &vv = utbl[ow.var_tbl];
-            for (std::uint32_t l2 = 0; l2 < ow.n_valid; ++l2) {
+            for (std::uint32_t l2 = 0; l2 < L && ow.mapped; ++l2) {
+                if ((ow.valid_mask >> l2 & 1u) != 0u) {
+                    col_of[vv[l2]] = utbl[ow.col_tbl][l2];
+                }
+            }
+            for (std::uint32_t l2 = 0; l2 < ow.n_valid && !ow.mapped; ++l2) {
                 col_of[vv[l2]] = ow.cbase + l2;
             }
         });
@@ -1606,6 +1663,15 @@ void cluster2_gen::text_kernel_prologue()
         src << "const double ccst" << x << " = dt" << cst_tbl[x] << ";\n";
     }
     for_each_owner([&](auto &gr, auto &ow) {
+        if (ow.mapped) {
+            // (Lane-reduced sums: the lane's jet column and whether the lane owns it come from the tables.)
+            src << "const bool ovalid" << ow.col << " = ((" << ow.valid_mask << "u >> l) & 1u) != 0u;\n";
+            const auto nm = (ow.derived ? "x0c" : "jc") + std::to_string(ow.col);
+            src << "double *const " << nm << " = jetw + " << (ow.derived ? jet_rows_doubles : 0u) << "u + q * " << jet_sys(ow)
+                << "u + hy_utbl[" << ow.col_tbl * L << "u + l];\n";
+            src << "const double *const " << (ow.derived ? "x0r" : "jr") << ow.col << " = " << nm << ";\n";
+            return;
+        }
         src << "const bool ovalid" << ow.col << " = l < " << gr.n_valid << "u;\n";
         if (ow.derived) {
             // (Current values of the derived variables: after the jet rows of the wavefront. One pointer for
@@ -1628,6 +1694,21 @@ void cluster2_gen::text_kernel_prologue()
         src << "const double *const jr" << ow.col << " = jetw + q * " << n_colp << "u + " << ow.cbase
             << "u + (ovalid" << ow.col << " ? l : 0u);\n";
     });
+    // Lane-reduced sums: the pointers of the packed final evaluation (pack_tail_slot()) are formed once here instead of in
+    // every step - three table lookups in LDS and their address arithmetic per step; the registers are the ones the
+    // operand table of the second round used to hold.
+    for (const auto &[col, tb] : pk_tbl) {
+        if (!lane_sum) {
+            break;
+        }
+        for_each_owner([&, col = col, tb = tb](auto &, auto &ow) {
+            if (ow.col == col) {
+                src << "const double *const pk_jh" << col << " = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[1] * L << "u + l];\n";
+                src << "const double *const pk_fh" << col << " = lds_fac + hy_utbl[" << tb[2] * L << "u + l];\n";
+                src << "double *const pk_v" << col << " = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[0] * L << "u + l];\n";
+            }
+        });
+    }
     // Lane slots of the final evaluation: slot h, lane l <-> jet column h * L + l (dummy column beyond the last one).
     for (std::uint32_t h = 0; !one_lane && h < n_hslots; ++h) {
         src << "double *const hc" << h << " = jetw + q * " << n_colp << "u + ((" << h * L << "u + l < " << n_col << "u) ? "
@@ -2047,8 +2128,10 @@ void cluster2_gen::text_selector()
             if (tp.packed) {
                 // (Row k of the lane's series at pk_jh[(k - 1) * stride], its factor at pk_fh[k]: see the pass below.)
                 const auto &tb = pk_tbl.at(tp.ow->col);
-                src << "const double *const pk_jh" << cs << " = jetw + q * " << jet_sys(*tp.ow) << "u + hy_utbl[" << tb[1] * L << "u + l];\n";
-                src << "const double *const pk_fh" << cs << " = lds_fac + hy_utbl[" << tb[2] * L << "u + l];\n";
+                if (!lane_sum) {
+                    src << "const double *const pk_jh" << cs << " = jetw + q * " << jet_sys(*tp.ow) << "u + hy_utbl[" << tb[1] * L << "u + l];\n";
+                    src << "const double *const pk_fh" << cs << " = lds_fac + hy_utbl[" << tb[2] * L << "u + l];\n";
+                }
                 tp.rows.resize(order + 1u);
                 tp.facs.resize(order + 1u);
                 for (std::uint32_t k = 1; k <= order; ++k) {
@@ -2230,7 +2313,9 @@ void cluster2_gen::text_final_evaluation_and_update()
             const auto cs = std::to_string(ow.col);
             const auto &tb = pk_tbl.at(ow.col);
             // (The current value of the lane's variable: order-0 row of the column / entry of the derived variable.)
-            src << "double *const pk_v" << cs << " = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[0] * L << "u + l];\n";
+            if (!lane_sum) {
+                src << "double *const pk_v" << cs << " = jetw + q * " << jet_sys(ow) << "u + hy_utbl[" << tb[0] * L << "u + l];\n";
+            }
             src << "double " << xn << ";\n{\n";
             // (Row k of the lane's series at pk_j[(k - 1) * stride]: the velocity column from row 1 on, from row 0
             // on for the derived series.)
@@ -2632,6 +2717,7 @@ void cluster2_gen::finish()
                 + std::to_string(n_own) + " state-variable owner slots, " + std::to_string(utbl.size())
                 + " slot tables, jets in " + (jet_lds ? "LDS" : "global scratch")
                 + (one_lane ? ", slab layout: " + std::to_string(bank_cost) + " conflict cycles per step in the model" : std::string{})
+                + (lane_sum ? ", later sums reduced across the lanes of the first round" : "")
                 + (ev_inline ? "; event equations, final step size and state update inside the stepper" : "");
 }
 

@@ -45,12 +45,17 @@ struct c2_variant {
     bool frx = false;     // one lane per pair: reactions fused into the acceleration sums (stage 0c)
     bool fuse_rx = false; // reaction fusion (both pair kernels), see anchors_and_reaction_fusion()
     bool frx_regs = false, merged = false;
+    // frx, sums of the later rounds taken from the registers of the first round's lanes by a segmented reduction over
+    // adjacent lanes instead of re-read from LDS (plan_lane_sums()).
+    bool lane_sum = false;
     // Experiment switches of this generator: ONE environment variable, HEYOKA_AMD_V5_OPTS, a comma-separated list of flags
     // (profiles/experiments/ab.py compares variants inside one process). Every flag switches OFF one of the round-5 items:
     //   nomsq     three accumulators for the half sums of squares (one per coordinate) instead of one;
     //   nopack2   the final evaluation of a partially filled owner slot as a full two-series pass;
     //   notailrd  the jet reads of the final evaluation behind the step size instead of ahead of the selector;
     //   nosc      the selector's logarithm / exponential with literal polynomial constants (hy_sel_log(), exp()).
+    //   nolanesum the sums of the rounds after the first read their operands from LDS, one round per L nodes, instead of
+    //             adding them across the lanes which hold them (plan_lane_sums()): the text of before that item.
     // (nofrx, nobkslab, nowide, novx, nostoreplace, frxlds, norx, bankdbg: where they are read.) Parsed once ('+' separates
     // flags where ',' separates variables: ab.py).
     std::set<std::string> v5_flags;
@@ -85,6 +90,12 @@ struct owner_slot {
     // order-0 entries of the derived variables (their current values).
     bool derived = false;
     std::uint32_t parent = 0; // owner slot id of the variable it is derived from
+    // Lane-reduced sums (lane_sum): lane l owns the jet column utbl[col_tbl][l] (absolute; an idle lane the column of the
+    // lane it replicates) and is valid where bit l of valid_mask is set - instead of column cbase + l for l < n_valid.
+    // reduced: the slot of a lane-reduced round (its other lanes hold partial sums).
+    bool mapped = false, reduced = false;
+    std::size_t col_tbl = 0;
+    std::uint32_t valid_mask = 0;
 };
 struct glue_round {
     std::vector<std::size_t> arg_tbl;
@@ -95,6 +106,7 @@ struct glue_round {
     std::vector<std::string> par_name; // per-lane parameter value names, by argument (empty: none)
     std::vector<std::string> c0name;   // names of the constant operands read at order 0, by argument
     std::vector<std::size_t> coef_tbl; // reaction fusion: per-lane coefficient tables, by argument (empty: not fused)
+    bool reduced = false;              // lane-reduced round: no operand reads, see emit_glue_compute()
 };
 
 // ---- Layout: anchors and owners, slab slots, wide-read / bank-model / bk placement decisions, rounds, jets. ----
@@ -119,6 +131,12 @@ struct c2_layout {
     std::vector<std::array<std::uint32_t, 3>> bodies; // position variables (x, y, z) of every body
     std::vector<std::uint32_t> node_coord, node_rank;   // per node of the glue group
     std::uint32_t n_rank = 0, n_args = 0;
+    // Lane-reduced sums (lane_sum, plan_lane_sums()): index in the sum group of the node which lane l computes in the first
+    // round (ls_first) and receives from the reduction (ls_last; ~0u: none), and the operand position of the first-round
+    // sums whose register holds the terms; ls_park: the first-round node on whose jet column a lane without a later sum parks
+    // its store of the reduced round.
+    std::vector<std::uint32_t> ls_first, ls_last, ls_park;
+    std::uint32_t ls_pos = 0;
     // LDS layout (doubles): buf_stride between the two parity buffers, slab_stride per system.
     std::uint32_t dummy_base = 0, n_slots_tot = 0, buf_stride = 0, slab_stride = 0;
     std::vector<std::vector<glue_round>> rounds;
@@ -244,7 +262,11 @@ struct cluster2_gen : c2_variant, c2_geometry, c2_layout, c2_tables, c2_emit {
         text_helpers_and_constant_tables(), text_kernel_prologue(), text_event_equations(), text_pickup(), text_selector(),
         text_event_exclusion(), text_final_evaluation_and_update(), text_refill_and_tail(), finish();
     // Parts of plan_and_select_variant() and of layout_one_lane().
-    void number_glue_slots(std::uint32_t ns), place_wide_read_slots();
+    void number_glue_slots(std::uint32_t ns), place_wide_read_slots(), plan_lane_sums(std::uint32_t n_first), renumber_sv_slots();
+    // The rounds of a glue group and the node (index in the group) which lane l computes in round r; false: the lane has
+    // no node of its own there and replicates that one. (One round per L nodes in order, unless lane_sum arranges them.)
+    std::uint32_t n_rounds_of(std::size_t g) const;
+    std::pair<std::uint32_t, bool> round_node(std::size_t g, std::uint32_t r, std::uint32_t l) const;
     template <typename F>
     void for_each_owner(F &&f) // f(glue round, owner slot), in the order of the rounds
     {

@@ -370,6 +370,131 @@ void cluster2_gen::place_wide_read_slots()
     }
 }
 
+// Lane-reduced sums (stage 0c, after frx has put the plain sums last). With the reactions fused, a first-round sum reads
+// the raw direct product of a pair and scales it itself - so the terms of a plain sum of the later rounds sit, unscaled,
+// in a register of the first-round lanes which read them, and the sum can be formed by additions across those lanes
+// instead of LDS reads (5 reads, a fifth of the reads of an order for the outer Solar System). Applies when every later
+// sum has 5 terms, each term is read by exactly one first-round sum at ONE common operand position, and the first-round
+// sums can be put on the lanes so that the holders of every later sum are 5 adjacent lanes of one 16-lane row in its
+// argument order: three row_shr steps on that one register (emit_glue_compute()) then reproduce the pairwise tree
+// ((t0 + t1) + (t2 + t3)) + t4 on the last lane of each segment - all the later sums at once. Anything else declines
+// (no per-lane operand select, no other term count). Leaves lane_sum, ls_first, ls_last, ls_pos.
+void cluster2_gen::plan_lane_sums(std::uint32_t n_first)
+{
+    constexpr std::uint32_t n_terms = 5;
+    const auto &nodes = pl.groups[0].nodes;
+    const auto n_nodes = static_cast<std::uint32_t>(nodes.size());
+    if (n_nodes <= L || n_first >= n_nodes || n_first > L) {
+        return;
+    }
+    // (What a sum reads in the place of a cluster output: the direct product.)
+    std::map<std::uint32_t, std::uint32_t> raw_of;
+    for (std::uint32_t c = 0; c < nc; ++c) {
+        for (std::uint32_t i = 0; i < 3u; ++i) {
+            raw_of[pl.clusters[c][pp.pr[i]]] = pl.clusters[c][pp.pr[i]];
+            raw_of[pl.clusters[c][static_cast<std::uint32_t>(pp.rx[i])]] = pl.clusters[c][pp.pr[i]];
+        }
+    }
+    std::map<std::uint32_t, std::pair<std::uint32_t, std::uint32_t>> holder; // product -> (first-round node, operand position)
+    std::set<std::uint32_t> shared;
+    for (std::uint32_t j = 0; j < n_first; ++j) {
+        const auto &args = p.nodes[nodes[j] - n_eq].args;
+        for (std::uint32_t a = 0; a < args.size(); ++a) {
+            const auto u = raw_of.at(args[a].idx);
+            if (!holder.emplace(u, std::make_pair(j, a)).second) {
+                shared.insert(u);
+            }
+        }
+    }
+    std::vector<std::uint32_t> first_lanes, last_lanes;
+    std::vector<char> taken(n_first, 0);
+    std::uint32_t pos = ~0u;
+    for (std::uint32_t j = n_first; j < n_nodes; ++j) {
+        const auto &args = p.nodes[nodes[j] - n_eq].args;
+        const auto l0 = static_cast<std::uint32_t>(first_lanes.size());
+        if (args.size() != n_terms || l0 % 16u + n_terms > std::min(L, 16u)) {
+            return;
+        }
+        for (const auto &o : args) {
+            const auto it = holder.find(o.idx);
+            if (it == holder.end() || shared.count(o.idx) != 0u || taken[it->second.first] != 0
+                || (pos != ~0u && it->second.second != pos)) {
+                return;
+            }
+            pos = it->second.second;
+            taken[it->second.first] = 1;
+            first_lanes.push_back(it->second.first);
+        }
+        last_lanes.push_back(l0 + n_terms - 1u);
+    }
+    for (std::uint32_t j = 0; j < n_first; ++j) {
+        if (taken[j] == 0) {
+            first_lanes.push_back(j);
+        }
+    }
+    ls_first.assign(L, ~0u);
+    ls_last.assign(L, ~0u);
+    std::copy(first_lanes.begin(), first_lanes.end(), ls_first.begin());
+    for (std::size_t s = 0; s < last_lanes.size(); ++s) {
+        ls_last[last_lanes[s]] = n_first + static_cast<std::uint32_t>(s);
+    }
+    ls_pos = pos;
+    // Where a lane without a later sum parks the store of that round: a column of the first round - the store of the first
+    // round, issued behind it, overwrites every one of them. Its own, unless the bank pair of that column (column mod 16: a
+    // ds_write_b64 is serviced per 16 lanes, the lanes of a system share the offset of its row) is the one of a later sum's
+    // column or already taken: then a free one.
+    ls_park.assign(L, ~0u);
+    std::set<std::uint32_t> banks;
+    for (const auto j : ls_last) {
+        if (j != ~0u) {
+            banks.insert(j % 16u);
+        }
+    }
+    for (std::uint32_t l = 0; l < L; ++l) {
+        if (ls_last[l] == ~0u && ls_first[l] != ~0u && banks.insert(ls_first[l] % 16u).second) {
+            ls_park[l] = ls_first[l];
+        }
+    }
+    for (std::uint32_t l = 0; l < L; ++l) {
+        for (std::uint32_t j = 0; ls_last[l] == ~0u && ls_park[l] == ~0u && j < n_first; ++j) {
+            if (banks.insert(j % 16u).second) {
+                ls_park[l] = j;
+            }
+        }
+        if (ls_last[l] == ~0u && ls_park[l] == ~0u) {
+            ls_park[l] = ls_first[l] != ~0u ? ls_first[l] : ls_first[0];
+        }
+    }
+    // The invariant the parked stores rest on: every parked column is the column of a lane which owns a first-round node,
+    // i.e. one which the store of the first round - emitted behind the reduced round's, emit_step_body() - writes at every order.
+    for (std::uint32_t l = 0; l < L; ++l) {
+        if (ls_last[l] == ~0u && std::find(first_lanes.begin(), first_lanes.end(), ls_park[l]) == first_lanes.end()) {
+            throw std::logic_error("hy_taylor (one lane per pair): a store of the lane-reduced round is parked on a column which "
+                                   "the first round does not overwrite");
+        }
+    }
+    lane_sum = true;
+}
+
+std::uint32_t cluster2_gen::n_rounds_of(std::size_t g) const
+{
+    return (lane_sum && g == 0u) ? 2u : (static_cast<std::uint32_t>(pl.groups[g].nodes.size()) + L - 1u) / L;
+}
+
+std::pair<std::uint32_t, bool> cluster2_gen::round_node(std::size_t g, std::uint32_t r, std::uint32_t l) const
+{
+    if (lane_sum && g == 0u) {
+        // (A lane without a later sum replicates a first-round node there - ls_park -, the idle lanes of the first round lane 0.)
+        if (r == 1u) {
+            return ls_last[l] != ~0u ? std::make_pair(ls_last[l], true) : std::make_pair(ls_park[l], false);
+        }
+        return ls_first[l] != ~0u ? std::make_pair(ls_first[l], true) : std::make_pair(ls_first[0], false);
+    }
+    const auto n_nodes = static_cast<std::uint32_t>(pl.groups[g].nodes.size());
+    const auto j = r * L + l;
+    return j < n_nodes ? std::make_pair(j, true) : std::make_pair(r * L, false);
+}
+
 // ---- 3. Tables. ----
 std::size_t cluster2_gen::add_utbl(std::vector<std::uint32_t> v, bool is_slot)
 {

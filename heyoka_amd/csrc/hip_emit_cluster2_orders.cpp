@@ -28,7 +28,11 @@ void cluster2_gen::publish_sv(owner_slot &ow, std::uint32_t k, const std::string
     }
     // NOTE: the idle lanes of a partially filled slot hold a copy of a valid lane's coefficient: harmless in a maximum.
     const char *acc = (k == 0u) ? "m0" : (k == order ? "mo" : (k == order - 1u ? "mom1" : nullptr));
-    if (acc != nullptr) {
+    if (acc != nullptr && ow.reduced && k != 0u) {
+        // (Lane-reduced round: the lanes without a sum hold partial sums, which stay out of the norms - a select at the
+        // two orders which enter them.)
+        os << acc << " = hy_nmax(" << acc << ", fabs(ovalid" << ow.col << " ? " << name << " : 0.0));\n";
+    } else if (acc != nullptr) {
         os << acc << " = hy_nmax(" << acc << ", fabs(" << name << "));\n";
     }
 }
@@ -50,7 +54,7 @@ std::vector<std::string> cluster2_gen::emit_glue_reads(std::size_t g, std::uint3
     auto &gr = rounds[g][r];
     const auto &n0 = p.nodes[grp.nodes[0] - n_eq];
     std::vector<std::string> names(n0.args.size());
-    for (std::size_t a = 0; a < n0.args.size(); ++a) {
+    for (std::size_t a = 0; a < n0.args.size() && !gr.reduced; ++a) {
         if (wide_rd && a + 1u < n0.args.size() && a % 2u == 0u) {
             // (Operands a, a + 1 of the sum: adjacent slots of the node's operand array.)
             const auto w = wide_read(utname(gr.arg_tbl[a]));
@@ -75,7 +79,21 @@ void cluster2_gen::emit_glue_compute(std::size_t g, std::uint32_t r, std::uint32
     const auto saved = e.numpar_override;
     std::vector<std::pair<std::uint32_t, std::string>> saved_vals, saved_vals0;
     std::string fused_val;
-    if (!gr.coef_tbl.empty()) {
+    if (gr.reduced) {
+        // Lane-reduced round (plan_lane_sums()): names[0] is the register of the first round which holds, on the five
+        // adjacent lanes of a segment, the terms t0 .. t4 of a sum. Three row_shr steps leave ((t0 + t1) + (t2 + t3)) + t4,
+        // the pairwise tree of the sum rule (additions commute: bit for bit), on the LAST lane of every segment:
+        //   a = t + shr1(t)   lane 1: t1 + t0, lane 3: t3 + t2
+        //   b = a + shr2(a)   lane 3: (t3 + t2) + (t1 + t0)
+        //   c = t + shr1(b)   lane 4: t4 + b3
+        // The other lanes end with partial sums, mixtures across segments or (row starts) whatever an out-of-row fetch
+        // yields - zeros on the hardware (hy_dpp sets bound_ctrl), the lanes wrapped around the row under the emulator of
+        // tests/emu -: none of it reaches a result (their stores: emit_step_body(), the norms: publish_sv()).
+        const auto &t = names.at(0);
+        const auto sa = e.def(t + " + hy_dpp<0x111>(" + t + ")");
+        const auto sb = e.def(sa + " + hy_dpp<0x112>(" + sa + ")");
+        fused_val = e.def(t + " + hy_dpp<0x111>(" + sb + ")");
+    } else if (!gr.coef_tbl.empty()) {
         // Sum of scaled products, pairwise like the sum rule: ((t0 + t1) + (t2 + t3)) + ..., t_i = c_i * p_i, the
         // first product of every pair fused into the addition.
         std::vector<std::string> terms;
