@@ -61,6 +61,8 @@ __all__ = [
     "native_event_counter",
     "native_event_recorder",
     "event_action",
+    "step_action",
+    "step_action_source",
     "event_log",
     "callback",
     "diff",
@@ -1072,6 +1074,61 @@ class event_action:
         return True
 
 
+class step_action:
+    """A step callback which lives in the library (an MI355X extension: the reference has no counterpart) and is defined by
+    assignments ``state variable <- expression`` and an optional stop condition instead of Python code:
+    ``ta.propagate_until(t, callback=step_action({v: 0.999 * v}, stop_when=gt(x * x + v * v, 4.0)))``. ``assignments``: a
+    dict, or a list of (variable, expression) pairs, which keeps its order; ``stop_when``: one expression; at least one of
+    the two. The expressions may read state variables, ``par[...]``, ``hy.time`` (the time after the step) and numbers,
+    and all of them - the condition included - read the state from before the action (``{x: v, v: x}`` swaps). It is
+    accepted wherever a step callback is, alone or in a list, and applied by a generated kernel over the device-resident
+    state after every sweep (``ta.last_callback_path == 4`` when every member of the callback is library-side), to the
+    systems whose last step had non-zero length; the values are bit for bit those of ``cfunc(rhs, vars=state variables)``.
+    The condition holds when its value ``c`` satisfies ``not (c == 0)``: the propagation of the batch ends with ``cb_stop``
+    like after a callback which returned False - under ``batch_semantics="independent"`` that system alone is retired with
+    the outcome ``cb_stop`` (``ta.n_stopped_by_action``) and the others carry on. Calling it with an integrator applies it
+    once and returns whether to continue."""
+
+    def __init__(self, assignments=None, stop_when=None, _handle=None):
+        if _handle is not None:
+            self._h = _handle
+            return
+        pairs = list(assignments.items()) if isinstance(assignments, dict) else [tuple(p) for p in (assignments or ())]
+        if any(len(p) != 2 for p in pairs):
+            raise ValueError("step_action takes a dict or a list of (state variable, expression) pairs")
+        lhs, larr = _handle_array([p[0] for p in pairs])
+        rhs, rarr = _handle_array([p[1] for p in pairs])
+        cond = None if stop_when is None else _as_ex(stop_when)
+        self._h = check_handle(lib.hy_step_action_new(larr, rarr, len(pairs), None if cond is None else cond._h))
+
+    def __del__(self, _free=lib.hy_step_action_free):
+        h = getattr(self, "_h", None)
+        if h:
+            _free(h)
+            self._h = None
+
+    def __copy__(self):
+        return step_action(_handle=check_handle(lib.hy_step_action_clone(self._h)))
+
+    def __deepcopy__(self, memo):
+        return self.__copy__()
+
+    def __repr__(self):
+        return take_str(lib.hy_step_action_str(self._h))
+
+    def __call__(self, ta):
+        rc = lib.hy_step_action_call(ta._h, self._h)
+        if rc < 0:
+            raise_for(lib.hy_last_error_code() or 4)
+        return rc != 0
+
+
+def step_action_source(sys, action):
+    """HIP source of the module of ``action`` (kernel hy_step_action) for the system ``sys``: no integrator, no GPU."""
+    s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
+    return take_str(check_handle(lib.hy_step_action_source(s._h, action._h)))
+
+
 class _angle_reducer:
     """callback::angle_reducer (include/heyoka/callback/angle_reducer.hpp): the step callback which keeps the given state
     variables in [0, 2 pi) - ``x -= 2 pi floor(x / 2 pi)`` after every step. It lives in the library: passed as
@@ -1341,6 +1398,26 @@ class taylor_adaptive_batch:
         propagate_until() / propagate_for() / propagate_grid() which went through the sweep loop."""
         return int(lib.hy_tab_get_n_retired(self._h))
 
+    @property
+    def n_stopped_by_action(self):
+        """batch_semantics="independent": systems retired with the outcome ``cb_stop`` by the stop condition of a
+        ``step_action`` in the last propagate_*() which went through the sweep loop (not counted by ``n_retired``)."""
+        return int(lib.hy_tab_get_n_stopped_by_action(self._h))
+
+    def step_action_module(self, action):
+        """(HIP source, gfx950 code object) of the module of ``action`` (kernel hy_step_action) in this integrator:
+        checked against its system and compiled on first use."""
+        src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        raise_for(lib.hy_tab_step_action_module(self._h, action._h, ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
+        return take_str(src.value), ctypes.string_at(data.value, n.value)
+
+    @property
+    def step_action_kernel_ms(self):
+        """With the event timing on: (sum of the durations of the hy_step_action launches in ms, number of launches)."""
+        ms, n = ctypes.c_double(), ctypes.c_uint64()
+        raise_for(lib.hy_tab_step_action_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return float(ms.value), int(n.value)
+
     # ---- event log (native_event_recorder) ----
     @property
     def event_log_size(self):
@@ -1580,7 +1657,8 @@ class taylor_adaptive_batch:
     def last_callback_path(self):
         """How the step callback of the last propagate_*() ran: 0 no callback, 1 host callback after every sweep of the
         lock-step loop, 2 ``callback.angle_reducer`` on the device after every sweep (kernel hy_angle_reduce), 3 the reduction
-        fused into the propagate kernel (one launch)."""
+        fused into the propagate kernel (one launch), 4 every member of the callback is library-side (``step_action`` and
+        ``callback.angle_reducer``, at least one action) and was applied on the device after every sweep."""
         return int(lib.hy_tab_last_callback_path(self._h))
 
     @property
@@ -1729,6 +1807,7 @@ class taylor_adaptive_batch:
         # (The library's own angle_reducer: its native descriptor instead of a ctypes thunk - recognised by address.)
         native_call = ctypes.cast(lib.hy_angle_reducer_call, _lib.STEP_CALLBACK)
         native_pre = ctypes.cast(lib.hy_angle_reducer_pre_hook, _lib.STEP_PRE_HOOK)
+        action_call = ctypes.cast(lib.hy_step_action_call, _lib.STEP_CALLBACK)
 
         def make(c):
             def call(_tab, _data):
@@ -1754,6 +1833,10 @@ class taylor_adaptive_batch:
         for i, c in enumerate(cbs):
             if isinstance(c, _angle_reducer):
                 arr[i].call, arr[i].pre_hook, arr[i].user_data = native_call, native_pre, c._h
+                keep.append(c)
+                continue
+            if isinstance(c, step_action):
+                arr[i].call, arr[i].pre_hook, arr[i].user_data = action_call, _lib.STEP_PRE_HOOK(), c._h
                 keep.append(c)
                 continue
             arr[i].call, arr[i].pre_hook = make(c)

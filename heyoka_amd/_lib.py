@@ -335,6 +335,15 @@ SIGNATURES = [
     ("hy_angle_reducer_call", c_int, [c_void_p, c_void_p]),
     ("hy_angle_reducer_pre_hook", c_int, [c_void_p, c_void_p]),
     ("hy_tab_last_callback_path", c_int, [c_void_p]),
+    ("hy_step_action_new", c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("hy_step_action_clone", c_void_p, [c_void_p]),
+    ("hy_step_action_free", None, [c_void_p]),
+    ("hy_step_action_str", c_void_p, [c_void_p]),
+    ("hy_step_action_call", c_int, [c_void_p, c_void_p]),
+    ("hy_step_action_source", c_void_p, [c_void_p, c_void_p]),
+    ("hy_tab_step_action_module", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("hy_tab_get_n_stopped_by_action", ctypes.c_uint64, [c_void_p]),
+    ("hy_tab_step_action_kernel_ms", c_int, [c_void_p, c_void_p, c_void_p]),
     ("hy_tab_angle_reduce_variant_source", c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p]),
     ("hy_tab_angle_reduce_compile_seconds", c_double, [c_void_p]),
     ("hy_angle_reduce_source", c_void_p, []),

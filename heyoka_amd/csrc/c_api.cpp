@@ -27,6 +27,7 @@
 #include "hip_emit.hpp"
 #include "model.hpp"
 #include "node_rule.hpp"
+#include "step_action.hpp"
 #include "taylor_adaptive_batch.hpp"
 #include "taylor_map.hpp"
 #include "var_ode_sys.hpp"
@@ -55,6 +56,10 @@ struct hy_angle_reducer_s {
 
 struct hy_event_action_s {
     event_action act;
+};
+
+struct hy_step_action_s {
+    step_action act;
 };
 
 struct hy_cout_s {
@@ -174,11 +179,12 @@ detail::tab_core::cb_t wrap_cb(hy_tab tab, hy_step_callback cb, void *cb_data)
 }
 
 // A set of C step callbacks with optional pre-hooks (hy_step_callback_desc): every member runs at every step, the
-// results are and-ed (src/step_callback.cpp:108-127). Returns (call, pre_hook, reducer indices) for the core.
+// results are and-ed (src/step_callback.cpp:108-127). Returns (call, pre_hook, reducer indices, whether the whole
+// set is library-side with at least one step action) for the core.
 // Members whose `call` is the library's hy_angle_reducer_call are recognised by address (like hy_event_counter_nt among the
 // event callbacks): the C++ object behind the handle is used directly - its exceptions reach the caller with their
 // messages -, and when every member is one the core learns the indices they reduce (tab_core::red_t).
-std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::red_t> wrap_cbs(hy_tab tab, const hy_step_callback_desc *cbs,
+std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::red_t, bool> wrap_cbs(hy_tab tab, const hy_step_callback_desc *cbs,
                                                                                              size_t n_cbs)
 {
     if (n_cbs == 0u || (n_cbs == 1u && cbs[0].call == nullptr)) {
@@ -194,11 +200,28 @@ std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::re
         return (c.call == &hy_angle_reducer_call && c.user_data != nullptr) ? &static_cast<hy_angle_reducer>(c.user_data)->ar
                                                                             : nullptr;
     };
-    detail::tab_core::cb_t call = [tab, v, reducer_of]() {
+    // (... and the members whose `call` is hy_step_action_call: the action is applied by its kernel, at its place in the
+    // order; a set of actions and reducers with at least one action is library-side as a whole, last_callback_path 4.)
+    const auto action_of = [](const hy_step_callback_desc &c) -> step_action * {
+        return (c.call == &hy_step_action_call && c.user_data != nullptr) ? &static_cast<hy_step_action>(c.user_data)->act : nullptr;
+    };
+    for (const auto &c : v) {
+        // (The first meeting with the integrator: the checks against its system, before anything runs.)
+        if (auto *sa = action_of(c)) {
+            tab->core.prepare_step_action(*sa);
+        }
+    }
+    const bool lib_cb = std::all_of(v.begin(), v.end(), [&](const auto &c) { return reducer_of(c) != nullptr || action_of(c) != nullptr; })
+                        && std::any_of(v.begin(), v.end(), [&](const auto &c) { return action_of(c) != nullptr; });
+    detail::tab_core::cb_t call = [tab, v, reducer_of, action_of]() {
         bool ret = true;
         for (const auto &c : v) {
             if (auto *ar = reducer_of(c)) {
                 (*ar)(tab->core);
+                continue;
+            }
+            if (auto *sa = action_of(c)) {
+                ret = (*sa)(tab->core) && ret;
                 continue;
             }
             const auto rc = c.call(tab, c.user_data);
@@ -234,7 +257,7 @@ std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::re
             return std::vector<std::uint32_t>(u.begin(), u.end());
         };
     }
-    return {std::move(call), std::move(pre), std::move(red)};
+    return {std::move(call), std::move(pre), std::move(red), lib_cb};
 }
 
 } // namespace
@@ -1560,18 +1583,18 @@ int hy_tab_propagate_until_cbs(hy_tab t, const double *ts, size_t n_ts, uint64_t
                                const hy_step_callback_desc *cbs, size_t n_cbs, int wtc, int c_out)
 {
     return guarded([&] {
-        auto [call, pre, red] = wrap_cbs(t, cbs, n_cbs);
+        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
         t->core.propagate_until(vec_from(ts, n_ts), static_cast<std::size_t>(max_steps),
-                                expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red);
+                                expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red, lib_cb);
     });
 }
 int hy_tab_propagate_for_cbs(hy_tab t, const double *dts, size_t n_dts, uint64_t max_steps, const double *mdts, size_t n_mdt,
                              const hy_step_callback_desc *cbs, size_t n_cbs, int wtc, int c_out)
 {
     return guarded([&] {
-        auto [call, pre, red] = wrap_cbs(t, cbs, n_cbs);
+        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
         t->core.propagate_for(vec_from(dts, n_dts), static_cast<std::size_t>(max_steps),
-                              expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red);
+                              expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red, lib_cb);
     });
 }
 int hy_tab_propagate_grid_cbs(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
@@ -1579,9 +1602,9 @@ int hy_tab_propagate_grid_cbs(hy_tab t, const double *grid, size_t n_grid, uint6
 {
     return guarded([&] {
         const auto bs = t->core.get_batch_size();
-        auto [call, pre, red] = wrap_cbs(t, cbs, n_cbs);
+        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
         auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
-                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red);
+                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red, lib_cb);
         std::memcpy(out, ret.data(), ret.size() * sizeof(double));
     });
 }
@@ -1650,6 +1673,95 @@ int hy_angle_reducer_pre_hook(hy_tab t, void *user)
         handle_exception();
         return 1;
     }
+}
+// ---- step_action (step_action.hpp) ----
+hy_step_action hy_step_action_new(const hy_expr *vars, const hy_expr *rhs, size_t n, hy_expr stop_when)
+{
+    try {
+        std::vector<std::pair<expression, expression>> a;
+        for (size_t i = 0; i < n; ++i) {
+            a.emplace_back(vars[i]->ex, rhs[i]->ex);
+        }
+        return new hy_step_action_s{
+            step_action(std::move(a), stop_when != nullptr ? std::optional<expression>(stop_when->ex) : std::nullopt)};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+hy_step_action hy_step_action_clone(hy_step_action h)
+{
+    try {
+        return new hy_step_action_s{h->act};
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+void hy_step_action_free(hy_step_action h)
+{
+    delete h;
+}
+char *hy_step_action_str(hy_step_action h)
+{
+    try {
+        return dup_str(h->act.to_string());
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+int hy_step_action_call(hy_tab t, void *user)
+{
+    try {
+        if (user == nullptr) {
+            throw std::invalid_argument("hy_step_action_call needs a hy_step_action handle as its user pointer");
+        }
+        return (static_cast<hy_step_action>(user)->act)(t->core) ? 1 : 0;
+    } catch (...) {
+        handle_exception();
+        return -1;
+    }
+}
+char *hy_step_action_source(hy_sys sys, hy_step_action h)
+{
+    try {
+        const auto svars = detail::state_variables_of(sys->sys);
+        // (Without an integrator there is no parameter array to check against: whatever the expressions use.)
+        return dup_str(detail::make_step_action_source(
+            detail::make_step_action_section(h->act, svars, std::numeric_limits<std::uint32_t>::max())));
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+int hy_tab_step_action_module(hy_tab t, hy_step_action h, char **source, const char **data, size_t *size)
+{
+    return guarded([&] {
+        const auto &src = t->core.step_action_source(h->act);
+        const auto &co = t->core.step_action_code_object(h->act);
+        if (source != nullptr) {
+            *source = dup_str(src);
+        }
+        if (data != nullptr) {
+            *data = co.data();
+        }
+        if (size != nullptr) {
+            *size = co.size();
+        }
+    });
+}
+uint64_t hy_tab_get_n_stopped_by_action(hy_tab t)
+{
+    return t->core.get_n_stopped_by_action();
+}
+int hy_tab_step_action_kernel_ms(hy_tab t, double *ms, uint64_t *launches)
+{
+    return guarded([&] {
+        const auto [m, n] = t->core.get_step_action_kernel_ms();
+        *ms = m;
+        *launches = n;
+    });
 }
 int hy_tab_last_callback_path(hy_tab t)
 {

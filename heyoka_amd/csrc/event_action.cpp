@@ -71,6 +71,45 @@ event_action_section make_event_action_section(const event_action &act, std::uin
     return ret;
 }
 
+std::string emit_assignment_section(const taylor_program &p, const std::vector<std::uint32_t> &rows)
+{
+    std::ostringstream src;
+    const auto code = emit_order0(p, [](std::uint32_t i) { return "x" + std::to_string(i); });
+    // State rows the section reads: the operands of its elementary functions and the outputs which are plain copies.
+    std::set<std::uint32_t> reads;
+    for (const auto &n : p.nodes) {
+        for (const auto &o : n.args) {
+            if (o.type == operand::kind::uvar && o.idx < p.n_eq) {
+                reads.insert(o.idx);
+            }
+        }
+    }
+    for (const auto &d : p.sv_defs) {
+        if (d.type == operand::kind::uvar && d.idx < p.n_eq) {
+            reads.insert(d.idx);
+        }
+    }
+    for (const auto r : reads) {
+        src << "const double x" << r << " = a.state[(u64)" << r << "u * N + s];\n";
+    }
+    for (std::uint32_t i = 0; i < p.n_par; ++i) {
+        src << "const double par_" << i << " = a.pars[(u64)" << i << "u * N + s];\n";
+    }
+    if (p.time_dependent) {
+        src << "const double t_hi = a.time_hi[s];\n";
+    }
+    src << code.body;
+    // (Named results first: an output which is a plain copy of a row, or a literal, is a value of its own before any
+    // row is written.)
+    for (std::size_t o = 0; o < code.outs.size(); ++o) {
+        src << "const double r" << o << " = " << code.outs[o] << ";\n";
+    }
+    for (std::size_t o = 0; o < rows.size(); ++o) {
+        src << "a.state[(u64)" << rows[o] << "u * N + s] = r" << o << ";\n";
+    }
+    return src.str();
+}
+
 std::string make_event_action_source(const std::vector<event_action_section> &sections)
 {
     std::ostringstream src;
@@ -108,41 +147,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_ev_action(const hy_eva_args
     switch (oc) {
 )HIP";
     for (const auto &sec : sections) {
-        const auto &p = sec.prog;
-        const auto code = emit_order0(p, [](std::uint32_t i) { return "x" + std::to_string(i); });
-        // State rows the section reads: the operands of its elementary functions and the outputs which are plain copies.
-        std::set<std::uint32_t> reads;
-        for (const auto &n : p.nodes) {
-            for (const auto &o : n.args) {
-                if (o.type == operand::kind::uvar && o.idx < p.n_eq) {
-                    reads.insert(o.idx);
-                }
-            }
-        }
-        for (const auto &d : p.sv_defs) {
-            if (d.type == operand::kind::uvar && d.idx < p.n_eq) {
-                reads.insert(d.idx);
-            }
-        }
-        src << "case " << sec.te_idx << ": {\n";
-        for (const auto r : reads) {
-            src << "const double x" << r << " = a.state[(u64)" << r << "u * N + s];\n";
-        }
-        for (std::uint32_t i = 0; i < p.n_par; ++i) {
-            src << "const double par_" << i << " = a.pars[(u64)" << i << "u * N + s];\n";
-        }
-        if (p.time_dependent) {
-            src << "const double t_hi = a.time_hi[s];\n";
-        }
-        src << code.body;
-        // (Named results first: an output which is a plain copy of a row, or a literal, is a value of its own before any
-        // row is written.)
-        for (std::size_t o = 0; o < code.outs.size(); ++o) {
-            src << "const double r" << o << " = " << code.outs[o] << ";\n";
-        }
-        for (std::size_t o = 0; o < code.outs.size(); ++o) {
-            src << "a.state[(u64)" << sec.rows[o] << "u * N + s] = r" << o << ";\n";
-        }
+        src << "case " << sec.te_idx << ": {\n" << emit_assignment_section(sec.prog, sec.rows);
         src << "break;\n}\n";
     }
     src << "default:\nbreak;\n}\n}\n";

@@ -76,11 +76,13 @@ __device__ __forceinline__ bool hy_indep_retired(const hy_grid_args &a, u64 i)
     a.lim[i] = 0.0;
     // (Frozen cooldowns: a zero-length step ages a cooldown by nothing, but it ends one of duration zero - the one the
     // retiring event may have set.)
-    if (so != HY_OC_ERR_NF_STATE && a.cd_active != nullptr) {
+    // (so > HY_OC_SUCCESS: a stopping terminal event. A system retired by a step_action carries cb_stop: no event, no cooldown,
+    // and it is counted by the action's own counter.)
+    if (so > HY_OC_SUCCESS && a.cd_active != nullptr) {
         const u64 p = (u64)(-so - 1) * a.N + i;
         if (a.cd_second[p] == 0.0) a.cd_active[p] = 1;
     }
-    hy_count(a.counters + 4, so != HY_OC_ERR_NF_STATE);
+    hy_count(a.counters + 4, so > HY_OC_SUCCESS);
     hy_count(a.counters + 5, so == HY_OC_ERR_NF_STATE);
     return true;
 }

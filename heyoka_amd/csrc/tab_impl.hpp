@@ -25,6 +25,7 @@
 #include "hip_backend.hpp"
 #include "hip_emit.hpp"
 #include "hip_emit_detail.hpp"
+#include "step_action.hpp"
 
 namespace heyoka_amd::detail
 {
@@ -256,6 +257,41 @@ struct tab_core::impl {
     // The callback of the running propagate_*() is a pure angle_reducer (set); how the callback of the last one ran.
     bool cb_is_reducer = false;
     int last_cb_path = 0;
+    // ---- step_action (step_action.hpp) ----
+    // The modules of the actions this integrator has met, keyed by the text of the action: checked against the system,
+    // generated and compiled on first use (the code objects live in the process-wide cache), loaded at the first launch.
+    struct sa_variant {
+        step_action_section sec;
+        std::string source;
+        std::shared_ptr<const compiled_module> cm;
+        std::unique_ptr<aux_module> dm;
+    };
+    std::map<std::string, sa_variant> sa_variants;
+    sa_variant &get_sa_variant(const step_action &act)
+    {
+        const auto key = act.to_string();
+        auto it = sa_variants.find(key);
+        if (it == sa_variants.end()) {
+            sa_variant v;
+            v.sec = make_step_action_section(act, state_variables_of(sys), prog.n_par);
+            v.source = make_step_action_source(v.sec);
+            const detail::stopwatch sw;
+            v.cm = hiprtc_compile_source(v.source);
+            detail::log_message(log_level::trace, "step_action: kernel compilation runtime: " + sw.str());
+            it = sa_variants.emplace(key, std::move(v)).first;
+        }
+        return it->second;
+    }
+    // The counter of the stop condition; systems retired by it in the running / last sweep loop; the grid indices of the
+    // running propagate_grid() loop (a system retired by the action is through its grid); every member of the callback of
+    // the running propagate_*() is library-side, with at least one action; accounting of the timed launches.
+    device_buffer d_sa_cnt;
+    std::uint64_t n_stopped_by_action = 0;
+    unsigned *sa_gidx = nullptr;
+    unsigned sa_n_grid = 0;
+    bool cb_is_library = false;
+    double sa_ms = 0;
+    std::uint64_t sa_timed = 0;
     ar_variant &get_ar_variant(const std::vector<std::uint32_t> &idx)
     {
         auto it = ar_variants.find(idx);
@@ -539,6 +575,7 @@ struct tab_core::impl {
     {
         n_retired = 0;
         n_retired_nf = 0;
+        n_stopped_by_action = 0;
         long long *r = nullptr;
         if (batch_semantics == 3) {
             if (d_retired.bytes() != N * sizeof(long long)) {

@@ -96,7 +96,7 @@ void tab_core::finish_device_propagate(const std::vector<double> &ts, std::size_
 
 void tab_core::propagate_for(const std::vector<double> &delta_ts, std::size_t max_steps,
                              const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                             const pre_t &pre, const red_t &red)
+                             const pre_t &pre, const red_t &red, bool lib_cb)
 {
     auto &d = *m_impl;
     if (delta_ts.size() != 1u && delta_ts.size() != d.N) {
@@ -116,18 +116,20 @@ void tab_core::propagate_for(const std::vector<double> &delta_ts, std::size_t ma
     // NOTE: double-length final times travel as a vector of size 2 * N: a form accepted only from here (a public
     // propagate_until() call with any size other than N throws like the reference).
     const scoped_value<bool> guard(d.dl_times_ok, true);
-    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, c_out, pre, red);
+    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, c_out, pre, red, lib_cb);
 }
 
 // Reference: propagate_until_impl(), src/taylor_adaptive_batch.cpp:1137-1534.
 void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_steps,
                                const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                               const pre_t &pre, const red_t &red)
+                               const pre_t &pre, const red_t &red, bool lib_cb)
 {
     auto &d = *m_impl;
     const auto N = d.N;
+    d.cb_is_library = cb && lib_cb;
     d.n_retired = 0;
     d.n_retired_nf = 0;
+    d.n_stopped_by_action = 0;
     // (The re-run of a rolled-back fused propagation keeps the kind of its callback.)
     if (!d.force_lockstep) {
         d.cb_is_reducer = cb && red;
@@ -253,7 +255,11 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
     // continuous output: the reference's loop, one single-step kernel launch per iteration.
     // The pre_hook() of the step callback, once, before the first step (src/taylor_adaptive_batch.cpp:1356-1365).
     if (cb) {
-        d.last_cb_path = d.cb_is_reducer ? 2 : 1;
+        d.last_cb_path = d.cb_is_library ? 4 : (d.cb_is_reducer ? 2 : 1);
+        if (d.cb_is_library) {
+            detail::log_message(log_level::info, "propagate_until(): library-side step callback (step_action) applied by its kernel after "
+                                                 "every sweep of the lock-step loop: fusing it into the propagate kernel is not implemented");
+        }
         if (d.cb_is_reducer && !pre_done && !d.force_lockstep) {
             detail::log_message(log_level::info,
                                 "propagate_until(): angle_reducer applied by hy_angle_reduce after every sweep of the lock-step loop ("
@@ -479,6 +485,9 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     // Independent semantics: see the loop of propagate_until(). A retired system keeps the samples of its last step, its
     // remaining rows stay NaN and its grid index goes to the end (hy_grid_post).
     const auto sw = d.start_retirement();
+    // (A system retired by a step_action is through its grid.)
+    const scoped_value<unsigned *> sa_gidx_guard(d.sa_gidx, b_gidx.as<unsigned>());
+    const scoped_value<unsigned> sa_ngrid_guard(d.sa_n_grid, n_grid);
     while (n_grid > 1u) {
         // (The sweep after which max_steps ends the loop stores the coefficients of EVERY lane: the reference leaves the
         // Taylor coefficients of the last step behind, src/taylor_adaptive_batch.cpp:1546-2055.)
@@ -608,7 +617,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
 // grid[point * N + lane]; return value ret[(point * dim + var) * N + lane], NaN where not reached.
 std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                              const std::vector<double> &max_delta_ts_, const cb_t &cb, double *d_out,
-                                             const pre_t &pre, const red_t &red)
+                                             const pre_t &pre, const red_t &red, bool lib_cb)
 {
     auto &d = *m_impl;
     const auto N = d.N;
@@ -728,7 +737,8 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     // output at the grid points covered by the step, next step limit) alternate without any per-lane host work; the host
     // reads three counters per sweep and runs the callback, if any.
     // (A pure angle_reducer callback runs hy_angle_reduce after every sweep: no fused grid launches.)
-    d.last_cb_path = cb ? (red ? 2 : 1) : 0;
+    d.cb_is_library = cb && lib_cb;
+    d.last_cb_path = cb ? (d.cb_is_library ? 4 : (red ? 2 : 1)) : 0;
     propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb);
     return retval;
 }
@@ -772,6 +782,105 @@ void tab_core::angle_reduce(const std::vector<std::uint32_t> &idx)
     if (d.sticky_const_refs) {
         d.to_host();
     }
+}
+
+// ---- step_action ----
+bool tab_core::apply_step_action(const step_action &act)
+{
+    auto &d = *m_impl;
+    // (The checks against the system, the first time; the kernel from then on.)
+    auto &var = d.get_sa_variant(act);
+    // The state is never downloaded: when the host mirror is the newer copy (or a mutable pointer to it is out) it is
+    // uploaded first, like before any kernel. A device which has not run a step yet holds no last_h: the mirror's.
+    const bool fresh_device = !d.dmod;
+    const bool upload = d.host_newer || d.sticky_host_ptr || fresh_device;
+    if (fresh_device || !d.lasth_dev_newer) {
+        // (No step since the mirror of last_h was made current - a fresh integrator, a copy, a move to another device: the
+        // device array may never have been written.)
+        (void)get_last_h();
+        if (std::all_of(d.last_h.begin(), d.last_h.end(), [](double h) { return h == 0.; })) {
+            detail::log_message(log_level::debug, "step_action: no system has taken a step of non-zero length, nothing to do");
+            return true;
+        }
+    }
+    d.before_kernel();
+    if (fresh_device || !d.lasth_dev_newer) {
+        d.d_lasth.upload(d.last_h.data(), d.last_h.size() * sizeof(double), d.stream);
+    }
+    if (detail::log_enabled(log_level::debug)) {
+        detail::log_message(log_level::debug, std::string("step_action: kernel hy_step_action over the device-resident state (")
+                                                  + (upload ? "the host mirror was the newer copy: uploaded first"
+                                                            : "the device copy was current: nothing moved")
+                                                  + ")");
+    }
+    if (!var.dm) {
+        var.dm = std::make_unique<aux_module>(var.cm, d.device);
+    }
+    const bool cond = var.sec.has_cond;
+    const bool indep = cond && d.retired_ptr != nullptr;
+    if (cond) {
+        if (d.d_sa_cnt.bytes() == 0u) {
+            d.d_sa_cnt = device_buffer(sizeof(unsigned), d.device);
+        }
+        d.d_sa_cnt.zero(d.stream);
+    }
+    const sa_kargs a{d.d_lasth.as<double>(),
+                     d.d_state.as<double>(),
+                     d.d_pars.as<double>(),
+                     d.d_thi.as<double>(),
+                     cond ? d.d_sa_cnt.as<unsigned>() : nullptr,
+                     indep ? d.d_retired.as<long long>() : nullptr,
+                     indep ? d.d_outcome.as<long long>() : nullptr,
+                     indep ? d.d_lim.as<double>() : nullptr,
+                     indep ? d.sa_gidx : nullptr,
+                     d.N,
+                     d.sa_n_grid,
+                     0u};
+    if (d.ev_timing) {
+        d.sa_ms += var.dm->launch_timed("hy_step_action", d.N, 256, &a, sizeof(a), d.stream);
+        ++d.sa_timed;
+    } else {
+        var.dm->launch("hy_step_action", d.N, 256, &a, sizeof(a), d.stream);
+    }
+    // The device copy of the state is the newer one; the mirrors somebody holds follow, as after any kernel.
+    d.dev_newer = true;
+    d.refresh_held_mirrors();
+    if (!cond) {
+        return true;
+    }
+    unsigned n_stop = 0;
+    d.d_sa_cnt.download(&n_stop, sizeof(unsigned), d.stream);
+    if (indep) {
+        // (The systems were retired on their own: the loop carries on.)
+        d.n_stopped_by_action += n_stop;
+        return true;
+    }
+    return n_stop == 0u;
+}
+
+void tab_core::prepare_step_action(const step_action &act)
+{
+    (void)m_impl->get_sa_variant(act);
+}
+
+std::uint64_t tab_core::get_n_stopped_by_action() const
+{
+    return m_impl->n_stopped_by_action;
+}
+
+const std::string &tab_core::step_action_source(const step_action &act)
+{
+    return m_impl->get_sa_variant(act).source;
+}
+
+const std::vector<char> &tab_core::step_action_code_object(const step_action &act)
+{
+    return m_impl->get_sa_variant(act).cm->code;
+}
+
+std::pair<double, std::uint64_t> tab_core::get_step_action_kernel_ms() const
+{
+    return {m_impl->sa_ms, m_impl->sa_timed};
 }
 
 int tab_core::get_last_callback_path() const

@@ -899,6 +899,11 @@ void tab_core::set_device(int device)
     d.evr_mod.reset();
     d.drow_mod.reset();
     d.act_mod.reset();
+    for (auto &[k, v] : d.sa_variants) {
+        (void)k;
+        v.dm.reset();
+    }
+    d.d_sa_cnt = {};
     d.d_ev_log = {};
     d.d_evr_isrec = {};
     d.d_evr_lane = {};

@@ -76,6 +76,7 @@ inline std::ostream &operator<<(std::ostream &os, taylor_outcome oc)
 
 template <typename T>
 class taylor_adaptive_batch;
+class step_action;
 
 // Type-erased step callback bool(taylor_adaptive_batch<T> &) with the optional pre_hook() member, and sets of them
 // (reference: include/heyoka/step_callback.hpp:46-62, :139-185) - step_callback.hpp.
@@ -215,21 +216,42 @@ public:
     // update - one launch, cb is not invoked - whenever there is no continuous output, there are no events and the generator
     // of the stepper implements the variant; otherwise cb runs after every sweep of the lock-step loop as usual.
     using red_t = std::function<std::vector<std::uint32_t>()>;
+    // lib_cb: every member of the callback is a step_action (step_action.hpp) or an angle_reducer, with at least one action -
+    // cb applies all of them on the device (get_last_callback_path() == 4).
     void propagate_until(const std::vector<double> &ts, std::size_t max_steps, const std::vector<double> &max_delta_ts,
-                         const cb_t &cb, bool wtc, bool c_out, const pre_t &pre = {}, const red_t &red = {});
+                         const cb_t &cb, bool wtc, bool c_out, const pre_t &pre = {}, const red_t &red = {}, bool lib_cb = false);
     void propagate_for(const std::vector<double> &delta_ts, std::size_t max_steps,
                        const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                       const pre_t &pre = {}, const red_t &red = {});
+                       const pre_t &pre = {}, const red_t &red = {}, bool lib_cb = false);
     std::vector<double> propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                        const std::vector<double> &max_delta_ts, const cb_t &cb,
-                                       double *d_out = nullptr, const pre_t &pre = {}, const red_t &red = {});
+                                       double *d_out = nullptr, const pre_t &pre = {}, const red_t &red = {},
+                                       bool lib_cb = false);
     // x -= 2 pi floor(x / 2 pi) on the state variables idx (sorted, < get_dim()) of every system - what the call operator
     // of callback::angle_reducer does: kernel hy_angle_reduce on the integrator's stream over the device-resident state
     // (no download, no switch to eager synchronisation), or on the host mirror when that is the newer copy.
     void angle_reduce(const std::vector<std::uint32_t> &idx);
     // How the step callback of the last propagate_*() ran: 0 no callback, 1 host callback after every sweep, 2 a pure
     // angle_reducer callback after every sweep (hy_angle_reduce), 3 fused into the propagate kernel.
+    // (... 4: every member of the callback is library-side - step_actions and angle_reducers, at least one action - and
+    // was applied on the device after every sweep)
     [[nodiscard]] int get_last_callback_path() const;
+    // ---- step_action (step_action.hpp) ----
+    // What the call operator of a step_action does: the checks against the system at the first meeting, then the kernel
+    // hy_step_action of that action over the device-resident state (the host mirror is uploaded first when it is the newer
+    // copy). Returns false when the stop condition held for a system it acted on - except inside a sweep loop under the
+    // independent semantics, where those systems are retired with the sticky outcome cb_stop and the call returns true.
+    bool apply_step_action(const step_action &act);
+    // The first meeting alone: the checks against the system and the compilation of the kernel. No GPU is needed.
+    void prepare_step_action(const step_action &act);
+    // Systems retired by the stop condition of a step_action in the last call which went through a sweep loop
+    // (config::batch_semantics == 3; they are not counted by get_n_retired()).
+    [[nodiscard]] std::uint64_t get_n_stopped_by_action() const;
+    // HIP source and gfx950 code object of the module of an action for this integrator (compiled on first use; no GPU needed).
+    [[nodiscard]] const std::string &step_action_source(const step_action &act);
+    [[nodiscard]] const std::vector<char> &step_action_code_object(const step_action &act);
+    // With set_event_timing(true): (sum of the durations of the hy_step_action launches in ms, number of timed launches).
+    [[nodiscard]] std::pair<double, std::uint64_t> get_step_action_kernel_ms() const;
     // HIP source of the stepper variant with the reduction of idx fused in (empty + the reason if the generator declines),
     // and the seconds its last compilation took (0: never compiled / cached).
     [[nodiscard]] std::string get_angle_reduce_variant_source(const std::vector<std::uint32_t> &idx, std::string &why_not) const;
@@ -356,6 +378,14 @@ std::vector<double> make_vector_from(double x);
 // function which returns the sorted union of their indices (tab_core::red_t, to be called after the pre_hook());
 // empty otherwise. Defined in angle_reducer.cpp.
 tab_core::red_t angle_reducer_indices_of(step_cb_wrap<taylor_adaptive_batch<double>> &cb);
+// cb holds a step_action (step_action.hpp), or a set whose members all are step_actions or callback::angle_reducers with
+// at least one action: every member is applied on the device (the lib_cb argument of tab_core::propagate_*()). Defined in
+// step_action.cpp.
+bool callback_is_library_action(const step_cb_wrap<taylor_adaptive_batch<double>> &cb);
+// What a front end does with the callback of a propagate_*() before it calls the core: the step_actions in it, at any depth
+// of nested sets, meet the integrator (tab_core::prepare_step_action(): std::invalid_argument before anything runs).
+// Returns callback_is_library_action(cb), false for an empty cb: the lib_cb argument of the core.
+bool prepare_step_actions(tab_core &core, const step_cb_wrap<taylor_adaptive_batch<double>> &cb);
 
 // HIP source of the post-step kernel of the device-resident propagate_grid() loop (exposed for the build-time
 // compilation check).
@@ -666,10 +696,12 @@ class taylor_adaptive_batch<double>
             // (The library's own angle_reducer is recognised by type: the core may apply it inside the propagate kernel.)
             red = detail::angle_reducer_indices_of(*user_cb);
         }
+        // (The step_actions in the callback meet the integrator now; lib: the whole callback is library-side.)
+        const bool lib = detail::prepare_step_actions(m_core, *user_cb);
         const auto wtc = static_cast<bool>(kw::get(kw::write_tc, false, kw_args...));
         const auto c_out = static_cast<bool>(kw::get(kw::c_output, false, kw_args...));
         return std::tuple{max_steps, std::move(max_delta_ts), std::move(cb), std::move(user_cb), wtc, c_out, std::move(pre),
-                          std::move(red)};
+                          std::move(red), lib};
     }
 
 public:
@@ -1015,43 +1047,43 @@ public:
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_until(const std::vector<double> &ts,
                                                                            KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_until(ts, max_steps, mdts, cb, wtc, c_out, pre, red);
+        m_core.propagate_until(ts, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_until(double t, KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_until(std::vector<double>{t}, max_steps, mdts, cb, wtc, c_out, pre, red);
+        m_core.propagate_until(std::vector<double>{t}, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_for(const std::vector<double> &dts,
                                                                          KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_for(dts, max_steps, mdts, cb, wtc, c_out, pre, red);
+        m_core.propagate_for(dts, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_for(double dt, KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_for(std::vector<double>{dt}, max_steps, mdts, cb, wtc, c_out, pre, red);
+        m_core.propagate_for(std::vector<double>{dt}, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
         return {make_c_out(), std::move(*user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<step_callback_batch<double>, std::vector<double>> propagate_grid(std::vector<double> grid,
                                                                                KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red);
+        auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib);
         return {std::move(*user_cb), std::move(ret)};
     }
 

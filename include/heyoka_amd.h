@@ -552,8 +552,39 @@ char *hy_angle_reducer_str(hy_angle_reducer);
 int hy_angle_reducer_call(hy_tab, void *user);     /* 1, or -1 on error (hy_last_error()) */
 int hy_angle_reducer_pre_hook(hy_tab, void *user); /* 0, or 1 on error */
 /* How the step callback of the last propagate_*() ran: 0 none, 1 host callback after every sweep, 2 angle reduction on the
- * device after every sweep, 3 angle reduction fused into the propagate kernel. */
+ * device after every sweep, 3 angle reduction fused into the propagate kernel, 4 every member of the callback set is
+ * library-side - step actions and angle reducers, at least one action - and was applied on the device after every sweep. */
 int hy_tab_last_callback_path(hy_tab);
+/* step_action (MI355X extension, no counterpart in the reference; heyoka_amd/csrc/step_action.hpp): a step callback defined by
+ * assignments `state variable <- expression` and an optional stop condition, applied by a generated kernel (hy_step_action,
+ * one lane per system) over the device-resident state after every sweep - the sibling of hy_event_action in the
+ * step-callback slot. The expressions may read state variables, par[...], the time (time_hi after the step) and numbers; all
+ * of them, the condition included, read the state from BEFORE the action. It acts on the systems whose last step had
+ * non-zero length; the values are bit for bit those of a hy_cfunc of the same expressions over the state variables; Taylor
+ * coefficients, last_h, times, cooldowns and the event log are left alone. stop_when (may be NULL; n may be 0 if it is not)
+ * holds for a system when its value c satisfies !(c == 0): with batch_semantics 0, 1, 2 the callback returns 0 and the loop
+ * ends as after a host callback which returned false; with batch_semantics 3 the system is retired alone with the sticky
+ * outcome cb_stop and the others carry on (hy_tab_get_n_stopped_by_action(): their number in the last call; they are not
+ * counted by hy_tab_get_n_retired()). hy_step_action_new() fails (NULL, hy_last_error()) on a left-hand side which is not a
+ * variable and without assignments and condition; the checks against the system of an integrator - a left-hand side which
+ * is not a state variable or is repeated, a variable which is not a state variable, a par[i] the integrator does not have -
+ * are made when the action first meets it (HY_ERR_INVALID_ARGUMENT from the propagate call, -1 from a direct call).
+ * hy_step_action_call is the ready-made member for a hy_step_callback_desc with the handle as user_data (no pre-hook),
+ * recognised by address: 1 to continue, 0 to stop, -1 on error (hy_last_error()). */
+typedef struct hy_step_action_s *hy_step_action;
+hy_step_action hy_step_action_new(const hy_expr *vars, const hy_expr *rhs, size_t n, hy_expr stop_when);
+hy_step_action hy_step_action_clone(hy_step_action);
+void hy_step_action_free(hy_step_action);
+/* "step_action({v: (0.999 * v)}, stop_when=...)". Caller frees. */
+char *hy_step_action_str(hy_step_action);
+int hy_step_action_call(hy_tab, void *user);
+uint64_t hy_tab_get_n_stopped_by_action(hy_tab);
+/* With hy_tab_set_event_timing(on): sum of the durations (ms, HIP events) of the hy_step_action launches and their number. */
+int hy_tab_step_action_kernel_ms(hy_tab, double *ms, uint64_t *launches);
+/* INTERNAL hooks of the test suite: the HIP source of the module of an action for a system (no integrator, no GPU; caller
+ * frees), and source (caller frees) / gfx950 code object (owned by the library) of the module inside an integrator. */
+char *hy_step_action_source(hy_sys, hy_step_action);
+int hy_tab_step_action_module(hy_tab, hy_step_action, char **source, const char **data, size_t *size);
 /* Beyond the constructor, the destructor and the two ready-made members: hy_angle_reducer_new_default / _clone / _str serve
  * the language bindings (default construction, copy, repr). The four entry points below are INTERNAL hooks of the test suite and
  * of the build-time compilation check, not part of the supported interface. */
