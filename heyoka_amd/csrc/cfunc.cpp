@@ -14,19 +14,6 @@
 namespace heyoka_amd::detail
 {
 
-namespace
-{
-
-struct cf_kargs {
-    double *out;
-    const double *in;
-    const double *pars;
-    const double *tm;
-    unsigned long long n;
-};
-
-} // namespace
-
 // Straight-line order-0 evaluation of the decomposition with the same node emitters as the Taylor stepper
 // (hip_emit_detail.hpp, ssa_emitter::node(i, 0)). See cfunc.hpp.
 order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input)
@@ -87,16 +74,8 @@ std::string emit_cfunc_source(const taylor_program &p)
 {
     const auto code = emit_order0(p, [](std::uint32_t i) { return "a.in[(u64)" + std::to_string(i) + "u * N + s]"; });
     std::ostringstream src;
-    src << emit_detail::prelude << emit_detail::rules_source(p);
-    src << R"HIP(
-struct hy_cf_args {
-    double *out;
-    const double *in;
-    const double *pars;
-    const double *tm;
-    u64 n;
-};
-
+    src << emit_detail::prelude() << emit_detail::rules_source(p);
+    src << "\n" << cf_kargs_text() << R"HIP(
 extern "C" __global__ void __launch_bounds__(256) hy_cfunc(const hy_cf_args a)
 {
     const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -233,7 +212,7 @@ void cfunc_core::call_device(double *d_out, const double *d_in, const double *d_
         d.mod = std::make_unique<aux_module>(d.cmod, d.device);
     }
     const cf_kargs a{d_out, d_in, d_pars, d_time, nevals};
-    d.mod->launch("hy_cfunc", nevals, 256, &a, sizeof(a), d.stream);
+    d.mod->launch("hy_cfunc", nevals, 256, a, d.stream);
 }
 
 // Reference: cfunc<T>::single_eval() / multi_eval(), src/cfunc_class.cpp:544-640, :875-1000.

@@ -22,18 +22,6 @@ namespace heyoka_amd::detail
 namespace
 {
 
-struct cout_kargs {
-    double *out;
-    const double *tm;
-    const double *const *tcs;
-    const double *thi;
-    const double *tlo;
-    unsigned long long N;
-    unsigned n_times;
-    unsigned scalar_tm;
-    double tm_s;
-};
-
 std::string fp_str(double x)
 {
     std::ostringstream oss;
@@ -54,21 +42,9 @@ std::string fp_str(double x)
 std::string make_cout_source(std::uint32_t order, std::uint32_t dim, bool ha)
 {
     std::ostringstream src;
-    src << emit_detail::prelude;
+    src << emit_detail::prelude();
     src << "#define HY_ORDER " << order << "u\n#define HY_DIM " << dim << "u\n#define HY_HA " << (ha ? 1 : 0) << "\n";
-    src << R"HIP(
-struct hy_cout_args {
-    double *out;
-    const double *tm;
-    const double *const *tcs;
-    const double *thi;
-    const double *tlo;
-    u64 N;
-    unsigned n_times;
-    unsigned scalar_tm;
-    double tm_s;
-};
-
+    src << "\n" << cout_kargs_text() << R"HIP(
 extern "C" __global__ void __launch_bounds__(256) hy_c_out(const hy_cout_args a)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -178,7 +154,7 @@ void c_out_core::call_device(const double *d_tm, double *d_out)
     const auto &d = *m_data;
     cout_kargs a{d_out, d_tm, d.d_ptrs.as<const double *>(), d.d_thi.as<double>(), d.d_tlo.as<double>(), d.N,
                  static_cast<unsigned>(d.n_rows()), 0u, 0.};
-    d.mod->launch("hy_c_out", d.N, 256, &a, sizeof(a), d.stream);
+    d.mod->launch("hy_c_out", d.N, 256, a, d.stream);
 }
 
 void c_out_core::run(const double *host_tm, bool scalar, double tm_s)
@@ -195,7 +171,7 @@ void c_out_core::run(const double *host_tm, bool scalar, double tm_s)
     cout_kargs a{m_scratch->d_out.as<double>(), m_scratch->d_tm.as<double>(), d.d_ptrs.as<const double *>(),
                  d.d_thi.as<double>(),          d.d_tlo.as<double>(),         d.N,
                  static_cast<unsigned>(d.n_rows()), scalar ? 1u : 0u, tm_s};
-    d.mod->launch("hy_c_out", d.N, 256, &a, sizeof(a), d.stream);
+    d.mod->launch("hy_c_out", d.N, 256, a, d.stream);
     m_output.resize(static_cast<std::size_t>(d.dim) * d.N);
     m_scratch->d_out.download(m_output.data(), m_output.size() * sizeof(double), d.stream);
     stream_synchronize(d.device, d.stream);

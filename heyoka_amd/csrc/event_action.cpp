@@ -113,7 +113,7 @@ std::string emit_assignment_section(const taylor_program &p, const std::vector<s
 std::string make_event_action_source(const std::vector<event_action_section> &sections)
 {
     std::ostringstream src;
-    src << emit_detail::prelude;
+    src << emit_detail::prelude();
     {
         // (The device code of the node rules of every section, once.)
         taylor_program all;
@@ -122,16 +122,7 @@ std::string make_event_action_source(const std::vector<event_action_section> &se
         }
         src << emit_detail::rules_source(all);
     }
-    src << R"HIP(
-struct hy_eva_args {
-    const i64 *outcome;
-    double *state;
-    const double *pars;
-    const double *time_hi;
-    u64 N, first, count;
-    i64 force;
-};
-
+    src << "\n" << eva_kargs_text() << R"HIP(
 // One lane per system. A system whose step ended at a terminal event with an action (continuing outcome = index of the
 // event) runs the section of that event; every other system leaves after the load of its outcome. A section is
 // straight-line code: the state rows it reads, parameters and time, all the right-hand sides, then the stores - every

@@ -28,7 +28,7 @@ std::size_t ed_work_list_bytes_per_slot(std::uint32_t order)
 std::string make_event_detection_source(std::uint32_t order, std::uint32_t max_detected)
 {
     std::ostringstream src;
-    src << emit_detail::prelude;
+    src << emit_detail::prelude();
     src << "#define HY_ORDER " << order << "u\n#define HY_P " << (order + 1u) << "u\n#define HY_MAXD " << max_detected
         << "u\n#define HY_WL_CAP " << ed_work_list_cap << "u\n";
     // Binomial coefficients for the translation by 1 (exact in double precision up to the orders in use).
@@ -48,51 +48,7 @@ std::string make_event_detection_source(std::uint32_t order, std::uint32_t max_d
         }
     }
     src << "};\n";
-    src << R"HIP(
-struct hy_ed_args {
-    const double *ev_tc;
-    const double *h;
-    const double *g_eps;
-    const int *dirs;
-    const double *cd_first;
-    const double *cd_second;
-    const int *cd_active;
-    double *out;
-    unsigned *counts;
-    unsigned *flags;
-    u64 N;
-    unsigned n_te, n_nte;
-    const double *mas;
-    double *g_eps_out;
-    double tol;
-    double *wl;
-    u64 wl_slots;
-    const double *maybe;
-};
-
-struct hy_ep_args {
-    const double *h;
-    const double *ed_out;
-    const unsigned *counts;
-    double *dout_h;
-    const double *g_eps;
-    const double *state;
-    double *time_hi, *time_lo;
-    const double *lim;
-    double *cd_first, *cd_second;
-    int *cd_active;
-    i64 *outcome;
-    double *last_h;
-    double *rec;
-    u64 *cursor;
-    const double *upd;
-    u64 N;
-    unsigned n_te, n_nte, dim, n_cd, n_oc, pad;
-    int native;
-    u64 *ev_counts;
-    const double *te_cd;
-};
-
+    src << "\n" << ed_kargs_text() << "\n" << ep_kargs_text() << R"HIP(
 __device__ __forceinline__ int hy_sgn(double x)
 {
     return (0.0 < x) - (x < 0.0);
@@ -649,12 +605,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_ev_scatter(const hy_ep_args
 // Copies of up to four arrays of doubles in one launch (the snapshot of state / times / parameters in front of a step whose
 // Taylor coefficients are stored on demand). One launch instead of three or four asynchronous copies (0.12 ms for
 // 300 MB).
-struct hy_copy_args {
-    double *dst[4];
-    const double *src[4];
-    u64 n[4];
-};
-extern "C" __global__ void __launch_bounds__(256) hy_copy_arrays(const hy_copy_args a)
+)HIP" << copy_kargs_text() << R"HIP(extern "C" __global__ void __launch_bounds__(256) hy_copy_arrays(const hy_copy_args a)
 {
     const u64 stride = (u64)gridDim.x * 256u;
     for (unsigned q = 0; q < 4u; ++q) {
@@ -671,24 +622,9 @@ extern "C" __global__ void __launch_bounds__(256) hy_copy_arrays(const hy_copy_a
 std::string make_event_recorder_source(std::uint32_t max_detected)
 {
     std::ostringstream src;
-    src << emit_detail::prelude;
+    src << emit_detail::prelude();
     src << "#define HY_MAXD " << max_detected << "u\n";
-    src << R"HIP(
-struct hy_evr_args {
-    const double *ed_out;
-    const unsigned *counts;
-    const double *dout_h;
-    const double *time_hi, *time_lo;
-    const i64 *outcome;
-    const int *is_rec;
-    unsigned *lane_rows;
-    u64 *blk;
-    u64 *total;
-    double *rows;
-    u64 N;
-    unsigned n_te, n_nte, row_doubles, pad;
-};
-
+    src << "\n" << evr_kargs_text() << R"HIP(
 // Does the c-th detected non-terminal event of the lane get a row? Its callback records, and it triggers before the
 // lane's first terminal event (the step ends there: |root| < |h|, src/taylor_adaptive_batch.cpp:837-871).
 __device__ __forceinline__ bool hy_evr_nt_row(const hy_evr_args &a, const double *nte, unsigned c, unsigned c_te, double h)

@@ -22,6 +22,7 @@
 
 #include "event_action.hpp"
 #include "expression.hpp"
+#include "kernel_args.hpp"
 
 namespace heyoka_amd
 {
@@ -97,65 +98,6 @@ std::size_t ed_work_list_bytes_per_slot(std::uint32_t order);
 // HIP source of the detection kernel for a given Taylor order and list capacity.
 std::string make_event_detection_source(std::uint32_t order, std::uint32_t max_detected);
 
-struct ed_kargs {
-    const double *ev_tc;      // [(event * (order + 1) + k) * N + lane], terminal events first
-    const double *h;          // [N] step taken
-    const double *g_eps;      // [N]
-    const int *dirs;          // [n_te + n_nte]
-    const double *cd_first;   // [n_te * N] terminal-event cooldowns (valid if cd_active != 0)
-    const double *cd_second;  // [n_te * N]
-    const int *cd_active;     // [n_te * N]
-    double *out;              // [2][N][ed_max_detected()][4]: idx, root, d_sgn, abs_der
-    unsigned *counts;         // [2][N]
-    unsigned *flags;          // [0] root isolations which failed, [1] event lists which overflowed, [2] root findings which
-                              // failed (event, lane) - the reference logs a warning and ignores the event
-    unsigned long long N;
-    unsigned n_te, n_nte;
-    // Device-side error bound of the Taylor series of the event equations (src/taylor_adaptive_batch.cpp:744-767):
-    // when mas != nullptr, g_eps is computed from max |x_i| and the tolerance and written to g_eps_out.
-    const double *mas;
-    double *g_eps_out;
-    double tol;
-    double *wl;               // working lists of the root isolation, ed_work_list_bytes_per_slot() per launched thread
-    unsigned long long wl_slots; // number of launched threads (grid-stride loop over the lanes)
-    // Optional [N]: 0.0 for the lanes in which the stepper has already ruled out events in this step (its conservative
-    // exclusion test on the jets it computed, emitted_module::events_in_stepper): they are skipped without reading their
-    // event jets.
-    const double *maybe;
-};
-
-// Per-lane bookkeeping of a step with events on the device (src/taylor_adaptive_batch.cpp:771-1030): hy_ev_pre
-// (truncation of the step at the first terminal event, size of the record buffer), the dense-output kernel, hy_ev_post
-// (time update, non-finite check, cooldown update, outcomes, compaction of the lanes with events into records),
-// hy_ev_scatter (cooldowns / outcomes set by the host for the lanes whose terminal events triggered).
-// Record of a lane with events: 8 doubles (lane, n_te, n_nte, g_eps, h, new time hi, new time lo, 0) followed by
-// 4 doubles per event (idx, root, d_sgn, |derivative|), terminal events first, in detection order.
-struct ep_kargs {
-    const double *h;          // [N] step sizes of the stepper
-    const double *ed_out;
-    const unsigned *counts;
-    double *dout_h;           // [N] final step sizes
-    const double *g_eps;      // [N]
-    const double *state;      // [dim * N], after the update
-    double *time_hi, *time_lo;
-    const double *lim;
-    double *cd_first, *cd_second;
-    int *cd_active;
-    long long *outcome;
-    double *last_h;
-    double *rec;
-    unsigned long long *cursor; // [0] record doubles needed (hy_ev_pre), [1] record doubles written (hy_ev_post)
-    const double *upd;          // hy_ev_scatter: n_cd x (position, first, second) then n_oc x (lane, outcome)
-    unsigned long long N;
-    unsigned n_te, n_nte, dim, n_cd, n_oc, pad;
-    // Every callback is the library's counting callback (core_*_event::native_counter): hy_ev_post applies the events of
-    // a lane itself - counts per event in ev_counts[n_te + n_nte] (terminal events first), cooldown and outcome of the
-    // first terminal event, cooldown settings in te_cd[n_te] (< 0: deduced) - and writes no records.
-    int native;
-    unsigned long long *ev_counts;
-    const double *te_cd;
-};
-
 // ---- event log (library-side recording callbacks, core_*_event::recorder) ----
 // A row of the log: event_log_header doubles (system, class - 0 terminal / 1 non-terminal -, event index within the
 // class, d_sgn, trigger time hi, trigger time lo, root, |d eq/dt| at the root), then - unless the states are switched
@@ -168,21 +110,6 @@ inline constexpr std::uint32_t event_log_header = 8;
 // (in-workgroup scan, sort of the lane's events, headers). A module of its own: the event-detection module of an
 // integrator without recorders is not touched.
 std::string make_event_recorder_source(std::uint32_t max_detected);
-
-struct evr_kargs {
-    const double *ed_out;      // as ed_kargs::out
-    const unsigned *counts;    // as ed_kargs::counts
-    const double *dout_h;      // [N] final step sizes
-    const double *time_hi, *time_lo; // [N] after hy_ev_post
-    const long long *outcome;  // [N] after hy_ev_post / hy_ev_native
-    const int *is_rec;         // [n_te + n_nte] != 0: the event has a recording callback (terminal events first)
-    unsigned *lane_rows;       // [N] rows of the lane in this step
-    unsigned long long *blk;   // [ceil(N / 256)] sums per workgroup, then (after hy_evr_scan) their exclusive scan
-    unsigned long long *total; // [0] rows of this step
-    double *rows;              // first new row of the log
-    unsigned long long N;
-    unsigned n_te, n_nte, row_doubles, pad;
-};
 
 } // namespace detail
 

@@ -11,43 +11,9 @@ namespace heyoka_amd::detail
 std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool ha)
 {
     std::ostringstream src;
-    src << emit_detail::prelude;
+    src << emit_detail::prelude();
     src << "#define HY_ORDER " << order << "u\n#define HY_DIM " << dim << "u\n#define HY_HA " << (ha ? 1 : 0) << "\n";
-    src << R"HIP(
-struct hy_grid_args {
-    const double *grid;
-    double *out;
-    const double *tc;
-    const double *thi;
-    const double *tlo;
-    const double *last_h;
-    const i64 *outcome;
-    double *rem_hi;
-    double *rem_lo;
-    const double *mdt;
-    const int *t_dir;
-    double *lim;
-    unsigned *gidx;
-    double *min_h;
-    double *max_h;
-    u64 *n_steps;
-    unsigned *counters;
-    u64 N;
-    unsigned n_grid;
-    double *next_tg;
-    u64 *acc_n_steps;
-    double *acc_min_h;
-    double *acc_max_h;
-    const double *grid_done;
-    const unsigned *launch_nf;
-    unsigned *gidx_prev;
-    i64 *retired;
-    i64 *outcome_w;
-    i64 override_oc;
-    int *cd_active;
-    const double *cd_second;
-};
-
+    src << "\n" << grid_kargs_text() << R"HIP(
 // Post-step kernel of the device-driven propagate_until() lock-step loop (callbacks / continuous output): the
 // per-lane bookkeeping of src/taylor_adaptive_batch.cpp:1395-1440 (step counters, min/max |h|, remaining time, limit of
 // the next step). counters[0] = lanes done in this sweep, counters[1] = lanes with a non-finite state. The final
@@ -147,13 +113,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_until_post(const hy_grid_ar
 // Independent semantics, events applied on the device: behind hy_ev_native, which has given the first terminal event of a
 // system its cooldown and the continuing outcome `index` - a terminal event WITHOUT a callback stops (te_stop[index] != 0:
 // the flag is data), outcome -index - 1.
-struct hy_ev_stop_args {
-    i64 *outcome;
-    const int *te_stop;
-    u64 N;
-    unsigned n_te, pad;
-};
-extern "C" __global__ void __launch_bounds__(256) hy_ev_stop(const hy_ev_stop_args a)
+)HIP" << ev_stop_kargs_text() << R"HIP(extern "C" __global__ void __launch_bounds__(256) hy_ev_stop(const hy_ev_stop_args a)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
     if (i >= a.N) return;

@@ -426,12 +426,7 @@ void device_module::launch_dout(double *out, const double *tc, const double *hs,
         return;
     }
     hip_check(hipSetDevice(m_impl->device), "hipSetDevice");
-    struct {
-        double *out;
-        const double *tc;
-        const double *hs;
-        unsigned long long N;
-    } a{out, tc, hs, N};
+    detail::dout_kargs a{out, tc, hs, N};
     std::size_t sz = sizeof(a);
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     const auto grid = (N + 255u) / 256u;

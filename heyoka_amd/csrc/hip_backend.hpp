@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "hip_emit.hpp"
@@ -73,10 +74,25 @@ public:
     aux_module &operator=(const aux_module &) = delete;
 
     [[nodiscard]] int device() const;
-    // Launch kernel `name` with n_threads threads in blocks of `block`, passing the args_size bytes at args.
+    // Launch kernel `name` with n_threads threads in blocks of `block`; a is the argument block of the kernel
+    // (kernel_args.hpp).
+    template <typename Args>
+    void launch(const char *name, std::uint64_t n_threads, unsigned block, const Args &a, void *stream)
+    {
+        static_assert(std::is_trivially_copyable_v<Args> && !std::is_pointer_v<Args>);
+        launch(name, n_threads, block, &a, sizeof(Args), stream);
+    }
+    // The same launch between two HIP events on the stream; waits for the kernel and returns its duration in ms.
+    template <typename Args>
+    double launch_timed(const char *name, std::uint64_t n_threads, unsigned block, const Args &a, void *stream)
+    {
+        static_assert(std::is_trivially_copyable_v<Args> && !std::is_pointer_v<Args>);
+        return launch_timed(name, n_threads, block, &a, sizeof(Args), stream);
+    }
+
+private:
     void launch(const char *name, std::uint64_t n_threads, unsigned block, const void *args, std::size_t args_size,
                 void *stream);
-    // The same launch between two HIP events on the stream; waits for the kernel and returns its duration in ms.
     double launch_timed(const char *name, std::uint64_t n_threads, unsigned block, const void *args, std::size_t args_size,
                         void *stream);
 };

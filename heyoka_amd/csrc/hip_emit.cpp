@@ -6,6 +6,7 @@
 #include "hip_emit.hpp"
 #include "hip_emit_detail.hpp"
 #include "logging.hpp"
+#include "taylor_adaptive_batch.hpp"
 
 #include <algorithm>
 #include <cassert>
@@ -59,14 +60,9 @@ __device__ __forceinline__ double hy_angle_red(double x)
 std::string make_angle_reduce_source()
 {
     std::string src = angle_reduce_helper_source;
+    src += "\n";
+    src += detail::ar_kargs_text();
     src += R"HIP(
-struct hy_ar_kargs {
-    double *state;            // [n_eq * N]
-    const unsigned *idx;      // [n_idx] state variables to reduce
-    unsigned long long N;     // number of systems
-    unsigned n_idx;
-};
-
 extern "C" __global__ void __launch_bounds__(256) hy_angle_reduce(const hy_ar_kargs a)
 {
     const unsigned long long t = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
@@ -110,43 +106,21 @@ emitted_module emit_angle_reduce_variant(const taylor_program &prog, const emit_
 namespace emit_detail
 {
 
-const char *const prelude = R"HIP(
-typedef unsigned long long u64;
-typedef long long i64;
+// (The values as taylor_outcome writes them: -2^32 - k.)
+std::string outcome_define(const char *name, taylor_outcome oc)
+{
+    const auto base = -(1ll << 32);
+    return std::string("#define ") + name + " (" + std::to_string(base) + "LL - " + std::to_string(base - static_cast<long long>(oc))
+           + ")\n";
+}
 
-struct hy_kargs {
-    double *state;
-    const double *pars;
-    double *time_hi;
-    double *time_lo;
-    const double *lim;
-    const double *tfin_hi;
-    const double *tfin_lo;
-    double *last_h;
-    i64 *outcome;
-    double *min_h;
-    double *max_h;
-    u64 *n_steps;
-    double *tc;
-    u64 N;
-    u64 max_steps;
-    int mode;
-    int pad;
-    unsigned int *counters;
-    double *scratch;
-    double tfin_s_hi, tfin_s_lo;
-    double *ev_tc;
-    double *max_abs_state;
-    double *sel_norms;
-    const double *tc_thr;
-    double *grid_done;
-};
-
-#define HY_OC_SUCCESS (-4294967296LL - 1)
-#define HY_OC_STEP_LIMIT (-4294967296LL - 2)
-#define HY_OC_TIME_LIMIT (-4294967296LL - 3)
-#define HY_OC_ERR_NF_STATE (-4294967296LL - 4)
-
+const std::string &prelude()
+{
+    static const std::string ret = "\ntypedef unsigned long long u64;\ntypedef long long i64;\n\n" + hy_kargs_text() + "\n"
+                                   + outcome_define("HY_OC_SUCCESS", taylor_outcome::success)
+                                   + outcome_define("HY_OC_STEP_LIMIT", taylor_outcome::step_limit)
+                                   + outcome_define("HY_OC_TIME_LIMIT", taylor_outcome::time_limit)
+                                   + outcome_define("HY_OC_ERR_NF_STATE", taylor_outcome::err_nf_state) + R"HIP(
 // Double-length (hi, lo) arithmetic: Knuth / Dekker error-free transformations
 // (reference: include/heyoka/detail/dfloat.hpp:109-164). No multiplications are involved, hence
 // FMA contraction cannot alter these sequences; reassociation is never enabled.
@@ -411,6 +385,8 @@ __device__ __forceinline__ bool hy_finite(double x)
     return __builtin_isfinite(x);
 }
 )HIP";
+    return ret;
+}
 
 // Scaling + safety factor of the step-size selector, folded on the host in double precision
 // (reference: taylor_determine_h_rhofac(), src/taylor_00.cpp:84-94).
@@ -426,8 +402,8 @@ void emit_dout(std::ostringstream &os, const taylor_program &p, const emit_optio
 {
     const auto n_eq = p.n_eq;
     const auto order = opts.order;
-    os << "extern \"C\" __global__ void __launch_bounds__(256) hy_dout(double *out, const double *tc, const double "
-          "*hs, u64 N)\n{\n";
+    os << "extern \"C\" __global__ void __launch_bounds__(256) hy_dout(" << detail::dout_kargs_parameters()
+       << ")\n{\n";
     os << "const u64 s = (u64)blockIdx.x * 256u + threadIdx.x;\nif (s >= N) return;\n";
     os << "const double h = hs[s];\n";
     os << "for (unsigned i = 0; i < " << n_eq << "u; ++i) {\n";
@@ -974,7 +950,7 @@ std::uint64_t reg_jet_estimate(const taylor_program &p, std::uint32_t order, boo
 emitted_module emit_unrolled(const taylor_program &p, const emit_options &opts)
 {
     std::ostringstream src;
-    src << prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << rules_source(p);
+    src << prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << rules_source(p);
     emit_dout(src, p, opts);
 
     emitted_module ret;
@@ -1119,9 +1095,7 @@ emitted_module emit_event_jets(const taylor_program &p, const emit_options &opts
         os << "};\n";
         const std::string coeff
             = opts.exact_division ? "(cp[(u64)(k - 1u) * N] / hy_rk_c[k])" : "hy_mul_nc(cp[(u64)(k - 1u) * N], hy_rk_c[k])";
-        // (hfull != nullptr: only the lanes whose step was truncated - hs[s] != hfull[s] - are updated: the stepper which
-        // evaluates the event equations itself has already taken the full step everywhere.)
-        os << "struct hy_doutc_args { double *out; const double *tc; const double *hs; u64 N; const double *hfull; };\n";
+        os << detail::doutc_kargs_text();
         // hy_dout_c: ONE pass over the coefficients of every stored variable v updates its own sum and the sum of the
         // variable x it defines (x' = v: x^[k] = v^[k-1] / k) - the rows of v are read once, with the operations and the
         // operation order of hy_dout on the full set.
@@ -1179,7 +1153,7 @@ emitted_module emit_event_jets(const taylor_program &p, const emit_options &opts
     }
     if (opts.ev_helpers_only) {
         std::ostringstream src;
-        src << emit_detail::prelude << os.str();
+        src << emit_detail::prelude() << os.str();
         ret.source = src.str();
         ret.kernel_name = "hy_dout_c";
         ret.block_size = 256;
@@ -1253,7 +1227,7 @@ emitted_module emit_event_jets(const taylor_program &p, const emit_options &opts
     os << "a.last_h[s] = h;\na.max_abs_state[s] = " << m0 << ";\n}\n";
 
     std::ostringstream src;
-    src << emit_detail::prelude << emit_detail::rules_source(p) << os.str();
+    src << emit_detail::prelude() << emit_detail::rules_source(p) << os.str();
     ret.source = src.str();
     ret.kernel_name = "hy_ev_jets";
     ret.block_size = 256;
@@ -1272,10 +1246,8 @@ std::string make_event_log_dout_source(const taylor_program &p, const emit_optio
     const auto n_eq = p.n_eq;
     const auto order = opts.order;
     std::ostringstream os;
-    os << emit_detail::prelude;
-    // n_rows != nullptr: the number of rows of the step is read from the device (written by hy_evr_scan), n_max bounds it.
-    os << "struct hy_drow_args { double *rows; const double *tc; const double *state; const u64 *n_rows; u64 n_max; u64 N; "
-          "unsigned row_doubles, pad; };\n";
+    os << emit_detail::prelude();
+    os << detail::drow_kargs_text();
     const auto derived = [&](std::uint32_t i) {
         return opts.compact_tc && p.sv_defs[i].type == operand::kind::uvar && p.sv_defs[i].idx < n_eq;
     };

@@ -14,54 +14,10 @@
 #include <vector>
 
 #include "decompose.hpp"
+#include "kernel_args.hpp"
 
 namespace heyoka_amd
 {
-
-// Kernel argument block. Must match the struct emitted in the generated source.
-struct hy_kargs {
-    double *state;            // [n_eq * N] rw
-    const double *pars;       // [n_par * N]
-    double *time_hi;          // [N] rw
-    double *time_lo;          // [N] rw
-    const double *lim;        // step mode: signed max step [N]; propagate mode: max_delta_t > 0 [N] or null
-    const double *tfin_hi;    // propagate mode: final times (double-length) [N]
-    const double *tfin_lo;    // [N]
-    double *last_h;           // [N] out
-    long long *outcome;       // [N] out (taylor_outcome)
-    double *min_h;            // [N] out (propagate mode)
-    double *max_h;            // [N] out (propagate mode)
-    unsigned long long *n_steps; // [N] out (propagate mode)
-    double *tc;               // [n_eq * (order + 1) * N] jet scratch == Taylor coefficients output
-    unsigned long long N;     // number of systems
-    unsigned long long max_steps; // propagate mode: 0 = unlimited
-    int mode;                 // 0 = single step, 1 = propagate_until, 2 = raw step, 4 = step with events
-    // Stepper with events which evaluates the event equations itself (emitted_module::events_in_stepper): bit 0 = every
-    // workgroup stores its Taylor coefficients (otherwise only those in which an event is possible), bit 1 = store NOTHING
-    // but the coefficients (the launch which regenerates them from the snapshot of the state before the step). 0 elsewhere.
-    int pad;
-    unsigned int *counters;   // [16] device counters: [0] lanes with non-finite state, [1] work-queue head
-    double *scratch;          // cluster mode: jet scratch, scratch_per_wave doubles per resident wave
-    double tfin_s_hi, tfin_s_lo; // propagate mode, scalar final time (used when tfin_hi == nullptr)
-    // mode 4 (stepper with events, no state update): Taylor coefficients of the event equations
-    // [(event * (order + 1) + k) * N + system] and max_i |x_i| per system.
-    double *ev_tc;
-    double *max_abs_state;
-    // mode 4 on the wave-cluster steppers (jets of the state variables to tc, no state update): the three norms of the
-    // step-size selector over the state variables, [3 * N] = max |x^[0]|, max |x^[p]|, max |x^[p-1]| per system. The
-    // jets of the event equations and the final step size are computed from tc by hy_ev_jets (emit_event_jets()).
-    // (With the event equations inside the stepper the first N entries carry its verdict per system for the detection
-    // kernel instead: 0.0 = no event possible in this step.)
-    double *sel_norms;
-    // Taylor coefficients on demand (hy_kargs::pad bit 2, emitted_module::tc_by_threshold / grid_multi_step): a time per
-    // system - the next grid point of propagate_grid() -; a step stores its coefficients only if it reaches that time, and in
-    // propagate mode (mode 1) the system leaves the step loop after that step: one launch takes every system from one grid
-    // point to the next instead of one step further.
-    const double *tc_thr;
-    // ... and, out, per system: 1.0 if its last step was clamped to the remaining time (h == rem.hi: the system has reached
-    // its final time - the post-step kernel of propagate_grid() then treats it as done), 0.0 otherwise.
-    double *grid_done;
-};
 
 enum class emit_mode { unrolled, cluster, table, block };
 

@@ -1999,7 +1999,7 @@ emitted_module emit_block(const taylor_program &p, const emit_options &opts, std
              : std::string{};
     // ===================== module text =====================
     std::ostringstream src;
-    src << prelude;
+    src << prelude();
     emit_detail::emit_dout(src, p, opts);
     src << tbl.str();
     src << "extern \"C\" __global__ void __launch_bounds__(" << bs << ") hy_taylor(const hy_kargs a)\n{\n";

@@ -2115,7 +2115,7 @@ emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts
 
     // ===================== module text =====================
     std::ostringstream src;
-    src << prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source);
+    src << prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source);
     emit_detail::emit_dout(src, p, opts);
 
     src << emit_detail::wsync_macro;

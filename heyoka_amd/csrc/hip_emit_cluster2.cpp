@@ -1370,7 +1370,7 @@ void cluster2_gen::text_helpers_and_constant_tables()
     src << "#define HY_GRID_FLAGS " << ((one_lane && jet_lds && !m4) ? "((HY_MODE == 1) & ((a.pad & 4) != 0))" : "false") << "\n";
     // (The stepper with events always uses the static schedule: its cooperative store has workgroup barriers.)
     src << "#define HY_NO_STATIC 0\n";
-    src << prelude;
+    src << prelude();
     emit_detail::emit_dout(src, p, opts);
     src << emit_detail::wsync_macro;
     src << R"HIP(

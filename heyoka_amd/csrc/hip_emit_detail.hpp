@@ -17,11 +17,18 @@
 #include "hip_emit.hpp"
 #include "node_rule.hpp"
 
+namespace heyoka_amd
+{
+enum class taylor_outcome : std::int64_t; // taylor_adaptive_batch.hpp
+}
+
 namespace heyoka_amd::emit_detail
 {
 
-// Common device-side prelude: argument block, double-length arithmetic, helpers.
-extern const char *const prelude;
+// Common device-side prelude: argument block, outcome codes, double-length arithmetic, helpers.
+const std::string &prelude();
+// "#define name (value)" for the kernels: every outcome code in a source comes from the enumerators through this.
+std::string outcome_define(const char *name, taylor_outcome oc);
 
 // The device code of the node rules a program uses (node_rule.hpp), to be emitted right behind the prelude.
 inline std::string rules_source(const taylor_program &p)

@@ -1050,7 +1050,7 @@ emitted_module emit_staged(const taylor_program &p, const emit_options &opts, st
 
     // ---- module text ----
     std::ostringstream src;
-    src << emit_detail::prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
+    src << emit_detail::prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
     emit_detail::emit_dout(src, p, opts);
     src << emit_detail::wsync_macro;
     {

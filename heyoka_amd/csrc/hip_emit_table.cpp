@@ -971,7 +971,7 @@ emitted_module emit_table(const taylor_program &p, const emit_options &opts)
     }
 
     std::ostringstream src;
-    src << emit_detail::prelude << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
+    src << emit_detail::prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
     emit_detail::emit_dout(src, p, opts);
     table_detail::emit_tables_and_rules(src, p, opts, "", "64u");
     src << table_hbm_kernel_code;

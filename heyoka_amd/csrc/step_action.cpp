@@ -122,24 +122,8 @@ std::string make_step_action_source(const step_action_section &sec)
 {
     const auto &p = sec.prog;
     std::ostringstream src;
-    src << emit_detail::prelude << emit_detail::rules_source(p);
-    src << R"HIP(
-#define HY_SA_CB_STOP (-4294967296LL - 5)
-
-struct hy_sa_args {
-    const double *last_h;
-    double *state;
-    const double *pars;
-    const double *time_hi;
-    unsigned *counter;
-    i64 *retired;
-    i64 *outcome_w;
-    double *lim;
-    unsigned *gidx;
-    u64 N;
-    unsigned n_grid, pad;
-};
-
+    src << emit_detail::prelude() << emit_detail::rules_source(p);
+    src << "\n" << emit_detail::outcome_define("HY_SA_CB_STOP", taylor_outcome::cb_stop) << "\n" << sa_kargs_text() << R"HIP(
 // One lane per system. A system whose last step had zero length (it has reached its final time, or was retired) leaves
 // after the load of last_h. The section is straight-line code: the state rows it reads, parameters and time, all the
 // right-hand sides and the condition, then the stores - every expression sees the state from before the action. Stop

@@ -36,6 +36,7 @@
 
 #include "decompose.hpp"
 #include "expression.hpp"
+#include "kernel_args.hpp"
 #include "taylor_adaptive_batch.hpp"
 
 namespace heyoka_amd
@@ -82,24 +83,6 @@ struct step_action_section {
 
 step_action_section make_step_action_section(const step_action &act, const std::vector<expression> &state_vars,
                                              std::uint32_t n_par);
-
-// Argument block of hy_step_action. counter: the number of systems whose condition held (one atomic per wavefront; null
-// without a condition). retired / outcome_w / lim (/ gidx, n_grid in propagate_grid()): the arrays of the independent
-// semantics, null otherwise.
-struct sa_kargs {
-    const double *last_h;
-    double *state;
-    const double *pars;
-    const double *time_hi;
-    unsigned *counter;
-    long long *retired;
-    long long *outcome_w;
-    double *lim;
-    unsigned *gidx;
-    unsigned long long N;
-    unsigned n_grid, pad;
-};
-static_assert(sizeof(sa_kargs) == 88 && offsetof(sa_kargs, n_grid) == 80); // hy_sa_args
 
 // HIP source of the module of one action (kernel hy_step_action, one lane per system, 256 lanes per workgroup): the load
 // of last_h, then one straight-line section - loads of the state rows it reads, parameters and time, the right-hand

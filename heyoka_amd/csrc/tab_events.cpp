@@ -232,7 +232,7 @@ void tab_core::impl::launch_event_stepper(const std::vector<double> *lims)
                 ca.src[3] = d_pars.as<double>();
                 ca.n[3] = d_pars.bytes() / dsz;
             }
-            ed_mod->launch("hy_copy_arrays", std::min<std::uint64_t>(ca.n[0], std::uint64_t(256) * 256u * 16u), 256, &ca, sizeof(ca), stream);
+            ed_mod->launch("hy_copy_arrays", std::min<std::uint64_t>(ca.n[0], std::uint64_t(256) * 256u * 16u), 256, ca, stream);
             a.pad = 0;
         }
     }
@@ -248,7 +248,7 @@ void tab_core::impl::launch_event_stepper(const std::vector<double> *lims)
     tc_expand_pending = cluster_events && emitted.compact_tc;
     if (cluster_events && !emitted.events_in_stepper) {
         // Jets of the event equations, extended norms and final step sizes from the jets of the state variables.
-        evj_mod->launch("hy_ev_jets", N, 256, &a, sizeof(a), stream);
+        evj_mod->launch("hy_ev_jets", N, 256, a, stream);
     }
 }
 
@@ -265,7 +265,7 @@ void tab_core::impl::launch_event_detection(bool device_g_eps)
                       // (The stepper which evaluates the event equations itself leaves a flag per system in the buffer of the
                       // selector norms, which it does not use: 0 = no event possible in this step.)
                       (cluster_events && emitted.events_in_stepper) ? d_selnorms.as<double>() : nullptr};
-    ed_mod->launch("hy_detect_events", ed_slots, 64, &ea, sizeof(ea), stream);
+    ed_mod->launch("hy_detect_events", ed_slots, 64, ea, stream);
 }
 
 // State columns of n_max rows of the log from first_row on (*d_n_rows of them, if given): dense output of the Taylor
@@ -274,7 +274,7 @@ void tab_core::impl::log_fill_states(std::uint64_t first_row, const unsigned lon
 {
     const drow_kargs da{d_ev_log.as<double>() + first_row * log_row_doubles(), d_tc.as<double>(), d_state.as<double>(), d_n_rows,
                         n_max, N, log_row_doubles(), 0u};
-    drow_mod->launch("hy_dout_rows", n_max, 256, &da, sizeof(da), stream);
+    drow_mod->launch("hy_dout_rows", n_max, 256, da, stream);
 }
 
 namespace
@@ -433,7 +433,7 @@ void tab_core::impl::ev_launch(ev_step &s, const std::vector<double> *lims)
     pa.n_nte = static_cast<std::uint32_t>(ntes.size());
     pa.dim = dim;
     d_ev_cursor.zero(stream);
-    ed_mod->launch("hy_ev_pre", N, 256, &pa, sizeof(pa), stream);
+    ed_mod->launch("hy_ev_pre", N, 256, pa, stream);
     unsigned flags[3] = {0, 0, 0};
     if (ev_native) {
         pa.native = 1;
@@ -473,16 +473,16 @@ void tab_core::impl::ev_update_state(ev_step &s)
         // stored them - a detected event is an event the stepper's exclusion test could not rule out.
         if (!tes.empty()) {
             const doutc_kargs da{d_state.as<double>(), d_tc.as<double>(), d_douth.as<double>(), N, d_lasth.as<double>()};
-            evj_mod->launch("hy_dout_c", N, 256, &da, sizeof(da), stream);
+            evj_mod->launch("hy_dout_c", N, 256, da, stream);
         }
     } else if (tc_expand_pending) {
         // (Compact Taylor coefficients: the dense output derives the rows the stepper left out.)
         const doutc_kargs da{d_state.as<double>(), d_tc.as<double>(), d_douth.as<double>(), N, nullptr};
-        evj_mod->launch("hy_dout_c", N, 256, &da, sizeof(da), stream);
+        evj_mod->launch("hy_dout_c", N, 256, da, stream);
     } else {
         dmod->launch_dout(d_state.as<double>(), d_tc.as<double>(), d_douth.as<double>(), N);
     }
-    ed_mod->launch("hy_ev_post", N, 256, &s.pa, sizeof(s.pa), stream);
+    ed_mod->launch("hy_ev_post", N, 256, s.pa, stream);
 }
 
 // Library-side events, applied on the device: counts, cooldowns and outcomes (hy_ev_native), plain stops, rows of the
@@ -492,14 +492,14 @@ void tab_core::impl::ev_apply_on_device(ev_step &s)
     const auto n_te = s.pa.n_te;
     const bool any = ev_native && s.cur[0] != 0u;
     if (any) {
-        ed_mod->launch("hy_ev_native", N, 256, &s.pa, sizeof(s.pa), stream);
+        ed_mod->launch("hy_ev_native", N, 256, s.pa, stream);
         if (d_te_stop.bytes() != 0u) {
             // Independent semantics: terminal events without a callback are applied on the device as well. hy_ev_native has
             // given them their cooldown and the continuing outcome `index`; hy_ev_stop (post-step module: the text of the
             // event-detection module is pinned) turns it into the stopping outcome -index - 1 where the flag is set.
             const ev_stop_kargs sa{d_outcome.as<long long>(), d_te_stop.as<int>(), N, n_te, 0u};
             ensure_grid_mod();
-            grid_mod->launch("hy_ev_stop", N, 256, &sa, sizeof(sa), stream);
+            grid_mod->launch("hy_ev_stop", N, 256, sa, stream);
         }
     }
     if (s.log_ub != 0u) {
@@ -522,9 +522,9 @@ void tab_core::impl::ev_apply_on_device(ev_step &s)
         ra.n_te = n_te;
         ra.n_nte = s.pa.n_nte;
         ra.row_doubles = log_row_doubles();
-        evr_mod->launch("hy_evr_count", N, 256, &ra, sizeof(ra), stream);
-        evr_mod->launch("hy_evr_scan", 256, 256, &ra, sizeof(ra), stream);
-        evr_mod->launch("hy_evr_write", N, 256, &ra, sizeof(ra), stream);
+        evr_mod->launch("hy_evr_count", N, 256, ra, stream);
+        evr_mod->launch("hy_evr_scan", 256, 256, ra, stream);
+        evr_mod->launch("hy_evr_write", N, 256, ra, stream);
         if (log_states) {
             log_fill_states(log_rows, ra.total, s.log_ub);
         }
@@ -735,7 +735,7 @@ void tab_core::impl::ev_scatter(ev_step &s)
         pa.upd = d_ev_upd.as<double>();
         pa.n_cd = static_cast<unsigned>(upd_cd.size() / 3u);
         pa.n_oc = static_cast<unsigned>(s.upd_oc.size() / 2u);
-        ed_mod->launch("hy_ev_scatter", pa.n_cd + pa.n_oc, 256, &pa, sizeof(pa), stream);
+        ed_mod->launch("hy_ev_scatter", pa.n_cd + pa.n_oc, 256, pa, stream);
         stream_synchronize(device, stream);
     }
     pending_cd.clear();

@@ -1,5 +1,4 @@
-// Private state of the host driver of the MI355X batch Taylor integrator (tab_core::impl) and the argument blocks of
-// its auxiliary kernels: shared by taylor_adaptive_batch.cpp, tab_events.cpp, tab_propagate.cpp and grid_post.cpp.
+// Private state of the host driver of the MI355X batch Taylor integrator (tab_core::impl): shared by taylor_adaptive_batch.cpp, tab_events.cpp, tab_propagate.cpp and grid_post.cpp.
 #ifndef HEYOKA_AMD_TAB_IMPL_HPP
 #define HEYOKA_AMD_TAB_IMPL_HPP
 
@@ -25,6 +24,7 @@
 #include "hip_backend.hpp"
 #include "hip_emit.hpp"
 #include "hip_emit_detail.hpp"
+#include "kernel_args.hpp"
 #include "step_action.hpp"
 
 namespace heyoka_amd::detail
@@ -38,99 +38,6 @@ inline std::string fp_to_string(double x)
     const auto res = std::to_chars(buf, buf + sizeof(buf), x);
     return std::string(buf, res.ptr);
 }
-
-// Argument block of the post-step kernels (hy_grid_post / hy_until_post, see make_grid_source()): mirrors hy_grid_args field by
-// field. The call sites name the fields they set; the others keep the null / zero below.
-struct grid_kargs {
-    const double *grid = nullptr;
-    double *out = nullptr;
-    const double *tc = nullptr;
-    const double *thi = nullptr;
-    const double *tlo = nullptr;
-    const double *last_h = nullptr;
-    const long long *outcome = nullptr;
-    double *rem_hi = nullptr;
-    double *rem_lo = nullptr;
-    const double *mdt = nullptr;
-    const int *t_dir = nullptr;
-    double *lim = nullptr;
-    unsigned *gidx = nullptr;
-    double *min_h = nullptr;
-    double *max_h = nullptr;
-    unsigned long long *n_steps = nullptr;
-    unsigned *counters = nullptr;
-    unsigned long long N = 0;
-    unsigned n_grid = 0;
-    // (Next grid time of every lane, +-inf once the lane is through its grid: hy_kargs::pad bit 2 of the next sweep.)
-    double *next_tg = nullptr;
-    // Launches which take every lane from one grid point to the next (emitted_module::grid_multi_step): the stepper leaves
-    // the counters / extrema of ITS launch in n_steps / min_h / max_h, which are accumulated here (null: single-step sweeps).
-    unsigned long long *acc_n_steps = nullptr;
-    double *acc_min_h = nullptr;
-    double *acc_max_h = nullptr;
-    // (... and whether the lane's last step was clamped to its remaining time: hy_kargs::grid_done.)
-    const double *grid_done = nullptr;
-    // (... and the stepper's count of systems which went non-finite in the launch, hy_kargs::counters[0]; nonzero with the
-    // reference's semantics: the launch is rolled back, nothing is recorded - counters[3] = 1 tells the host. Null: no check.)
-    const unsigned *launch_nf = nullptr;
-    // (The grid index of every lane before this sweep's samples: hy_grid_unsample takes them back. Null: not kept.)
-    unsigned *gidx_prev = nullptr;
-    // Independent semantics (config::batch_semantics == 3), null / 0 otherwise. retired[N]: the sticky outcome of a system
-    // retired in this call (0: not retired); outcome_w: the outcome array, writable - the sticky outcome is put back after
-    // every zero-length step; counters[4] / [5] count the systems retired by events / as non-finite. override_oc:
-    // hy_indep_override only - the outcome (step_limit, cb_stop) of the systems which are neither done nor retired.
-    long long *retired = nullptr;
-    long long *outcome_w = nullptr;
-    long long override_oc = 0;
-    // (... and the cooldown flags / durations of the terminal events, [n_te * N]: see hy_indep_retired(). Null: none.)
-    int *cd_active = nullptr;
-    const double *cd_second = nullptr;
-};
-
-static_assert(sizeof(grid_kargs) == 248 && offsetof(grid_kargs, cd_second) == 240); // hy_grid_args
-
-// Argument blocks of the other auxiliary kernels (like ed_kargs / ep_kargs / evr_kargs in event_detection.hpp), each with
-// the layout of the kernel-side struct named behind it.
-// hy_dout_c, hy_tc_expand: hy_doutc_args (emit_event_jets()).
-struct doutc_kargs {
-    double *out;
-    const double *tc, *hs;
-    unsigned long long N;
-    const double *hfull;
-};
-static_assert(sizeof(doutc_kargs) == 40 && offsetof(doutc_kargs, hfull) == 32);
-// hy_ev_stop: hy_ev_stop_args (make_grid_source()).
-struct ev_stop_kargs {
-    long long *outcome;
-    const int *te_stop;
-    unsigned long long N;
-    unsigned n_te, pad;
-};
-static_assert(sizeof(ev_stop_kargs) == 32 && offsetof(ev_stop_kargs, pad) == 28);
-// hy_dout_rows: hy_drow_args (make_event_log_dout_source()).
-struct drow_kargs {
-    double *rows;
-    const double *tc, *state;
-    const unsigned long long *n_rows;
-    unsigned long long n_max, N;
-    unsigned row_doubles, pad;
-};
-static_assert(sizeof(drow_kargs) == 56 && offsetof(drow_kargs, pad) == 52);
-// hy_copy_arrays: hy_copy_args (make_event_detection_source()).
-struct copy_kargs {
-    double *dst[4];
-    const double *src[4];
-    unsigned long long n[4];
-};
-static_assert(sizeof(copy_kargs) == 96 && offsetof(copy_kargs, n) == 64);
-// hy_angle_reduce: hy_ar_kargs (make_angle_reduce_source()).
-struct ar_kargs {
-    double *state;
-    const unsigned *idx;
-    unsigned long long N;
-    unsigned n_idx;
-};
-static_assert(sizeof(ar_kargs) == 32 && offsetof(ar_kargs, n_idx) == 24);
 
 // Sets a value for the lifetime of the object and puts the previous one back.
 template <typename T>
@@ -495,10 +402,10 @@ struct tab_core::impl {
         const eva_kargs ka{d_outcome.as<long long>(), d_state.as<double>(), d_pars.as<double>(), d_thi.as<double>(), N, first, count, force};
         if (ev_timing) {
             // (Event timing on: the duration of the kernel from HIP events, see get_event_action_kernel_ms().)
-            act_ms += act_mod->launch_timed("hy_ev_action", count, 256, &ka, sizeof(ka), stream);
+            act_ms += act_mod->launch_timed("hy_ev_action", count, 256, ka, stream);
             ++act_timed;
         } else {
-            act_mod->launch("hy_ev_action", count, 256, &ka, sizeof(ka), stream);
+            act_mod->launch("hy_ev_action", count, 256, ka, stream);
         }
     }
     mutable double act_ms = 0;
@@ -565,7 +472,7 @@ struct tab_core::impl {
         {
             if (indep) {
                 a.override_oc = static_cast<long long>(oc);
-                d.grid_mod->launch("hy_indep_override", d.N, 256, &a, sizeof(a), d.stream);
+                d.grid_mod->launch("hy_indep_override", d.N, 256, a, d.stream);
             } else {
                 d.prop_res_override = oc;
             }

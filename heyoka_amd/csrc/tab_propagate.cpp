@@ -340,7 +340,7 @@ void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_s
                      .max_h = d.d_maxh.as<double>(), .n_steps = d.d_nsteps.as<unsigned long long>(),
                      .counters = b_cnt.as<unsigned>(), .N = N};
         sw.fill(a);
-        d.grid_mod->launch("hy_until_post", N, 256, &a, sizeof(a), d.stream);
+        d.grid_mod->launch("hy_until_post", N, 256, a, d.stream);
         unsigned cnt[6] = {0, 0, 0, 0, 0, 0};
         sw.read_counters(b_cnt, cnt, 3u);
         // Outcomes of the last sweep + accumulated statistics: on the device.
@@ -531,7 +531,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                      .launch_nf = (multi_step && d.batch_semantics == 0) ? d.d_counters.as<unsigned>() : nullptr,
                      .gidx_prev = b_gidx_prev.as<unsigned>()};
         sw.fill(a);
-        d.grid_mod->launch("hy_grid_post", N, 256, &a, sizeof(a), d.stream);
+        d.grid_mod->launch("hy_grid_post", N, 256, a, d.stream);
         unsigned cnt[6] = {0, 0, 0, 0, 0, 0};
         sw.read_counters(b_cnt, cnt, 4u);
         if (cnt[3] != 0u) {
@@ -548,7 +548,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
             // (Lock-step sweeps: no samples of this step, src/taylor_adaptive_batch.cpp:1962-1968. The multi-step launches of
             // batch_semantics == 2 keep theirs: every lane on its own.)
             if (!multi_step) {
-                d.grid_mod->launch("hy_grid_unsample", N, 256, &a, sizeof(a), d.stream);
+                d.grid_mod->launch("hy_grid_unsample", N, 256, a, d.stream);
             }
             // A non-finite state was detected: stop (the outcomes of the last step are reported). With coefficients on
             // demand the lanes which did not reach a grid point in this sweep hold the coefficients of OLDER steps:
@@ -776,7 +776,7 @@ void tab_core::angle_reduce(const std::vector<std::uint32_t> &idx)
         d.d_ar_idx.upload(d.ar_idx_dev.data(), d.ar_idx_dev.size() * sizeof(std::uint32_t), d.stream);
     }
     const ar_kargs a{d.d_state.as<double>(), d.d_ar_idx.as<unsigned>(), d.N, static_cast<unsigned>(idx.size())};
-    d.ar_mod->launch("hy_angle_reduce", static_cast<std::uint64_t>(d.N) * idx.size(), 256, &a, sizeof(a), d.stream);
+    d.ar_mod->launch("hy_angle_reduce", static_cast<std::uint64_t>(d.N) * idx.size(), 256, a, d.stream);
     // The device copy of the state is the newer one; callers who hold references to the host mirror see it refreshed.
     d.dev_newer = true;
     if (d.sticky_const_refs) {
@@ -837,10 +837,10 @@ bool tab_core::apply_step_action(const step_action &act)
                      d.sa_n_grid,
                      0u};
     if (d.ev_timing) {
-        d.sa_ms += var.dm->launch_timed("hy_step_action", d.N, 256, &a, sizeof(a), d.stream);
+        d.sa_ms += var.dm->launch_timed("hy_step_action", d.N, 256, a, d.stream);
         ++d.sa_timed;
     } else {
-        var.dm->launch("hy_step_action", d.N, 256, &a, sizeof(a), d.stream);
+        var.dm->launch("hy_step_action", d.N, 256, a, d.stream);
     }
     // The device copy of the state is the newer one; the mirrors somebody holds follow, as after any kernel.
     d.dev_newer = true;

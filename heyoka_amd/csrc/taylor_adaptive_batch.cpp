@@ -648,7 +648,7 @@ void tab_core::impl::ensure_tc_expanded() const
         return;
     }
     const doutc_kargs ea{d_tc.as<double>(), d_tc.as<double>(), nullptr, N, nullptr};
-    evj_mod->launch("hy_tc_expand", N, 256, &ea, sizeof(ea), stream);
+    evj_mod->launch("hy_tc_expand", N, 256, ea, stream);
     tc_expand_pending = false;
 }
 
@@ -1040,12 +1040,12 @@ void tab_core::raw_step_e(double *d_jet, const double *d_state, const double *d_
     }
     if (d.cluster_events && !d.emitted.events_in_stepper) {
         // (Jets of the event equations, extended norms and the step size from the jets of the state variables.)
-        d.evj_mod->launch("hy_ev_jets", n_systems, 256, &a, sizeof(a), d.stream);
+        d.evj_mod->launch("hy_ev_jets", n_systems, 256, a, d.stream);
     }
     if (d.emitted.compact_tc && d.evj_mod) {
         // (The stepper left the rows of the variables defined by another state variable to be derived: x^[k] = v^[k-1] / k.)
         const doutc_kargs ea{d_jet, d_jet, nullptr, n_systems, nullptr};
-        d.evj_mod->launch("hy_tc_expand", n_systems, 256, &ea, sizeof(ea), d.stream);
+        d.evj_mod->launch("hy_tc_expand", n_systems, 256, ea, d.stream);
     }
     // The step size which was taken.
     device_copy(d_h, lh.get(), n * w, d.device, d.stream);

@@ -149,20 +149,7 @@ std::string make_taylor_map_source(std::uint32_t n_orig, std::uint32_t n_args, s
     std::ostringstream o;
     o << "// Taylor map: n_orig_sv = " << n_orig << ", n_args = " << n_args << ", order = " << order << ", " << nt
       << " terms per output.\n";
-    o << R"HIP(struct hy_tmap_args {
-    const double *state; // [dim * N] SoA state of the variational integrator
-    const double *in;    // [n_args * N]
-    double *out;         // [n_orig * N]
-    unsigned long long N;
-};
-struct hy_tmap_cloud_args {
-    const double *state;
-    const double *delta; // [N * n_args * n_samples], or [n_args * n_samples] when shared
-    double *out;         // [N * n_orig * n_samples]
-    unsigned long long N, n_samples;
-    unsigned blocks_per_sys, shared;
-};
-
+    o << tmap_kargs_text() << tmap_cloud_kargs_text() << R"HIP(
 extern "C" __global__ void __launch_bounds__(256) hy_tmap(const hy_tmap_args a)
 {
     const unsigned long long sys = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
@@ -406,7 +393,7 @@ void tab_core::eval_taylor_map_device(const double *d_in, double *d_out)
         d.tmap_mod = std::make_unique<aux_module>(d.var->tmap_cmod, d.device);
     }
     const tmap_kargs ka{d.d_state.as<double>(), d_in, d_out, d.N};
-    d.tmap_mod->launch("hy_tmap", d.N, 256, &ka, sizeof(ka), d.stream);
+    d.tmap_mod->launch("hy_tmap", d.N, 256, ka, d.stream);
 }
 
 const std::vector<double> &tab_core::eval_taylor_map(const double *in, std::size_t n)
@@ -461,7 +448,7 @@ void tab_core::eval_taylor_map_cloud(const double *d_delta, double *d_out, std::
     const std::uint64_t chunks = (n_samples + 255u) / 256u, target = 8192;
     const auto bps = static_cast<unsigned>(std::min<std::uint64_t>(chunks, std::max<std::uint64_t>(1, (target + d.N - 1u) / d.N)));
     const tmap_cloud_kargs ka{d.d_state.as<double>(), d_delta, d_out, d.N, n_samples, bps, shared ? 1u : 0u};
-    d.tmap_mod->launch("hy_tmap_cloud", static_cast<std::uint64_t>(d.N) * bps * 256u, 256, &ka, sizeof(ka), d.stream);
+    d.tmap_mod->launch("hy_tmap_cloud", static_cast<std::uint64_t>(d.N) * bps * 256u, 256, ka, d.stream);
 }
 
 } // namespace heyoka_amd::detail

@@ -21,6 +21,8 @@
 #include <string>
 #include <vector>
 
+#include "kernel_args.hpp"
+
 namespace heyoka_amd::detail
 {
 
@@ -66,20 +68,5 @@ std::size_t taylor_map_lds_bytes();
 // null) receives what was decided, for the stage logger.
 std::string make_taylor_map_source(std::uint32_t n_orig, std::uint32_t n_args, std::uint32_t order,
                                    std::size_t lds_bytes = taylor_map_default_lds_bytes, std::string *note = nullptr);
-
-// Argument blocks: hy_tmap_args / hy_tmap_cloud_args of the module.
-struct tmap_kargs {
-    const double *state, *in;
-    double *out;
-    unsigned long long N;
-};
-static_assert(sizeof(tmap_kargs) == 32);
-struct tmap_cloud_kargs {
-    const double *state, *delta;
-    double *out;
-    unsigned long long N, n_samples;
-    unsigned blocks_per_sys, shared;
-};
-static_assert(sizeof(tmap_cloud_kargs) == 48);
 
 } // namespace heyoka_amd::detail
