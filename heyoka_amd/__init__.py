@@ -63,6 +63,7 @@ __all__ = [
     "event_action",
     "step_action",
     "step_action_source",
+    "grid_observables_source",
     "event_log",
     "callback",
     "diff",
@@ -1129,6 +1130,15 @@ def step_action_source(sys, action):
     return take_str(check_handle(lib.hy_step_action_source(s._h, action._h)))
 
 
+def grid_observables_source(sys, observables, order=20, high_accuracy=False):
+    """HIP source of the post-step module of propagate_grid() with the section of ``observables`` for the system ``sys`` at
+    the Taylor order ``order``: no integrator, no GPU. ``HEYOKA_AMD_GRID_OBS=registers|staged`` overrides how the kernel
+    holds the samples of a grid point (default: registers up to 64 state rows read, the staging buffer beyond)."""
+    s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
+    obs, oarr = _handle_array(list(observables))
+    return take_str(check_handle(lib.hy_grid_obs_source(s._h, oarr, len(obs), int(order), int(bool(high_accuracy)))))
+
+
 class _angle_reducer:
     """callback::angle_reducer (include/heyoka/callback/angle_reducer.hpp): the step callback which keeps the given state
     variables in [0, 2 pi) - ``x -= 2 pi floor(x / 2 pi)`` after every step. It lives in the library: passed as
@@ -1875,13 +1885,21 @@ class taylor_adaptive_batch:
     def propagate_for(self, delta_t, max_steps=0, max_delta_t=None, callback=None, write_tc=False, c_output=False):
         return self._propagate(lib.hy_tab_propagate_for, delta_t, max_steps, max_delta_t, callback, write_tc, c_output)
 
-    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None):
+    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None, observables=None):
+        """propagate_grid(): ``(callback, out)`` with ``out[point, var, lane]``, NaN where not reached. ``observables`` (an
+        MI355X extension): a list of expressions over the state variables, ``par[...]`` and ``hy.time`` -
+        ``out[point, observable, lane]`` then holds, bit for bit, ``cfunc(observables, vars=state variables)`` of the state
+        sample, the parameters of the lane and the grid time of the row, evaluated inside the post-step kernel of the grid
+        loop from the dense output of the state rows the observables read; a row which was not reached is NaN in every
+        column. Everything else is as without observables."""
         g = _f64(grid)
         if g.ndim == 1:
             g = np.repeat(g[:, None], self.batch_size, axis=1)
         g = np.ascontiguousarray(g)
         n_grid = g.shape[0]
-        out = np.empty((n_grid, self.dim, self.batch_size))
+        if observables is not None:
+            obs, oarr = _handle_array(list(observables))
+        out = np.empty((n_grid, self.dim if observables is None else len(obs), self.batch_size))
         if max_delta_t is None:
             mptr, mn, mkeep = None, 0, None
         else:
@@ -1889,8 +1907,12 @@ class taylor_adaptive_batch:
             mptr, mn = mkeep.ctypes.data, mkeep.size
         err = []
         descs, n_cbs, keep = self._callback_descs(callback, err)
-        rc = lib.hy_tab_propagate_grid_cbs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
-                                           out.ctypes.data)
+        if observables is None:
+            rc = lib.hy_tab_propagate_grid_cbs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
+                                               out.ctypes.data)
+        else:
+            rc = lib.hy_tab_propagate_grid_obs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
+                                               oarr, len(obs), out.ctypes.data)
         del keep
         if err:
             raise err[0]
@@ -1898,10 +1920,11 @@ class taylor_adaptive_batch:
         raise_for(rc)
         return callback, out
 
-    def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None):
+    def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None, observables=None):
         """propagate_grid() with the samples written to a caller-owned device buffer (``out_ptr``: device address of
         n_grid * dim * batch_size doubles, layout [point, var, lane]); ``grid``: 1-D (shared by all the lanes) or
-        (n_grid, batch_size). Nothing of that size is materialised on the host."""
+        (n_grid, batch_size). Nothing of that size is materialised on the host. With ``observables`` (see
+        propagate_grid()) the buffer holds n_grid * len(observables) * batch_size doubles, layout [point, observable, lane]."""
         g = np.ascontiguousarray(_f64(grid))
         scalar = g.ndim == 1
         if max_delta_t is None:
@@ -1909,8 +1932,22 @@ class taylor_adaptive_batch:
         else:
             mkeep = _f64(max_delta_t).reshape(-1)
             mptr, mn = mkeep.ctypes.data, mkeep.size
+        if observables is not None:
+            obs, oarr = _handle_array(list(observables))
+            raise_for(lib.hy_tab_propagate_grid_obs_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
+                                                           mptr, mn, oarr, len(obs), ctypes.c_void_p(int(out_ptr))))
+            return
         raise_for(lib.hy_tab_propagate_grid_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
                                                    mptr, mn, ctypes.c_void_p(int(out_ptr))))
+
+    def grid_observables_module(self, observables):
+        """(HIP source, gfx950 code object) of the post-step module of propagate_grid() with the section of ``observables``
+        (kernels hy_grid_post, hy_grid_obs0, hy_grid_unsample) in this integrator: checked against its system and compiled
+        on first use. No GPU is needed."""
+        obs, oarr = _handle_array(list(observables))
+        src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        raise_for(lib.hy_tab_grid_obs_module(self._h, oarr, len(obs), ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
+        return take_str(src.value), ctypes.string_at(data.value, n.value)
 
     @property
     def propagate_res(self):

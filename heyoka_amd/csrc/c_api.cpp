@@ -24,6 +24,7 @@
 #include "expression.hpp"
 #include "expression_diff.hpp"
 #include "hip_backend.hpp"
+#include "grid_observables.hpp"
 #include "hip_emit.hpp"
 #include "model.hpp"
 #include "node_rule.hpp"
@@ -1987,6 +1988,108 @@ int hy_tab_propagate_grid_device(hy_tab t, const double *grid, size_t n_grid, in
             throw std::invalid_argument("hy_tab_propagate_grid_device(): the device output pointer is null");
         }
         t->core.propagate_grid(std::move(g), static_cast<std::size_t>(max_steps), expand_mdt(mdts, n_mdt, bs), {}, d_out);
+    });
+}
+// ---- grid observables (grid_observables.hpp) ----
+namespace
+{
+
+std::vector<expression> obs_from(const char *fn, const hy_expr *obs, size_t n_obs)
+{
+    if (obs == nullptr && n_obs != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of observables is null");
+    }
+    std::vector<expression> ret;
+    for (size_t i = 0; i < n_obs; ++i) {
+        if (obs[i] == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the observable " + std::to_string(i) + " is a null expression");
+        }
+        ret.push_back(obs[i]->ex);
+    }
+    return ret;
+}
+
+void check_tab(const char *fn, hy_tab t)
+{
+    if (t == nullptr) {
+        throw std::invalid_argument(std::string(fn) + "(): the integrator handle is null");
+    }
+}
+
+} // namespace
+
+int hy_tab_propagate_grid_obs(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
+                              size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
+                              double *out)
+{
+    return guarded([&] {
+        check_tab("hy_tab_propagate_grid_obs", t);
+        const auto ov = obs_from("hy_tab_propagate_grid_obs", obs, n_obs);
+        // (The checks against the system come before the callbacks are touched and before anything runs.)
+        t->core.prepare_grid_observables(ov);
+        const auto bs = t->core.get_batch_size();
+        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
+        auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
+                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red, lib_cb, &ov);
+        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
+    });
+}
+int hy_tab_propagate_grid_obs_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                     const double *mdts, size_t n_mdt, const hy_expr *obs, size_t n_obs, double *d_out)
+{
+    return guarded([&] {
+        check_tab("hy_tab_propagate_grid_obs_device", t);
+        const auto ov = obs_from("hy_tab_propagate_grid_obs_device", obs, n_obs);
+        t->core.prepare_grid_observables(ov);
+        const auto bs = t->core.get_batch_size();
+        std::vector<double> g;
+        if (scalar_grid != 0) {
+            g.reserve(n_grid * bs);
+            for (size_t k = 0; k < n_grid; ++k) {
+                g.insert(g.end(), bs, grid[k]);
+            }
+        } else {
+            g = vec_from(grid, n_grid * bs);
+        }
+        if (d_out == nullptr) {
+            throw std::invalid_argument("hy_tab_propagate_grid_obs_device(): the device output pointer is null");
+        }
+        t->core.propagate_grid(std::move(g), static_cast<std::size_t>(max_steps), expand_mdt(mdts, n_mdt, bs), {}, d_out, {}, {},
+                               false, &ov);
+    });
+}
+char *hy_grid_obs_source(hy_sys sys, const hy_expr *obs, size_t n_obs, uint32_t order, int high_accuracy)
+{
+    try {
+        if (sys == nullptr) {
+            throw std::invalid_argument("hy_grid_obs_source(): the system handle is null");
+        }
+        const auto ov = obs_from("hy_grid_obs_source", obs, n_obs);
+        const auto svars = detail::state_variables_of(sys->sys);
+        // (Without an integrator there is no parameter array to check against: whatever the expressions use.)
+        const auto sec = detail::make_grid_obs_section(ov, svars, std::numeric_limits<std::uint32_t>::max());
+        return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+int hy_tab_grid_obs_module(hy_tab t, const hy_expr *obs, size_t n_obs, char **source, const char **data, size_t *size)
+{
+    return guarded([&] {
+        check_tab("hy_tab_grid_obs_module", t);
+        const auto ov = obs_from("hy_tab_grid_obs_module", obs, n_obs);
+        const auto &src = t->core.grid_observables_source(ov);
+        const auto &co = t->core.grid_observables_code_object(ov);
+        if (source != nullptr) {
+            *source = dup_str(src);
+        }
+        if (data != nullptr) {
+            *data = co.data();
+        }
+        if (size != nullptr) {
+            *size = co.size();
+        }
     });
 }
 int hy_tab_get_propagate_res(hy_tab t, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps)

@@ -16,7 +16,8 @@ namespace heyoka_amd::detail
 
 // Straight-line order-0 evaluation of the decomposition with the same node emitters as the Taylor stepper
 // (hip_emit_detail.hpp, ssa_emitter::node(i, 0)). See cfunc.hpp.
-order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input)
+order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input,
+                        const std::map<const operand *, std::string> *num_names)
 {
     // NOTE: the decomposition is sorted breadth-first (all the nodes of a dependency level before the next one),
     // which is the right order for the Taylor recursions but, for a straight-line evaluation, keeps every value of
@@ -25,6 +26,9 @@ order0_code emit_order0(const taylor_program &p, const std::function<std::string
     // depth-first from the outputs (operands right before their consumer), and the inputs are read where they are
     // used.
     emit_detail::ssa_emitter e(p, 0);
+    if (num_names != nullptr) {
+        e.numpar_override = *num_names;
+    }
     for (std::uint32_t i = 0; i < p.n_eq; ++i) {
         e.val(i, 0) = input(i);
     }

@@ -13,6 +13,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <memory>
 #include <optional>
 #include <string>
@@ -38,7 +39,10 @@ struct order0_code {
     std::string body;
     std::vector<std::string> outs;
 };
-order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input);
+// num_names (optional): names which stand for numerical operands of p, by address, in place of their literals - values the
+// caller defines with the same bits (the grid observables keep their constants out of the scalar registers that way).
+order0_code emit_order0(const taylor_program &p, const std::function<std::string(std::uint32_t)> &input,
+                        const std::map<const operand *, std::string> *num_names = nullptr);
 
 class cfunc_core
 {

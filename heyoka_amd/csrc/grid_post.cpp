@@ -1,8 +1,200 @@
 // Post-step kernels of the device-driven sweep loops of propagate_until() and propagate_grid() (tab_propagate.cpp).
 #include "tab_impl.hpp"
 
+#include <set>
+
+#include "cfunc.hpp"
+#include "grid_observables.hpp"
+
 namespace heyoka_amd::detail
 {
+
+grid_obs_section make_grid_obs_section(const std::vector<expression> &obs, const std::vector<expression> &state_vars,
+                                       std::uint32_t n_par)
+{
+    if (obs.empty()) {
+        throw std::invalid_argument("The list of observables of propagate_grid() is empty");
+    }
+    std::set<std::string> names;
+    for (const auto &sv : state_vars) {
+        names.insert(sv.var_name());
+    }
+    for (std::size_t o = 0; o < obs.size(); ++o) {
+        for (const auto &v : get_variables(obs[o])) {
+            if (names.count(v) == 0u) {
+                throw std::invalid_argument("The observable " + std::to_string(o) + " of propagate_grid() uses the variable '" + v
+                                            + "', which is not a state variable of the system");
+            }
+        }
+    }
+    grid_obs_section ret;
+    ret.n_obs = static_cast<std::uint32_t>(obs.size());
+    const auto dc = function_decompose(obs, state_vars);
+    ret.prog = make_program(dc, static_cast<std::uint32_t>(state_vars.size()), ret.n_obs);
+    if (ret.prog.n_par > n_par) {
+        throw std::invalid_argument("An observable of propagate_grid() uses par[" + std::to_string(ret.prog.n_par - 1u)
+                                    + "], but the integrator has " + std::to_string(n_par) + " parameter(s)");
+    }
+    // State rows the section reads: the operands of its elementary functions and the outputs which are plain copies.
+    std::set<std::uint32_t> reads;
+    for (const auto &n : ret.prog.nodes) {
+        for (const auto &a : n.args) {
+            if (a.type == operand::kind::uvar && a.idx < ret.prog.n_eq) {
+                reads.insert(a.idx);
+            }
+        }
+    }
+    for (const auto &d : ret.prog.sv_defs) {
+        if (d.type == operand::kind::uvar && d.idx < ret.prog.n_eq) {
+            reads.insert(d.idx);
+        }
+    }
+    ret.rows.assign(reads.begin(), reads.end());
+    ret.staged = ret.rows.size() > grid_obs_max_register_rows;
+    if (const char *env = std::getenv("HEYOKA_AMD_GRID_OBS")) {
+        const std::string mode(env);
+        if (mode == "registers") {
+            ret.staged = false;
+        } else if (mode == "staged") {
+            ret.staged = true;
+        } else if (!mode.empty()) {
+            throw std::invalid_argument("Invalid value '" + mode + "' of HEYOKA_AMD_GRID_OBS: 'registers' or 'staged'");
+        }
+    }
+    return ret;
+}
+
+std::string grid_obs_key(const std::vector<expression> &obs)
+{
+    std::string key;
+    for (const auto &ex : obs) {
+        key += ex.to_string() + ";";
+    }
+    const char *env = std::getenv("HEYOKA_AMD_GRID_OBS");
+    return key + "|" + (env != nullptr ? env : "");
+}
+
+namespace
+{
+
+// The observable section of the module: the dense output of one state row (the loop of the plain hy_grid_post, operation by
+// operation) and hy_obs_section(), the straight-line code of emit_order0() with its stores. Registers: the samples arrive as
+// arguments x<row>; staged: they are read from a.stage at the point of use, through a volatile pointer - the loads are not
+// replaced by the values just stored, which would keep every sample alive in a register after all.
+std::string grid_obs_device_functions(const grid_obs_section &sec)
+{
+    const auto &p = sec.prog;
+    // The numerical constants of the section which are not inline constants of the instruction set - a pair of SGPRs each,
+    // and the compiler moves all of them ahead of the grid loop (44 SGPRs for the energy of the outer Solar System, more
+    // than are left) - become named values c<k> in VGPRs: the same bits in the same operations.
+    std::map<const operand *, std::string> lit_names;
+    std::vector<std::string> lit_decls;
+    {
+        std::map<std::uint64_t, std::string> by_bits;
+        const auto visit = [&](const operand &o) {
+            if (o.type != operand::kind::num) {
+                return;
+            }
+            const auto av = std::abs(o.value);
+            if (av == 0. || av == 0.5 || av == 1. || av == 2. || av == 4.) {
+                return;
+            }
+            std::uint64_t bits = 0;
+            std::memcpy(&bits, &o.value, sizeof(bits));
+            auto it = by_bits.find(bits);
+            if (it == by_bits.end()) {
+                it = by_bits.emplace(bits, "c" + std::to_string(by_bits.size())).first;
+                lit_decls.push_back("double " + it->second + " = " + fp_literal(o.value) + ";\nasm volatile(\"\" : \"+v\"("
+                                    + it->second + "));\n");
+            }
+            lit_names.emplace(&o, it->second);
+        };
+        for (const auto &n : p.nodes) {
+            for (const auto &o : n.args) {
+                visit(o);
+            }
+        }
+        for (const auto &d : p.sv_defs) {
+            visit(d);
+        }
+    }
+    const auto code = emit_order0(
+        p,
+        [&](std::uint32_t r) {
+            return sec.staged ? "((const volatile double *)stg)[(u64)" + std::to_string(r) + "u * N]" : "x" + std::to_string(r);
+        },
+        &lit_names);
+    std::ostringstream src;
+    src << "\n// The state rows the observables read.\n#define HY_NROWS " << sec.rows.size() << "u\n__device__ const unsigned hy_obs_rows[HY_NROWS] = {";
+    for (std::size_t j = 0; j < sec.rows.size(); ++j) {
+        src << (j != 0u ? ", " : "") << sec.rows[j] << "u";
+    }
+    src << "};\n";
+    src << R"HIP(
+// The observables of lane i at grid point g and time t_hi, stored to out[(g * HY_NOUT + o) * N + i]: outp points to out[i]
+// (and stg to the staged samples of the lane).
+__device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 i, const u64 N, double *outp, const unsigned g, const double t_hi
+)HIP";
+    if (sec.staged) {
+        src << ", const double *stg";
+    } else {
+        for (const auto r : sec.rows) {
+            src << ", const double x" << r;
+        }
+    }
+    src << ")\n{\n";
+    for (std::uint32_t k = 0; k < p.n_par; ++k) {
+        src << "const double par_" << k << " = a.pars[(u64)" << k << "u * N + i];\n";
+    }
+    if (!p.time_dependent) {
+        src << "(void)t_hi;\n";
+    }
+    for (const auto &d : lit_decls) {
+        src << d;
+    }
+    src << code.body;
+    for (std::size_t o = 0; o < code.outs.size(); ++o) {
+        src << "outp[((u64)g * HY_NOUT + " << o << "u) * N] = " << code.outs[o] << ";\n";
+    }
+    src << "}\n";
+    return src.str();
+}
+
+// The call of hy_obs_section() behind the samples x<row> / the staged samples.
+std::string grid_obs_call(const grid_obs_section &sec, const char *outp, const char *stg, const char *xs, const char *g, const char *t)
+{
+    std::string ret = std::string("hy_obs_section(a, i, N, ") + outp + ", " + g + ", " + t;
+    if (sec.staged) {
+        ret += std::string(", ") + stg;
+    } else {
+        for (std::size_t j = 0; j < sec.rows.size(); ++j) {
+            ret += ", " + std::string(xs) + "[" + std::to_string(j) + "]";
+        }
+    }
+    return ret + ");\n";
+}
+
+} // namespace
+
+// The dense output of one state row inside hy_grid_post - c points to its order-0 coefficient, hd is the time from the start
+// of the step, the sample is res -: shared, text for text, by the plain kernel and by the kernel with an observable section.
+constexpr const char *dense_row_text = R"HIP(#if HY_HA
+            double res = c[0], comp = 0.0, cur_h = hd;
+            for (unsigned k = 1; k <= HY_ORDER; ++k) {
+                const double tmp = c[(u64)k * N] * cur_h;
+                const double y = tmp - comp;
+                const double t = res + y;
+                comp = (t - res) - y;
+                res = t;
+                cur_h = cur_h * hd;
+            }
+#else
+            double res = c[(u64)HY_ORDER * N];
+            for (unsigned k = 1; k <= HY_ORDER; ++k) {
+                res = c[(u64)(HY_ORDER - k) * N] + res * hd;
+            }
+#endif
+)HIP";
 
 // Post-step kernel of the device-resident propagate_grid() loop: the per-lane body of the reference's loop
 // (src/taylor_adaptive_batch.cpp:1760-2040) - step counters, remaining time, dense output at every grid
@@ -10,9 +202,21 @@ namespace heyoka_amd::detail
 // compensated summation as in taylor_add_d_out_function()), limit of the next step.
 std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool ha)
 {
+    return make_grid_source(order, dim, ha, nullptr);
+}
+
+std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool ha, const grid_obs_section *sec)
+{
     std::ostringstream src;
     src << emit_detail::prelude();
+    if (sec != nullptr) {
+        src << emit_detail::rules_source(sec->prog);
+    }
     src << "#define HY_ORDER " << order << "u\n#define HY_DIM " << dim << "u\n#define HY_HA " << (ha ? 1 : 0) << "\n";
+    if (sec != nullptr) {
+        src << "#define HY_NOUT " << sec->n_obs << "u\n";
+    }
+    const char *const ncol = sec != nullptr ? "HY_NOUT" : "HY_DIM";
     src << "\n" << grid_kargs_text() << R"HIP(
 // Post-step kernel of the device-driven propagate_until() lock-step loop (callbacks / continuous output): the
 // per-lane bookkeeping of src/taylor_adaptive_batch.cpp:1395-1440 (step counters, min/max |h|, remaining time, limit of
@@ -131,7 +335,11 @@ extern "C" __global__ void __launch_bounds__(256) hy_indep_override(const hy_gri
     const bool done = (a.gidx != nullptr) ? (a.gidx[i] >= a.n_grid) : (a.rem_hi[i] == 0.0 && a.rem_lo[i] == 0.0);
     if (!done) a.outcome_w[i] = a.override_oc;
 }
-
+)HIP";
+    if (sec != nullptr) {
+        src << grid_obs_device_functions(*sec);
+    }
+    src << R"HIP(
 extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_args a)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -209,33 +417,61 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
     const bool fwd = !hy_df_lt(tcur, tstart);
     const hy_df t0 = fwd ? tstart : tcur, t1 = fwd ? tcur : tstart;
     const bool done_lane = (rem.hi == 0.0 && rem.lo == 0.0);
-    unsigned g = a.gidx[i];
+)HIP";
+    if (sec != nullptr) {
+        // The addresses the sampling uses, per lane and in VGPRs (the empty asm statements): as uniform base addresses they
+        // would hold a pair of SGPRs each across the whole loop, next to the literals of the section, which are moved ahead
+        // of the loop as well - the wave has 102 SGPRs, and 512 VGPRs per lane at 256 lanes per workgroup.
+        src << "    const double *tc0 = a.tc + i;\n    asm volatile(\"\" : \"+v\"(tc0));\n";
+        src << "    double *out0 = a.out + i;\n    asm volatile(\"\" : \"+v\"(out0));\n";
+        if (sec->staged) {
+            src << "    double *stg = a.stage + i;\n    asm volatile(\"\" : \"+v\"(stg));\n";
+        }
+    }
+    src << R"HIP(    unsigned g = a.gidx[i];
     while (g < ng) {
         hy_df tg; tg.hi = a.grid[(u64)g * N + i]; tg.lo = 0.0;
         const bool avail = (!hy_df_lt(tg, t0) && !hy_df_lt(t1, tg)) || done_lane;
         if (!avail) break;
         const double hd = hy_df_sub(tg, tstart).hi;
-        for (unsigned v = 0; v < HY_DIM; ++v) {
+)HIP";
+    if (sec == nullptr) {
+        src << R"HIP(        for (unsigned v = 0; v < HY_DIM; ++v) {
             const double *c = a.tc + (u64)v * (HY_ORDER + 1u) * N + i;
-#if HY_HA
-            double res = c[0], comp = 0.0, cur_h = hd;
-            for (unsigned k = 1; k <= HY_ORDER; ++k) {
-                const double tmp = c[(u64)k * N] * cur_h;
-                const double y = tmp - comp;
-                const double t = res + y;
-                comp = (t - res) - y;
-                res = t;
-                cur_h = cur_h * hd;
-            }
-#else
-            double res = c[(u64)HY_ORDER * N];
-            for (unsigned k = 1; k <= HY_ORDER; ++k) {
-                res = c[(u64)(HY_ORDER - k) * N] + res * hd;
-            }
-#endif
-            a.out[((u64)g * HY_DIM + v) * N + i] = res;
+)HIP" << dense_row_text
+            << R"HIP(            a.out[((u64)g * HY_DIM + v) * N + i] = res;
         }
-        ++g;
+)HIP";
+    } else {
+        // The rows the observables read, in the order of the plain loop, then the section. The loop over the rows runs over
+        // the table hy_obs_rows with the body of the plain loop, text for text (dense_row_text): the compiler makes of the
+        // inner loop what it makes of it in the plain kernel - in particular it does or does not unroll it completely, which
+        // decides whether its first iteration is folded (comp = 0) and with that the last bits of the sample. Staged: a loop,
+        // the samples go to the staging buffer. Registers: the loop over the rows is unrolled into the named values xs[j];
+        // a scheduling barrier behind every row keeps the loads of one row in flight, not those of all of them (HY_ORDER + 1
+        // coefficients per row: 1 512 VGPRs for the 36 rows of the outer Solar System).
+        // The coefficients do not depend on the grid point: the empty asm statements on their base address and on the stride
+        // keep the loads and the scalar offsets inside the iteration of the while loop (hoisted out of it they are all alive
+        // at once again).
+        src << "        const double *tcb = tc0;\n        asm volatile(\"\" : \"+v\"(tcb));\n";
+        src << "        u64 Ns = N;\n        asm volatile(\"\" : \"+s\"(Ns));\n";
+        if (!sec->staged) {
+            src << "        double xs[HY_NROWS];\n#pragma unroll\n";
+        }
+        src << R"HIP(        for (unsigned j = 0; j < HY_NROWS; ++j) {
+            const unsigned v = hy_obs_rows[j];
+            // (This N shadows the kernel's on purpose: the shared body below says N, and here it must be the stride Ns.)
+            const u64 N = Ns;
+            const double *c = tcb + (u64)v * (HY_ORDER + 1u) * N;
+)HIP" << dense_row_text;
+        if (sec->staged) {
+            src << "            stg[(u64)v * N] = res;\n        }\n";
+        } else {
+            src << "            xs[j] = res;\n            __builtin_amdgcn_sched_barrier(0);\n        }\n";
+        }
+        src << "        " << grid_obs_call(*sec, "out0", "stg", "xs", "g", "tg.hi");
+    }
+    src << R"HIP(        ++g;
     }
     if (retire) g = ng;
     a.gidx[i] = g;
@@ -262,12 +498,37 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
     if (i >= N) return;
     const unsigned g1 = a.gidx[i];
     for (unsigned g = a.gidx_prev[i]; g < g1; ++g) {
-        for (unsigned v = 0; v < HY_DIM; ++v) {
-            a.out[((u64)g * HY_DIM + v) * N + i] = __builtin_nan("");
+        for (unsigned v = 0; v < )HIP" << ncol << R"HIP(; ++v) {
+            a.out[((u64)g * )HIP" << ncol << R"HIP( + v) * N + i] = __builtin_nan("");
         }
     }
 }
 )HIP";
+    if (sec != nullptr) {
+        src << R"HIP(
+// Row 0 of the output: the observables of the current state at the first grid time (at the start of the call and again
+// after a rollback).
+extern "C" __global__ void __launch_bounds__(256) hy_grid_obs0(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (i >= N) return;
+)HIP";
+        if (sec->staged) {
+            src << "    double *stg = a.stage + i;\n";
+        } else {
+            src << "    double xs[HY_NROWS];\n";
+        }
+        std::size_t n_obs0 = 0;
+        for (const auto r : sec->rows) {
+            if (sec->staged) {
+                src << "    stg[(u64)" << r << "u * N] = a.state[(u64)" << r << "u * N + i];\n";
+            } else {
+                src << "    xs[" << n_obs0++ << "] = a.state[(u64)" << r << "u * N + i];\n";
+            }
+        }
+        src << "    " << grid_obs_call(*sec, "a.out + i", "stg", "xs", "0u", "a.grid[i]") << "}\n";
+    }
     return src.str();
 }
 

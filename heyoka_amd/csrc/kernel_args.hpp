@@ -157,6 +157,11 @@ HY_KARGS(grid_kargs, hy_grid_args,
     // (... and the cooldown flags / durations of the terminal events, [n_te * N]: see hy_indep_retired(). Null: none.)
     int *cd_active = nullptr;
     const double *cd_second = nullptr;
+    // Grid observables (make_grid_source() with a section), null otherwise: the parameters [n_par * N], the
+    // staging buffer of one sample [dim * N] (staged mode only) and, for hy_grid_obs0, the current state [dim * N].
+    const double *pars = nullptr;
+    double *stage = nullptr;
+    const double *state = nullptr;
 )
 
 // hy_ev_stop (make_grid_source()).

@@ -65,6 +65,9 @@ HEYOKA_AMD_KWARG(max_delta_t);
 HEYOKA_AMD_KWARG(callback);
 HEYOKA_AMD_KWARG(write_tc);
 HEYOKA_AMD_KWARG(c_output);
+// propagate_grid() / ensemble_propagate_grid_batch(), MI355X extension: kw::observables = std::vector<expression>{...} - the
+// grid output has one column per observable instead of one per state variable (grid_observables.hpp).
+HEYOKA_AMD_KWARG(observables);
 // Events (reference: include/heyoka/events.hpp:87-100).
 HEYOKA_AMD_KWARG(direction);
 HEYOKA_AMD_KWARG(cooldown);

@@ -23,6 +23,7 @@
 #include "dfloat.hpp"
 #include "hip_backend.hpp"
 #include "hip_emit.hpp"
+#include "grid_observables.hpp"
 #include "hip_emit_detail.hpp"
 #include "kernel_args.hpp"
 #include "step_action.hpp"
@@ -296,6 +297,34 @@ struct tab_core::impl {
     std::optional<c_out_core> last_c_out;
     // Post-step kernel of the device-resident propagate_grid() loop (created on first use).
     mutable std::unique_ptr<aux_module> grid_mod;
+    // ---- grid observables (grid_observables.hpp) ----
+    // The post-step modules with an observable section this integrator has met, keyed by the text of the observables and
+    // the way of holding the samples: checked against the system, generated and compiled on first use (the code objects
+    // live in the process-wide cache), loaded at the first launch. Nothing is ever dropped: an integrator which meets
+    // generated observables without end keeps a section, a source text and a loaded module for each of them. The intended
+    // use is a handful of lists per integrator; a copy of the integrator starts with an empty map.
+    struct go_variant {
+        grid_obs_section sec;
+        std::string source;
+        std::shared_ptr<const compiled_module> cm;
+        std::unique_ptr<aux_module> dm;
+    };
+    std::map<std::string, go_variant> go_variants;
+    go_variant &get_go_variant(const std::vector<expression> &obs)
+    {
+        const auto key = grid_obs_key(obs);
+        auto it = go_variants.find(key);
+        if (it == go_variants.end()) {
+            go_variant v;
+            v.sec = make_grid_obs_section(obs, state_variables_of(sys), prog.n_par);
+            v.source = make_grid_source(order, dim, high_accuracy, &v.sec);
+            const detail::stopwatch sw;
+            v.cm = hiprtc_compile_source(v.source);
+            detail::log_message(log_level::trace, "grid observables: kernel compilation runtime: " + sw.str());
+            it = go_variants.emplace(key, std::move(v)).first;
+        }
+        return it->second;
+    }
 
     // ---- event detection (see event_detection.hpp) ----
     std::vector<core_t_event> tes;

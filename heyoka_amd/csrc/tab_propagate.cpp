@@ -383,7 +383,7 @@ std::optional<c_out_core> tab_core::take_c_output()
 void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                           const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
                                           const std::vector<double> &max_delta_ts, std::size_t max_steps,
-                                          double *d_out, const cb_t &cb)
+                                          double *d_out, const cb_t &cb, const std::vector<expression> *obs)
 {
     auto &d = *m_impl;
     const auto N = d.N;
@@ -395,8 +395,17 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     d.ensure_device();
     d.ensure_tc();
     d.ensure_grid_mod();
+    // Grid observables: the post-step module with their section takes the place of the plain one for the
+    // samples - hy_grid_post, hy_grid_unsample, and hy_grid_obs0 for row 0 -, one column per observable.
+    auto *const gov = obs != nullptr ? &d.get_go_variant(*obs) : nullptr;
+    if (gov != nullptr && !gov->dm) {
+        gov->dm = std::make_unique<aux_module>(gov->cm, d.device);
+    }
+    aux_module &sample_mod = gov != nullptr ? *gov->dm : *d.grid_mod;
+    const std::size_t n_col = gov != nullptr ? gov->sec.n_obs : dim;
+    device_buffer b_stage((gov != nullptr && gov->sec.staged) ? static_cast<std::size_t>(dim) * N * dsz : 0u, d.device);
 
-    const auto out_doubles = grid.size() * dim;
+    const auto out_doubles = grid.size() * n_col;
     device_buffer b_grid(grid.size() * dsz, d.device), b_out(d_out != nullptr ? 0u : out_doubles * dsz, d.device);
     double *const out_ptr = d_out != nullptr ? d_out : b_out.as<double>();
     device_buffer b_rem_hi(N * dsz, d.device), b_rem_lo(N * dsz, d.device), b_mdt(N * dsz, d.device);
@@ -424,7 +433,17 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
             // NOTE: the all-ones byte pattern is a (quiet) NaN.
             device_fill_bytes(out_ptr, 0xFF, out_doubles * dsz, d.device, d.stream);
             d.to_device();
-            device_copy(out_ptr, d.d_state.get(), static_cast<std::size_t>(dim) * N * dsz, d.device, d.stream);
+            if (gov == nullptr) {
+                device_copy(out_ptr, d.d_state.get(), static_cast<std::size_t>(dim) * N * dsz, d.device, d.stream);
+            }
+        }
+        if (gov != nullptr) {
+            // (Row 0: the observables of the current state - the one the call without observables copies - at the first
+            // grid time. The host output arrives all NaN.)
+            d.before_kernel();
+            const grid_kargs a0{.grid = b_grid.as<double>(), .out = out_ptr, .N = N, .n_grid = n_grid, .pars = d.d_pars.as<double>(),
+                                .stage = b_stage.as<double>(), .state = d.d_state.as<double>()};
+            sample_mod.launch("hy_grid_obs0", N, 256, a0, d.stream);
         }
         b_rem_hi.upload(rhi.data(), N * dsz, d.stream);
         b_rem_lo.upload(rlo.data(), N * dsz, d.stream);
@@ -530,8 +549,12 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                      .grid_done = multi_step ? b_grid_done.as<double>() : nullptr,
                      .launch_nf = (multi_step && d.batch_semantics == 0) ? d.d_counters.as<unsigned>() : nullptr,
                      .gidx_prev = b_gidx_prev.as<unsigned>()};
+        if (gov != nullptr) {
+            a.pars = d.d_pars.as<double>();
+            a.stage = b_stage.as<double>();
+        }
         sw.fill(a);
-        d.grid_mod->launch("hy_grid_post", N, 256, a, d.stream);
+        sample_mod.launch("hy_grid_post", N, 256, a, d.stream);
         unsigned cnt[6] = {0, 0, 0, 0, 0, 0};
         sw.read_counters(b_cnt, cnt, 4u);
         if (cnt[3] != 0u) {
@@ -548,7 +571,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
             // (Lock-step sweeps: no samples of this step, src/taylor_adaptive_batch.cpp:1962-1968. The multi-step launches of
             // batch_semantics == 2 keep theirs: every lane on its own.)
             if (!multi_step) {
-                d.grid_mod->launch("hy_grid_unsample", N, 256, a, d.stream);
+                sample_mod.launch("hy_grid_unsample", N, 256, a, d.stream);
             }
             // A non-finite state was detected: stop (the outcomes of the last step are reported). With coefficients on
             // demand the lanes which did not reach a grid point in this sweep hold the coefficients of OLDER steps:
@@ -592,7 +615,11 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                 + ", " + std::to_string(n_launches) + " stepper launches for " + std::to_string(n_grid - 1u)
                 + " grid intervals"
                 + (n_rollbacks != 0u ? ", a non-finite lane: rolled back to the start of the grid and redone in single-step sweeps"
-                                     : ""));
+                                     : "")
+                + (gov != nullptr ? ", " + std::to_string(gov->sec.n_obs) + " observables over " + std::to_string(gov->sec.rows.size())
+                                        + " of " + std::to_string(dim) + " state rows, samples held "
+                                        + (gov->sec.staged ? "in the staging buffer" : "in registers")
+                                  : std::string{}));
     }
     if (multi_step && any_step) {
         // (The accumulated counters / extrema take the place of the last launch's own.)
@@ -617,12 +644,16 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
 // grid[point * N + lane]; return value ret[(point * dim + var) * N + lane], NaN where not reached.
 std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                              const std::vector<double> &max_delta_ts_, const cb_t &cb, double *d_out,
-                                             const pre_t &pre, const red_t &red, bool lib_cb)
+                                             const pre_t &pre, const red_t &red, bool lib_cb,
+                                             const std::vector<expression> *obs)
 {
     auto &d = *m_impl;
     const auto N = d.N;
     const auto dim = d.dim;
     const auto pinf = std::numeric_limits<double>::infinity();
+
+    // Grid observables: the checks against the system before anything runs; n_col columns per grid point.
+    const std::size_t n_col = obs != nullptr ? d.get_go_variant(*obs).sec.n_obs : dim;
 
     if (grid.empty()) {
         throw std::invalid_argument(
@@ -695,7 +726,7 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     if (d_out != nullptr && cb) {
         throw std::invalid_argument("propagate_grid() with a device output buffer does not support callbacks");
     }
-    std::vector<double> retval(d_out != nullptr ? 0u : grid.size() * dim, std::numeric_limits<double>::quiet_NaN());
+    std::vector<double> retval(d_out != nullptr ? 0u : grid.size() * n_col, std::numeric_limits<double>::quiet_NaN());
     std::vector<double> pgrid_tmp(gp, gp + N);
 
     // Propagate up to the first grid point (absorbs the low part of the double-length time).
@@ -713,7 +744,10 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     }
     if (d_out == nullptr) {
         d.to_host();
-        std::copy(d.state.begin(), d.state.end(), retval.begin());
+        // (With observables row 0 is computed on the device, hy_grid_obs0.)
+        if (obs == nullptr) {
+            std::copy(d.state.begin(), d.state.end(), retval.begin());
+        }
     } else {
         d.times_to_host();
     }
@@ -739,8 +773,24 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     // (A pure angle_reducer callback runs hy_angle_reduce after every sweep: no fused grid launches.)
     d.cb_is_library = cb && lib_cb;
     d.last_cb_path = cb ? (d.cb_is_library ? 4 : (red ? 2 : 1)) : 0;
-    propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb);
+    propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb, obs);
     return retval;
+}
+
+// ---- grid observables ----
+void tab_core::prepare_grid_observables(const std::vector<expression> &obs)
+{
+    (void)m_impl->get_go_variant(obs);
+}
+
+const std::string &tab_core::grid_observables_source(const std::vector<expression> &obs)
+{
+    return m_impl->get_go_variant(obs).source;
+}
+
+const std::vector<char> &tab_core::grid_observables_code_object(const std::vector<expression> &obs)
+{
+    return m_impl->get_go_variant(obs).cm->code;
 }
 
 // ---- callback::angle_reducer ----

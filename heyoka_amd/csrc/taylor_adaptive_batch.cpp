@@ -904,6 +904,10 @@ void tab_core::set_device(int device)
         v.dm.reset();
     }
     d.d_sa_cnt = {};
+    for (auto &[k, v] : d.go_variants) {
+        (void)k;
+        v.dm.reset();
+    }
     d.d_ev_log = {};
     d.d_evr_isrec = {};
     d.d_evr_lane = {};

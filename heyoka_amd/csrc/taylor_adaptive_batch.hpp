@@ -226,7 +226,17 @@ public:
     std::vector<double> propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                        const std::vector<double> &max_delta_ts, const cb_t &cb,
                                        double *d_out = nullptr, const pre_t &pre = {}, const red_t &red = {},
-                                       bool lib_cb = false);
+                                       bool lib_cb = false, const std::vector<expression> *obs = nullptr);
+    // ---- grid observables (grid_observables.hpp) ----
+    // obs != nullptr in propagate_grid(): the output has one column per observable - ret[(point * n_obs + o) * N + lane] -,
+    // bit for bit cfunc(obs, vars = state variables) of the state sample, the parameters and the grid time of the row; NaN
+    // in every column of a row which was not reached. Everything else is as without observables.
+    // The checks against the system (std::invalid_argument: an empty list, a variable which is not a state variable, a
+    // par[i] the integrator does not have) and the compilation of the module. No GPU is needed.
+    void prepare_grid_observables(const std::vector<expression> &obs);
+    // HIP source and gfx950 code object of the post-step module with the section of obs (compiled on first use).
+    [[nodiscard]] const std::string &grid_observables_source(const std::vector<expression> &obs);
+    [[nodiscard]] const std::vector<char> &grid_observables_code_object(const std::vector<expression> &obs);
     // x -= 2 pi floor(x / 2 pi) on the state variables idx (sorted, < get_dim()) of every system - what the call operator
     // of callback::angle_reducer does: kernel hy_angle_reduce on the integrator's stream over the device-resident state
     // (no download, no switch to eager synchronisation), or on the host mirror when that is the newer copy.
@@ -260,7 +270,7 @@ public:
     void propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                     const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
                                     const std::vector<double> &max_delta_ts, std::size_t max_steps,
-                                    double *d_out, const cb_t &cb);
+                                    double *d_out, const cb_t &cb, const std::vector<expression> *obs = nullptr);
     // ---- events (reference: taylor.hpp:1008-1014) ----
     [[nodiscard]] bool with_events() const;
     [[nodiscard]] const std::vector<core_t_event> &get_t_events() const;
@@ -1083,8 +1093,16 @@ public:
     {
         auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib);
-        return {std::move(*user_cb), std::move(ret)};
+        if constexpr (kw::has_v<kw::observables_tag, KwArgs...>) {
+            // (kw::observables: the checks against the system come before anything runs.)
+            const std::vector<expression> obs(kw::get(kw::observables, 0, kw_args...));
+            m_core.prepare_grid_observables(obs);
+            auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib, &obs);
+            return {std::move(*user_cb), std::move(ret)};
+        } else {
+            auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib);
+            return {std::move(*user_cb), std::move(ret)};
+        }
     }
 
     // MI355X extensions.

@@ -637,6 +637,30 @@ int hy_tab_propagate_grid(hy_tab, const double *grid, size_t n_grid, uint64_t ma
  * src/ensemble_propagate.cpp:266-273), otherwise n_grid * batch_size values. */
 int hy_tab_propagate_grid_device(hy_tab, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
                                  const double *max_delta_ts, size_t n_mdt, double *d_out);
+/* Grid observables (MI355X extension, no counterpart in the reference; heyoka_amd/csrc/grid_observables.hpp): n_obs expressions
+ * over the state variables of the system, par[...] and the time. out holds n_grid * n_obs * batch_size values laid out
+ * out[(point * n_obs + observable) * batch_size + lane] - the layout of hy_tab_propagate_grid() with n_eq replaced by n_obs.
+ * The post-step kernel of the grid loop evaluates the dense output of the state rows the observables read and the
+ * observables themselves: a reached row holds, bit for bit, what a hy_cfunc of the same expressions over the state variables
+ * returns for the state sample hy_tab_propagate_grid() writes for that row, the parameters of the lane and the grid time of
+ * the row and lane; a row which was not reached (step limit, callback stop, non-finite lane, retired system) is NaN in every
+ * column. State, times, outcomes, step counts, min / max |h| and Taylor coefficients are those of the call without
+ * observables. cbs / n_cbs as in hy_tab_propagate_grid_cbs() (NULL / 0: no callback). HY_ERR_INVALID_ARGUMENT before
+ * anything runs for a null handle, a null expression, an empty list, a variable which is not a state variable and a par[i]
+ * the integrator does not have. */
+int hy_tab_propagate_grid_obs(hy_tab, const double *grid, size_t n_grid, uint64_t max_steps, const double *max_delta_ts,
+                              size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
+                              double *out);
+/* The same into a caller-owned device buffer d_out of n_grid * n_obs * batch_size doubles; no callback; scalar_grid as in
+ * hy_tab_propagate_grid_device(). */
+int hy_tab_propagate_grid_obs_device(hy_tab, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                     const double *max_delta_ts, size_t n_mdt, const hy_expr *obs, size_t n_obs, double *d_out);
+/* INTERNAL hooks of the test suite: the HIP source of the post-step module with the section of the observables (kernels
+ * hy_grid_post, hy_grid_obs0, hy_grid_unsample) for a system, without an integrator and without a GPU (caller frees; NULL
+ * and hy_last_error() on error), and source (caller frees) / gfx950 code object (owned by the library) of the module
+ * inside an integrator. HEYOKA_AMD_GRID_OBS=registers|staged overrides how the kernel holds the samples of a grid point. */
+char *hy_grid_obs_source(hy_sys, const hy_expr *obs, size_t n_obs, uint32_t order, int high_accuracy);
+int hy_tab_grid_obs_module(hy_tab, const hy_expr *obs, size_t n_obs, char **source, const char **data, size_t *size);
 /* get_propagate_res(): (outcome, min |h|, max |h|, n_steps) per lane. */
 int hy_tab_get_propagate_res(hy_tab, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps);
 
