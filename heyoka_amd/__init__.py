@@ -64,6 +64,7 @@ __all__ = [
     "step_action",
     "step_action_source",
     "grid_observables_source",
+    "GRID_STATISTICS",
     "event_log",
     "callback",
     "diff",
@@ -1130,12 +1131,34 @@ def step_action_source(sys, action):
     return take_str(check_handle(lib.hy_step_action_source(s._h, action._h)))
 
 
-def grid_observables_source(sys, observables, order=20, high_accuracy=False):
+GRID_STATISTICS = ("min", "max", "t_min", "t_max", "sum", "last", "count")
+
+
+def _grid_statistics(statistics, observables):
+    """The HY_GRID_STAT_* codes of a list of names as a C array: (codes, array). The checks which need no library call are
+    made here, with the messages of the library; the empty list and the statistic named twice are the library's."""
+    if observables is None:
+        raise ValueError("The statistics of propagate_grid() need a list of observables")
+    codes = []
+    for s in statistics:
+        if s not in GRID_STATISTICS:
+            raise ValueError("The statistic %r of propagate_grid() is unknown: one of %s" % (s, ", ".join(GRID_STATISTICS)))
+        codes.append(GRID_STATISTICS.index(s))
+    return codes, (ctypes.c_int * max(len(codes), 1))(*codes)
+
+
+def grid_observables_source(sys, observables, order=20, high_accuracy=False, statistics=None):
     """HIP source of the post-step module of propagate_grid() with the section of ``observables`` for the system ``sys`` at
     the Taylor order ``order``: no integrator, no GPU. ``HEYOKA_AMD_GRID_OBS=registers|staged`` overrides how the kernel
-    holds the samples of a grid point (default: registers up to 64 state rows read, the staging buffer beyond)."""
+    holds the samples of a grid point (default: registers up to 64 state rows read, the staging buffer beyond).
+    ``statistics``: the module which folds the observables into these statistics (see propagate_grid())."""
     s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
+    if statistics is not None:
+        codes, sarr = _grid_statistics(statistics, observables)
     obs, oarr = _handle_array(list(observables))
+    if statistics is not None:
+        return take_str(check_handle(lib.hy_grid_stats_source(s._h, oarr, len(obs), sarr, len(codes), int(order),
+                                                              int(bool(high_accuracy)))))
     return take_str(check_handle(lib.hy_grid_obs_source(s._h, oarr, len(obs), int(order), int(bool(high_accuracy)))))
 
 
@@ -1885,13 +1908,22 @@ class taylor_adaptive_batch:
     def propagate_for(self, delta_t, max_steps=0, max_delta_t=None, callback=None, write_tc=False, c_output=False):
         return self._propagate(lib.hy_tab_propagate_for, delta_t, max_steps, max_delta_t, callback, write_tc, c_output)
 
-    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None, observables=None):
+    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None, observables=None, statistics=None):
         """propagate_grid(): ``(callback, out)`` with ``out[point, var, lane]``, NaN where not reached. ``observables`` (an
         MI355X extension): a list of expressions over the state variables, ``par[...]`` and ``hy.time`` -
         ``out[point, observable, lane]`` then holds, bit for bit, ``cfunc(observables, vars=state variables)`` of the state
         sample, the parameters of the lane and the grid time of the row, evaluated inside the post-step kernel of the grid
         loop from the dense output of the state rows the observables read; a row which was not reached is NaN in every
-        column. Everything else is as without observables."""
+        column. Everything else is as without observables.
+
+        ``statistics`` (only with ``observables``): a list of names out of ``min, max, t_min, t_max, sum, last, count`` - the
+        observables are folded over the grid points every system reaches, in ascending order, and ``out[observable,
+        statistic, lane]`` is returned; nothing of the size of the grid is allocated for the output. ``min`` / ``max`` ignore
+        NaN values unless all are NaN, ``t_min`` / ``t_max`` are the first grid times at which they were attained, ``sum`` is
+        one rounded addition per point, ``count`` the number of points reached. The integrator is left as by the call with
+        ``observables`` alone."""
+        if statistics is not None:
+            codes, sarr = _grid_statistics(statistics, observables)
         g = _f64(grid)
         if g.ndim == 1:
             g = np.repeat(g[:, None], self.batch_size, axis=1)
@@ -1899,7 +1931,10 @@ class taylor_adaptive_batch:
         n_grid = g.shape[0]
         if observables is not None:
             obs, oarr = _handle_array(list(observables))
-        out = np.empty((n_grid, self.dim if observables is None else len(obs), self.batch_size))
+        if statistics is not None:
+            out = np.empty((len(obs), len(codes), self.batch_size))
+        else:
+            out = np.empty((n_grid, self.dim if observables is None else len(obs), self.batch_size))
         if max_delta_t is None:
             mptr, mn, mkeep = None, 0, None
         else:
@@ -1910,6 +1945,9 @@ class taylor_adaptive_batch:
         if observables is None:
             rc = lib.hy_tab_propagate_grid_cbs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
                                                out.ctypes.data)
+        elif statistics is not None:
+            rc = lib.hy_tab_propagate_grid_stats(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
+                                                 oarr, len(obs), sarr, len(codes), out.ctypes.data)
         else:
             rc = lib.hy_tab_propagate_grid_obs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
                                                oarr, len(obs), out.ctypes.data)
@@ -1920,11 +1958,15 @@ class taylor_adaptive_batch:
         raise_for(rc)
         return callback, out
 
-    def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None, observables=None):
+    def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None, observables=None, statistics=None):
         """propagate_grid() with the samples written to a caller-owned device buffer (``out_ptr``: device address of
         n_grid * dim * batch_size doubles, layout [point, var, lane]); ``grid``: 1-D (shared by all the lanes) or
         (n_grid, batch_size). Nothing of that size is materialised on the host. With ``observables`` (see
-        propagate_grid()) the buffer holds n_grid * len(observables) * batch_size doubles, layout [point, observable, lane]."""
+        propagate_grid()) the buffer holds n_grid * len(observables) * batch_size doubles, layout [point, observable, lane];
+        with ``statistics`` as well, len(observables) * len(statistics) * batch_size doubles, layout [observable, statistic,
+        lane]."""
+        if statistics is not None:
+            codes, sarr = _grid_statistics(statistics, observables)
         g = np.ascontiguousarray(_f64(grid))
         scalar = g.ndim == 1
         if max_delta_t is None:
@@ -1934,18 +1976,29 @@ class taylor_adaptive_batch:
             mptr, mn = mkeep.ctypes.data, mkeep.size
         if observables is not None:
             obs, oarr = _handle_array(list(observables))
+            if statistics is not None:
+                raise_for(lib.hy_tab_propagate_grid_stats_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
+                                                                 mptr, mn, oarr, len(obs), sarr, len(codes),
+                                                                 ctypes.c_void_p(int(out_ptr))))
+                return
             raise_for(lib.hy_tab_propagate_grid_obs_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
                                                            mptr, mn, oarr, len(obs), ctypes.c_void_p(int(out_ptr))))
             return
         raise_for(lib.hy_tab_propagate_grid_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
                                                    mptr, mn, ctypes.c_void_p(int(out_ptr))))
 
-    def grid_observables_module(self, observables):
+    def grid_observables_module(self, observables, statistics=None):
         """(HIP source, gfx950 code object) of the post-step module of propagate_grid() with the section of ``observables``
         (kernels hy_grid_post, hy_grid_obs0, hy_grid_unsample) in this integrator: checked against its system and compiled
-        on first use. No GPU is needed."""
+        on first use. No GPU is needed. ``statistics``: the module which folds them (see propagate_grid())."""
+        if statistics is not None:
+            codes, sarr = _grid_statistics(statistics, observables)
         obs, oarr = _handle_array(list(observables))
         src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        if statistics is not None:
+            raise_for(lib.hy_tab_grid_stats_module(self._h, oarr, len(obs), sarr, len(codes), ctypes.byref(src),
+                                                   ctypes.byref(data), ctypes.byref(n)))
+            return take_str(src.value), ctypes.string_at(data.value, n.value)
         raise_for(lib.hy_tab_grid_obs_module(self._h, oarr, len(obs), ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
         return take_str(src.value), ctypes.string_at(data.value, n.value)
 

@@ -282,6 +282,19 @@ SIGNATURES = [
     ),
     ("hy_grid_obs_source", c_void_p, [c_void_p, c_void_p, c_size_t, ctypes.c_uint32, c_int]),
     ("hy_tab_grid_obs_module", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    (
+        "hy_tab_propagate_grid_stats",
+        c_int,
+        [c_void_p, c_void_p, c_size_t, c_uint64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+         c_void_p],
+    ),
+    (
+        "hy_tab_propagate_grid_stats_device",
+        c_int,
+        [c_void_p, c_void_p, c_size_t, c_int, c_uint64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p],
+    ),
+    ("hy_grid_stats_source", c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_uint32, c_int]),
+    ("hy_tab_grid_stats_module", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     ("hy_tab_get_propagate_res", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("hy_model_nbody_ex", c_void_p, [c_uint32, c_void_p, c_size_t, c_void_p]),
     ("hy_model_nbody_energy", c_void_p, [c_uint32, c_void_p, c_size_t, c_void_p]),

@@ -2092,6 +2092,101 @@ int hy_tab_grid_obs_module(hy_tab t, const hy_expr *obs, size_t n_obs, char **so
         }
     });
 }
+// ---- grid statistics (grid_observables.hpp) ----
+namespace
+{
+
+std::vector<grid_statistic> stats_from(const char *fn, const int *stats, size_t n_stats)
+{
+    if (stats == nullptr && n_stats != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of statistics is null");
+    }
+    return detail::grid_statistics_from_codes(stats, n_stats);
+}
+
+} // namespace
+
+int hy_tab_propagate_grid_stats(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
+                                size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
+                                const int *stats, size_t n_stats, double *out)
+{
+    return guarded([&] {
+        check_tab("hy_tab_propagate_grid_stats", t);
+        const auto ov = obs_from("hy_tab_propagate_grid_stats", obs, n_obs);
+        const auto sv = stats_from("hy_tab_propagate_grid_stats", stats, n_stats);
+        // (The checks against the system come before the callbacks are touched and before anything runs.)
+        t->core.prepare_grid_statistics(ov, sv);
+        const auto bs = t->core.get_batch_size();
+        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
+        auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
+                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red, lib_cb, &ov, &sv);
+        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
+    });
+}
+int hy_tab_propagate_grid_stats_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                       const double *mdts, size_t n_mdt, const hy_expr *obs, size_t n_obs, const int *stats,
+                                       size_t n_stats, double *d_out)
+{
+    return guarded([&] {
+        check_tab("hy_tab_propagate_grid_stats_device", t);
+        const auto ov = obs_from("hy_tab_propagate_grid_stats_device", obs, n_obs);
+        const auto sv = stats_from("hy_tab_propagate_grid_stats_device", stats, n_stats);
+        t->core.prepare_grid_statistics(ov, sv);
+        const auto bs = t->core.get_batch_size();
+        std::vector<double> g;
+        if (scalar_grid != 0) {
+            g.reserve(n_grid * bs);
+            for (size_t k = 0; k < n_grid; ++k) {
+                g.insert(g.end(), bs, grid[k]);
+            }
+        } else {
+            g = vec_from(grid, n_grid * bs);
+        }
+        if (d_out == nullptr) {
+            throw std::invalid_argument("hy_tab_propagate_grid_stats_device(): the device output pointer is null");
+        }
+        t->core.propagate_grid(std::move(g), static_cast<std::size_t>(max_steps), expand_mdt(mdts, n_mdt, bs), {}, d_out, {}, {},
+                               false, &ov, &sv);
+    });
+}
+char *hy_grid_stats_source(hy_sys sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, uint32_t order,
+                           int high_accuracy)
+{
+    try {
+        if (sys == nullptr) {
+            throw std::invalid_argument("hy_grid_stats_source(): the system handle is null");
+        }
+        const auto ov = obs_from("hy_grid_stats_source", obs, n_obs);
+        const auto sv = stats_from("hy_grid_stats_source", stats, n_stats);
+        const auto svars = detail::state_variables_of(sys->sys);
+        auto sec = detail::make_grid_obs_section(ov, svars, std::numeric_limits<std::uint32_t>::max());
+        detail::set_grid_statistics(sec, sv);
+        return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+int hy_tab_grid_stats_module(hy_tab t, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
+                             const char **data, size_t *size)
+{
+    return guarded([&] {
+        check_tab("hy_tab_grid_stats_module", t);
+        const auto ov = obs_from("hy_tab_grid_stats_module", obs, n_obs);
+        const auto sv = stats_from("hy_tab_grid_stats_module", stats, n_stats);
+        const auto &src = t->core.grid_statistics_source(ov, sv);
+        const auto &co = t->core.grid_statistics_code_object(ov, sv);
+        if (source != nullptr) {
+            *source = dup_str(src);
+        }
+        if (data != nullptr) {
+            *data = co.data();
+        }
+        if (size != nullptr) {
+            *size = co.size();
+        }
+    });
+}
 int hy_tab_get_propagate_res(hy_tab t, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps)
 {
     return guarded([&] {

@@ -5,6 +5,20 @@
 // observables read, runs the straight-line section of detail::emit_order0() (cfunc.hpp) on them and stores the results:
 // a reached row holds, bit for bit, what cfunc(observables, vars = state variables) returns for the state sample of that
 // row, the parameters of the lane and the grid time of the row; a row which is not reached is NaN in every column.
+//
+// Grid statistics: with a list of statistics next to the observables nothing is stored per grid point. Let
+// y_g be the value of an observable of a lane at the g-th grid point the lane reaches (g = 0 ... r - 1, a prefix of its grid)
+// and t_g the grid time of that row. Every (observable, statistic) is one double per lane, folded in ascending g:
+//   min / max   m = y_0; then, if y_g < m (y_g > m) or m != m: m = y_g - NaN values are ignored unless all are NaN, -0.0 does
+//               not replace +0.0;
+//   t_min / t_max   the grid time at which the current minimum / maximum was first attained;
+//   sum         s = y_0, then s = s + y_g, one rounded addition per point (NaN propagates);
+//   last        y_{r-1};    count   r as a double.
+// With r = 0 (the first grid point was not reached) every statistic is NaN and count is 0. The output is
+// out[(observable * n_stat + statistic) * N + lane], statistics in the order of the list. The accumulators are those slots,
+// followed by hidden ones (the extremum behind a t_min / t_max which was asked for alone): n_slots * N doubles owned by their
+// lanes, read and written by hy_grid_post at every grid point, with a shadow copy of the same size behind them - a sweep
+// which merges copies the lane's slots there first, and hy_grid_unsample puts them back where the plain module clears rows.
 #pragma once
 
 #include <cstdint>
@@ -13,6 +27,7 @@
 
 #include "decompose.hpp"
 #include "expression.hpp"
+#include "kw.hpp"
 
 namespace heyoka_amd::detail
 {
@@ -25,6 +40,9 @@ struct grid_obs_section {
     // false: registers (the rows are named scalars), true: staged (the rows go through hy_grid_args::stage).
     bool staged = false;
     taylor_program prog;
+    // Grid statistics, empty: none. n_slots: accumulators per lane, the n_obs * stats.size() of the output first.
+    std::vector<grid_statistic> stats;
+    std::uint32_t n_slots = 0;
 };
 
 // The largest number of rows held in registers: see DESIGN 4.3e for the budget.
@@ -38,9 +56,27 @@ grid_obs_section make_grid_obs_section(const std::vector<expression> &obs, const
 // make_grid_source() (taylor_adaptive_batch.hpp) with the section: hy_grid_post samples the rows of the section only and
 // stores HY_NOUT columns per grid point, hy_grid_unsample clears HY_NOUT columns, hy_grid_obs0 computes row 0 from the
 // current state. The other kernels of the module are those of the plain module.
+// With statistics in the section (set_grid_statistics()): hy_grid_post folds the HY_NOUT values of a grid point into the
+// HY_NSLOT accumulators of the lane instead of storing them, hy_grid_obs0 starts the accumulators, hy_grid_unsample puts
+// them back from their shadow copy. Without statistics the text is, byte for byte, the one of a section without the field.
 std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool high_accuracy, const grid_obs_section *sec);
 
 // The key of the module of a list of observables inside an integrator: their text and the way of holding the samples.
 std::string grid_obs_key(const std::vector<expression> &obs);
+
+// ---- grid statistics ----
+inline constexpr const char *grid_statistic_names[] = {"min", "max", "t_min", "t_max", "sum", "last", "count"};
+inline constexpr int n_grid_statistics = 7;
+
+// The statistics of a list of codes. std::invalid_argument: an empty list, an unknown code, a statistic named twice.
+std::vector<grid_statistic> grid_statistics_from_codes(const int *codes, std::size_t n);
+// The same checks on a list which is already typed (an enumerator may have been cast from anything).
+void check_grid_statistics(const std::vector<grid_statistic> &stats);
+// sec with the statistics: make_grid_source() then emits the variant which folds (checks as above).
+void set_grid_statistics(grid_obs_section &sec, const std::vector<grid_statistic> &stats);
+// grid_obs_key() of the module with statistics.
+std::string grid_obs_key(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats);
+// The message of the front ends for statistics without observables.
+inline constexpr const char *grid_statistics_need_observables = "The statistics of propagate_grid() need a list of observables";
 
 } // namespace heyoka_amd::detail

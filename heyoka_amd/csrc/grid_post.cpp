@@ -74,6 +74,82 @@ std::string grid_obs_key(const std::vector<expression> &obs)
     return key + "|" + (env != nullptr ? env : "");
 }
 
+// ---- grid statistics ----
+void check_grid_statistics(const std::vector<grid_statistic> &stats)
+{
+    if (stats.empty()) {
+        throw std::invalid_argument("The list of statistics of propagate_grid() is empty");
+    }
+    std::set<int> seen;
+    for (const auto s : stats) {
+        const auto code = static_cast<int>(s);
+        if (code < 0 || code >= n_grid_statistics) {
+            throw std::invalid_argument("The statistic code " + std::to_string(code) + " of propagate_grid() is unknown");
+        }
+        if (!seen.insert(code).second) {
+            throw std::invalid_argument(std::string("The statistic '") + grid_statistic_names[code]
+                                        + "' of propagate_grid() is named twice");
+        }
+    }
+}
+
+std::vector<grid_statistic> grid_statistics_from_codes(const int *codes, std::size_t n)
+{
+    std::vector<grid_statistic> ret;
+    for (std::size_t k = 0; k < n; ++k) {
+        ret.push_back(static_cast<grid_statistic>(codes[k]));
+    }
+    check_grid_statistics(ret);
+    return ret;
+}
+
+namespace
+{
+
+// The slots of the accumulators of one observable, by statistic (-1: not kept): those of the output, o * n_stat + position in
+// the list, and behind all of them the extremum a t_min / t_max needs when it was asked for alone.
+struct stat_slots {
+    int slot[n_grid_statistics];
+};
+
+std::vector<stat_slots> grid_stat_slots(std::uint32_t n_obs, const std::vector<grid_statistic> &stats, std::uint32_t &n_slots)
+{
+    const auto n_stat = static_cast<std::uint32_t>(stats.size());
+    n_slots = n_obs * n_stat;
+    std::vector<stat_slots> ret(n_obs);
+    for (std::uint32_t o = 0; o < n_obs; ++o) {
+        auto &s = ret[o].slot;
+        std::fill(std::begin(s), std::end(s), -1);
+        for (std::uint32_t k = 0; k < n_stat; ++k) {
+            s[static_cast<int>(stats[k])] = static_cast<int>(o * n_stat + k);
+        }
+        for (const auto &[tm, m] : {std::pair{grid_statistic::t_min, grid_statistic::min}, std::pair{grid_statistic::t_max, grid_statistic::max}}) {
+            if (s[static_cast<int>(tm)] >= 0 && s[static_cast<int>(m)] < 0) {
+                s[static_cast<int>(m)] = static_cast<int>(n_slots++);
+            }
+        }
+    }
+    return ret;
+}
+
+} // namespace
+
+void set_grid_statistics(grid_obs_section &sec, const std::vector<grid_statistic> &stats)
+{
+    check_grid_statistics(stats);
+    sec.stats = stats;
+    (void)grid_stat_slots(sec.n_obs, stats, sec.n_slots);
+}
+
+std::string grid_obs_key(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats)
+{
+    auto key = grid_obs_key(obs) + "|statistics:";
+    for (const auto s : stats) {
+        key += std::to_string(static_cast<int>(s)) + ",";
+    }
+    return key;
+}
+
 namespace
 {
 
@@ -130,11 +206,24 @@ std::string grid_obs_device_functions(const grid_obs_section &sec)
         src << (j != 0u ? ", " : "") << sec.rows[j] << "u";
     }
     src << "};\n";
-    src << R"HIP(
+    const bool folds = !sec.stats.empty();
+    if (folds) {
+        src << R"HIP(
+// Grid statistics: the accumulators of a lane are the slots out[s * N + i], s < HY_NSLOT - those of the output first -, and
+// out[(HY_NSLOT + s) * N + i] is their shadow copy.
+#define HY_NSLOT )HIP" << sec.n_slots << R"HIP(u
+
+// The observables of lane i at grid point g and time t_hi, folded into the accumulators of the lane: outp points to out[i]
+// (and stg to the staged samples of the lane). g == 0: the accumulators start from these values.
+__device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 i, const u64 N, double *outp, const unsigned g, const double t_hi
+)HIP";
+    } else {
+        src << R"HIP(
 // The observables of lane i at grid point g and time t_hi, stored to out[(g * HY_NOUT + o) * N + i]: outp points to out[i]
 // (and stg to the staged samples of the lane).
 __device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 i, const u64 N, double *outp, const unsigned g, const double t_hi
 )HIP";
+    }
     if (sec.staged) {
         src << ", const double *stg";
     } else {
@@ -153,10 +242,65 @@ __device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 
         src << d;
     }
     src << code.body;
-    for (std::size_t o = 0; o < code.outs.size(); ++o) {
-        src << "outp[((u64)g * HY_NOUT + " << o << "u) * N] = " << code.outs[o] << ";\n";
+    if (!folds) {
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            src << "outp[((u64)g * HY_NOUT + " << o << "u) * N] = " << code.outs[o] << ";\n";
+        }
+        src << "}\n";
+        return src.str();
     }
-    src << "}\n";
+    // The merge, behind the last value of the section: its temporaries are dead, the accumulators come from memory and go
+    // back there - nothing is held in a register across the grid loop. A value which went through an asm operand is opaque
+    // to the backend: the addition of `sum` is not contracted with a product which ends the observable.
+    std::uint32_t n_slots = 0;
+    const auto slots = grid_stat_slots(sec.n_obs, sec.stats, n_slots);
+    const auto acc = [](int s) { return "outp[(u64)" + std::to_string(s) + "u * N]"; };
+    const auto sl = [&](std::size_t o, grid_statistic s) { return slots[o].slot[static_cast<int>(s)]; };
+    for (std::size_t o = 0; o < code.outs.size(); ++o) {
+        src << "double y" << o << " = " << code.outs[o] << ";\nasm volatile(\"\" : \"+v\"(y" << o << "));\n";
+    }
+    src << "if (g == 0u) {\n";
+    for (std::size_t o = 0; o < code.outs.size(); ++o) {
+        for (const auto s : {grid_statistic::min, grid_statistic::max, grid_statistic::sum, grid_statistic::last}) {
+            if (sl(o, s) >= 0) {
+                src << acc(sl(o, s)) << " = y" << o << ";\n";
+            }
+        }
+        for (const auto s : {grid_statistic::t_min, grid_statistic::t_max}) {
+            if (sl(o, s) >= 0) {
+                src << acc(sl(o, s)) << " = t_hi;\n";
+            }
+        }
+        if (sl(o, grid_statistic::count) >= 0) {
+            src << acc(sl(o, grid_statistic::count)) << " = 1.0;\n";
+        }
+    }
+    src << "} else {\n";
+    for (std::size_t o = 0; o < code.outs.size(); ++o) {
+        const auto extremum = [&](grid_statistic m, grid_statistic tm, const char *cmp) {
+            if (sl(o, m) < 0) {
+                return;
+            }
+            src << "{ const double m = " << acc(sl(o, m)) << "; if (y" << o << " " << cmp << " m || m != m) { " << acc(sl(o, m))
+                << " = y" << o << "; ";
+            if (sl(o, tm) >= 0) {
+                src << acc(sl(o, tm)) << " = t_hi; ";
+            }
+            src << "} }\n";
+        };
+        extremum(grid_statistic::min, grid_statistic::t_min, "<");
+        extremum(grid_statistic::max, grid_statistic::t_max, ">");
+        if (sl(o, grid_statistic::sum) >= 0) {
+            src << acc(sl(o, grid_statistic::sum)) << " = __dadd_rn(" << acc(sl(o, grid_statistic::sum)) << ", y" << o << ");\n";
+        }
+        if (sl(o, grid_statistic::last) >= 0) {
+            src << acc(sl(o, grid_statistic::last)) << " = y" << o << ";\n";
+        }
+        if (sl(o, grid_statistic::count) >= 0) {
+            src << acc(sl(o, grid_statistic::count)) << " = " << acc(sl(o, grid_statistic::count)) << " + 1.0;\n";
+        }
+    }
+    src << "}\n}\n";
     return src.str();
 }
 
@@ -427,6 +571,9 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         if (sec->staged) {
             src << "    double *stg = a.stage + i;\n    asm volatile(\"\" : \"+v\"(stg));\n";
         }
+        if (!sec->stats.empty()) {
+            src << "    bool shadowed = false;\n";
+        }
     }
     src << R"HIP(    unsigned g = a.gidx[i];
     while (g < ng) {
@@ -453,6 +600,17 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         // The coefficients do not depend on the grid point: the empty asm statements on their base address and on the stride
         // keep the loads and the scalar offsets inside the iteration of the while loop (hoisted out of it they are all alive
         // at once again).
+        if (!sec->stats.empty()) {
+            // Grid statistics: what is folded cannot be taken back - the first merge of a sweep is preceded by the copy of
+            // the lane's accumulators which hy_grid_unsample restores. Ahead of the samples: nothing of the point is alive
+            // yet. (The grid index of a lane starts at 1: row 0 is hy_grid_obs0's, and the start branch of the section goes.)
+            src << R"HIP(        if (!shadowed) {
+            for (unsigned s = 0; s < HY_NSLOT; ++s) out0[(u64)(HY_NSLOT + s) * N] = out0[(u64)s * N];
+            shadowed = true;
+        }
+        __builtin_assume(g != 0u);
+)HIP";
+        }
         src << "        const double *tcb = tc0;\n        asm volatile(\"\" : \"+v\"(tcb));\n";
         src << "        u64 Ns = N;\n        asm volatile(\"\" : \"+s\"(Ns));\n";
         if (!sec->staged) {
@@ -487,7 +645,26 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
     a.lim[i] = retire ? 0.0 : lim;
     hy_count(a.counters, g < ng);
 }
-
+)HIP";
+    if (sec != nullptr && !sec->stats.empty()) {
+        // (The lock-step sweeps in which this kernel runs retire nobody: a grid index which moved is a lane which merged, and
+        // a lane which merged has made its copy.)
+        src << R"HIP(
+// A sweep in which a lane went non-finite: the reference leaves its loop right after that step, before the dense output of
+// the step (src/taylor_adaptive_batch.cpp:1962-1968) - the lanes which merged grid points in hy_grid_post just now get back
+// the accumulators they had before. Nothing of the size of the grid is written.
+extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid_args a)
+{
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    const u64 N = a.N;
+    if (i >= N) return;
+    if (a.gidx_prev[i] < a.gidx[i]) {
+        for (unsigned s = 0; s < HY_NSLOT; ++s) a.out[(u64)s * N + i] = a.out[(u64)(HY_NSLOT + s) * N + i];
+    }
+}
+)HIP";
+    } else {
+        src << R"HIP(
 // A sweep in which a lane went non-finite: the reference leaves its loop right after that step, before the dense output of
 // the step (src/taylor_adaptive_batch.cpp:1962-1968; the samples of a step are taken at the top of the NEXT iteration,
 // :1800-1871) - the samples hy_grid_post has just taken in the other lanes are NaN again.
@@ -504,11 +681,18 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
     }
 }
 )HIP";
+    }
     if (sec != nullptr) {
-        src << R"HIP(
+        if (!sec->stats.empty()) {
+            src << "\n// The start of the accumulators: the observables of the current state at the first grid time (at the start of "
+                   "the call and\n// again after a rollback).\n";
+        } else {
+            src << R"HIP(
 // Row 0 of the output: the observables of the current state at the first grid time (at the start of the call and again
 // after a rollback).
-extern "C" __global__ void __launch_bounds__(256) hy_grid_obs0(const hy_grid_args a)
+)HIP";
+        }
+        src << R"HIP(extern "C" __global__ void __launch_bounds__(256) hy_grid_obs0(const hy_grid_args a)
 {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
     const u64 N = a.N;

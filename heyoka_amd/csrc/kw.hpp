@@ -14,6 +14,10 @@
 namespace heyoka_amd
 {
 
+// The statistics of the grid observables (kw::statistics, grid_observables.hpp). The values are the HY_GRID_STAT_* codes of the
+// C interface.
+enum class grid_statistic : int { min = 0, max = 1, t_min = 2, t_max = 3, sum = 4, last = 5, count = 6 };
+
 namespace kw
 {
 
@@ -68,6 +72,9 @@ HEYOKA_AMD_KWARG(c_output);
 // propagate_grid() / ensemble_propagate_grid_batch(), MI355X extension: kw::observables = std::vector<expression>{...} - the
 // grid output has one column per observable instead of one per state variable (grid_observables.hpp).
 HEYOKA_AMD_KWARG(observables);
+// ... and kw::statistics = std::vector<grid_statistic>{...}, only together with kw::observables: the observables are folded over
+// the grid points a system reaches, and the output is out[(observable * n_stat + statistic) * N + lane] (grid_observables.hpp).
+HEYOKA_AMD_KWARG(statistics);
 // Events (reference: include/heyoka/events.hpp:87-100).
 HEYOKA_AMD_KWARG(direction);
 HEYOKA_AMD_KWARG(cooldown);

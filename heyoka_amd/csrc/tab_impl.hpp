@@ -310,13 +310,21 @@ struct tab_core::impl {
         std::unique_ptr<aux_module> dm;
     };
     std::map<std::string, go_variant> go_variants;
-    go_variant &get_go_variant(const std::vector<expression> &obs)
+    // (stats != nullptr: the module which folds the observables into grid statistics, DESIGN 4.3f - one module per
+    // (observables, statistics).)
+    go_variant &get_go_variant(const std::vector<expression> &obs, const std::vector<grid_statistic> *stats = nullptr)
     {
-        const auto key = grid_obs_key(obs);
+        if (stats != nullptr) {
+            check_grid_statistics(*stats);
+        }
+        const auto key = stats != nullptr ? grid_obs_key(obs, *stats) : grid_obs_key(obs);
         auto it = go_variants.find(key);
         if (it == go_variants.end()) {
             go_variant v;
             v.sec = make_grid_obs_section(obs, state_variables_of(sys), prog.n_par);
+            if (stats != nullptr) {
+                set_grid_statistics(v.sec, *stats);
+            }
             v.source = make_grid_source(order, dim, high_accuracy, &v.sec);
             const detail::stopwatch sw;
             v.cm = hiprtc_compile_source(v.source);

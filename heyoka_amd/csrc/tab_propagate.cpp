@@ -383,7 +383,8 @@ std::optional<c_out_core> tab_core::take_c_output()
 void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                           const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
                                           const std::vector<double> &max_delta_ts, std::size_t max_steps,
-                                          double *d_out, const cb_t &cb, const std::vector<expression> *obs)
+                                          double *d_out, const cb_t &cb, const std::vector<expression> *obs,
+                                          const std::vector<grid_statistic> *stats)
 {
     auto &d = *m_impl;
     const auto N = d.N;
@@ -392,12 +393,25 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     const auto pinf = std::numeric_limits<double>::infinity();
     const auto dsz = sizeof(double);
 
+    const auto stat_names = [](const std::vector<grid_statistic> &v) {
+        std::string ret;
+        for (const auto s : v) {
+            ret += (ret.empty() ? "" : ", ") + std::string(grid_statistic_names[static_cast<int>(s)]);
+        }
+        return ret;
+    };
+
     d.ensure_device();
     d.ensure_tc();
     d.ensure_grid_mod();
     // Grid observables: the post-step module with their section takes the place of the plain one for the
     // samples - hy_grid_post, hy_grid_unsample, and hy_grid_obs0 for row 0 -, one column per observable.
-    auto *const gov = obs != nullptr ? &d.get_go_variant(*obs) : nullptr;
+    // Grid statistics: the variant of that module which folds. Its output buffer holds the accumulators of the
+    // lanes, n_slots * N doubles with those of the result first, and their shadow copy behind them - whatever the caller gets,
+    // host vector or device buffer, is the first n_obs * n_stat * N of them, copied at the end.
+    auto *const gov = obs != nullptr ? &d.get_go_variant(*obs, stats) : nullptr;
+    const bool folds = stats != nullptr;
+    const std::size_t n_res = folds ? gov->sec.n_obs * stats->size() * N : 0u;
     if (gov != nullptr && !gov->dm) {
         gov->dm = std::make_unique<aux_module>(gov->cm, d.device);
     }
@@ -405,9 +419,9 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     const std::size_t n_col = gov != nullptr ? gov->sec.n_obs : dim;
     device_buffer b_stage((gov != nullptr && gov->sec.staged) ? static_cast<std::size_t>(dim) * N * dsz : 0u, d.device);
 
-    const auto out_doubles = grid.size() * n_col;
-    device_buffer b_grid(grid.size() * dsz, d.device), b_out(d_out != nullptr ? 0u : out_doubles * dsz, d.device);
-    double *const out_ptr = d_out != nullptr ? d_out : b_out.as<double>();
+    const auto out_doubles = folds ? 2u * gov->sec.n_slots * static_cast<std::size_t>(N) : grid.size() * n_col;
+    device_buffer b_grid(grid.size() * dsz, d.device), b_out((d_out != nullptr && !folds) ? 0u : out_doubles * dsz, d.device);
+    double *const out_ptr = (d_out != nullptr && !folds) ? d_out : b_out.as<double>();
     device_buffer b_rem_hi(N * dsz, d.device), b_rem_lo(N * dsz, d.device), b_mdt(N * dsz, d.device);
     device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(6u * sizeof(unsigned), d.device),
         b_gidx_prev(N * sizeof(unsigned), d.device);
@@ -426,8 +440,12 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     device_buffer b_next_tg(N * dsz, d.device);
     // The samples and the per-lane bookkeeping at the first grid point: at the start, and again after a rollback (below).
     const auto init_grid_state = [&]() {
-        // Row 0 = current state, everything else NaN until reached.
-        if (d_out == nullptr) {
+        // Row 0 = current state, everything else NaN until reached. (Statistics: hy_grid_obs0 below writes every accumulator.)
+        if (folds) {
+            if (d_out != nullptr) {
+                d.to_device();
+            }
+        } else if (d_out == nullptr) {
             b_out.upload(retval.data(), retval.size() * dsz, d.stream);
         } else {
             // NOTE: the all-ones byte pattern is a (quiet) NaN.
@@ -619,7 +637,10 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                 + (gov != nullptr ? ", " + std::to_string(gov->sec.n_obs) + " observables over " + std::to_string(gov->sec.rows.size())
                                         + " of " + std::to_string(dim) + " state rows, samples held "
                                         + (gov->sec.staged ? "in the staging buffer" : "in registers")
-                                  : std::string{}));
+                                  : std::string{})
+                + (folds ? ", statistics " + stat_names(*stats) + " folded over the grid (" + std::to_string(gov->sec.n_slots)
+                               + " accumulators per system)"
+                         : std::string{}));
     }
     if (multi_step && any_step) {
         // (The accumulated counters / extrema take the place of the last launch's own.)
@@ -632,7 +653,10 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         d.prop_res_dev_newer = true;
         d.step_res_dev_newer = true;
     }
-    if (d_out == nullptr) {
+    if (folds && d_out != nullptr) {
+        device_copy(d_out, b_out.get(), n_res * dsz, d.device, d.stream);
+        stream_synchronize(d.device, d.stream);
+    } else if (d_out == nullptr) {
         b_out.download(retval.data(), retval.size() * dsz, d.stream);
     } else {
         stream_synchronize(d.device, d.stream);
@@ -645,7 +669,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
 std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                              const std::vector<double> &max_delta_ts_, const cb_t &cb, double *d_out,
                                              const pre_t &pre, const red_t &red, bool lib_cb,
-                                             const std::vector<expression> *obs)
+                                             const std::vector<expression> *obs, const std::vector<grid_statistic> *stats)
 {
     auto &d = *m_impl;
     const auto N = d.N;
@@ -653,7 +677,11 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     const auto pinf = std::numeric_limits<double>::infinity();
 
     // Grid observables: the checks against the system before anything runs; n_col columns per grid point.
-    const std::size_t n_col = obs != nullptr ? d.get_go_variant(*obs).sec.n_obs : dim;
+    // (... and the statistics: retval is the reduced output, NaN and a count of zero until the loop has run.)
+    if (stats != nullptr && obs == nullptr) {
+        throw std::invalid_argument(grid_statistics_need_observables);
+    }
+    const std::size_t n_col = obs != nullptr ? d.get_go_variant(*obs, stats).sec.n_obs : dim;
 
     if (grid.empty()) {
         throw std::invalid_argument(
@@ -726,7 +754,17 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     if (d_out != nullptr && cb) {
         throw std::invalid_argument("propagate_grid() with a device output buffer does not support callbacks");
     }
-    std::vector<double> retval(d_out != nullptr ? 0u : grid.size() * n_col, std::numeric_limits<double>::quiet_NaN());
+    std::vector<double> retval(d_out != nullptr ? 0u : (stats != nullptr ? n_col * stats->size() * N : grid.size() * n_col),
+                               std::numeric_limits<double>::quiet_NaN());
+    if (stats != nullptr && d_out == nullptr) {
+        for (std::size_t k = 0; k < stats->size(); ++k) {
+            if ((*stats)[k] == grid_statistic::count) {
+                for (std::size_t o = 0; o < n_col; ++o) {
+                    std::fill_n(retval.begin() + static_cast<std::ptrdiff_t>((o * stats->size() + k) * N), N, 0.);
+                }
+            }
+        }
+    }
     std::vector<double> pgrid_tmp(gp, gp + N);
 
     // Propagate up to the first grid point (absorbs the low part of the double-length time).
@@ -773,7 +811,7 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     // (A pure angle_reducer callback runs hy_angle_reduce after every sweep: no fused grid launches.)
     d.cb_is_library = cb && lib_cb;
     d.last_cb_path = cb ? (d.cb_is_library ? 4 : (red ? 2 : 1)) : 0;
-    propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb, obs);
+    propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb, obs, stats);
     return retval;
 }
 
@@ -791,6 +829,23 @@ const std::string &tab_core::grid_observables_source(const std::vector<expressio
 const std::vector<char> &tab_core::grid_observables_code_object(const std::vector<expression> &obs)
 {
     return m_impl->get_go_variant(obs).cm->code;
+}
+
+// ---- grid statistics ----
+void tab_core::prepare_grid_statistics(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats)
+{
+    (void)m_impl->get_go_variant(obs, &stats);
+}
+
+const std::string &tab_core::grid_statistics_source(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats)
+{
+    return m_impl->get_go_variant(obs, &stats).source;
+}
+
+const std::vector<char> &tab_core::grid_statistics_code_object(const std::vector<expression> &obs,
+                                                               const std::vector<grid_statistic> &stats)
+{
+    return m_impl->get_go_variant(obs, &stats).cm->code;
 }
 
 // ---- callback::angle_reducer ----

@@ -30,6 +30,7 @@
 #include "dfloat.hpp"
 #include "event_detection.hpp"
 #include "expression.hpp"
+#include "grid_observables.hpp"
 #include "kw.hpp"
 #include "step_callback.hpp"
 #include "var_ode_sys.hpp"
@@ -226,7 +227,8 @@ public:
     std::vector<double> propagate_grid(std::vector<double> grid, std::size_t max_steps,
                                        const std::vector<double> &max_delta_ts, const cb_t &cb,
                                        double *d_out = nullptr, const pre_t &pre = {}, const red_t &red = {},
-                                       bool lib_cb = false, const std::vector<expression> *obs = nullptr);
+                                       bool lib_cb = false, const std::vector<expression> *obs = nullptr,
+                                       const std::vector<grid_statistic> *stats = nullptr);
     // ---- grid observables (grid_observables.hpp) ----
     // obs != nullptr in propagate_grid(): the output has one column per observable - ret[(point * n_obs + o) * N + lane] -,
     // bit for bit cfunc(obs, vars = state variables) of the state sample, the parameters and the grid time of the row; NaN
@@ -237,6 +239,17 @@ public:
     // HIP source and gfx950 code object of the post-step module with the section of obs (compiled on first use).
     [[nodiscard]] const std::string &grid_observables_source(const std::vector<expression> &obs);
     [[nodiscard]] const std::vector<char> &grid_observables_code_object(const std::vector<expression> &obs);
+    // ---- grid statistics (grid_observables.hpp) ----
+    // stats != nullptr in propagate_grid() (only with obs; std::invalid_argument otherwise, and for an empty list, an unknown
+    // code or a statistic named twice): the observables are folded over the grid points every system reaches, the return
+    // value is ret[(o * n_stat + k) * N + lane] (d_out: that many doubles), and nothing of the size of the grid is allocated
+    // for the output. The integrator is left, bit for bit, as by the call with obs alone.
+    // The counterparts of the three functions above.
+    void prepare_grid_statistics(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats);
+    [[nodiscard]] const std::string &grid_statistics_source(const std::vector<expression> &obs,
+                                                            const std::vector<grid_statistic> &stats);
+    [[nodiscard]] const std::vector<char> &grid_statistics_code_object(const std::vector<expression> &obs,
+                                                                       const std::vector<grid_statistic> &stats);
     // x -= 2 pi floor(x / 2 pi) on the state variables idx (sorted, < get_dim()) of every system - what the call operator
     // of callback::angle_reducer does: kernel hy_angle_reduce on the integrator's stream over the device-resident state
     // (no download, no switch to eager synchronisation), or on the host mirror when that is the newer copy.
@@ -270,7 +283,8 @@ public:
     void propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                     const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
                                     const std::vector<double> &max_delta_ts, std::size_t max_steps,
-                                    double *d_out, const cb_t &cb, const std::vector<expression> *obs = nullptr);
+                                    double *d_out, const cb_t &cb, const std::vector<expression> *obs = nullptr,
+                                    const std::vector<grid_statistic> *stats = nullptr);
     // ---- events (reference: taylor.hpp:1008-1014) ----
     [[nodiscard]] bool with_events() const;
     [[nodiscard]] const std::vector<core_t_event> &get_t_events() const;
@@ -1096,9 +1110,19 @@ public:
         if constexpr (kw::has_v<kw::observables_tag, KwArgs...>) {
             // (kw::observables: the checks against the system come before anything runs.)
             const std::vector<expression> obs(kw::get(kw::observables, 0, kw_args...));
-            m_core.prepare_grid_observables(obs);
-            auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib, &obs);
-            return {std::move(*user_cb), std::move(ret)};
+            if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
+                // (kw::statistics: the return value is ret[(observable * n_stat + statistic) * batch_size + lane].)
+                const std::vector<grid_statistic> stats(kw::get(kw::statistics, 0, kw_args...));
+                m_core.prepare_grid_statistics(obs, stats);
+                auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib, &obs, &stats);
+                return {std::move(*user_cb), std::move(ret)};
+            } else {
+                m_core.prepare_grid_observables(obs);
+                auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib, &obs);
+                return {std::move(*user_cb), std::move(ret)};
+            }
+        } else if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
+            throw std::invalid_argument(detail::grid_statistics_need_observables);
         } else {
             auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib);
             return {std::move(*user_cb), std::move(ret)};

@@ -661,6 +661,39 @@ int hy_tab_propagate_grid_obs_device(hy_tab, const double *grid, size_t n_grid, 
  * inside an integrator. HEYOKA_AMD_GRID_OBS=registers|staged overrides how the kernel holds the samples of a grid point. */
 char *hy_grid_obs_source(hy_sys, const hy_expr *obs, size_t n_obs, uint32_t order, int high_accuracy);
 int hy_tab_grid_obs_module(hy_tab, const hy_expr *obs, size_t n_obs, char **source, const char **data, size_t *size);
+/* Grid statistics (MI355X extension): the observables are not stored per grid point but folded, per observable and system, over
+ * the grid points the system reaches - the rows of hy_tab_propagate_grid_obs() which are not NaN fill, a prefix of its grid -
+ * in ascending order. With y the value at a point and t the grid time of the row and lane:
+ *   MIN / MAX      start with the first value; then the value replaces the extremum m if y < m (y > m) or m != m: NaN values are
+ *                  ignored unless all are NaN, -0.0 does not replace +0.0;
+ *   T_MIN / T_MAX  the first grid time at which the current minimum / maximum was attained;
+ *   SUM            one rounded addition per point, in this order (NaN propagates);
+ *   LAST           the value at the last point reached;   COUNT   the number of points reached, as a double.
+ * A system which reached no point (the call returned before its first grid point) has NaN everywhere and COUNT 0. out holds
+ * n_obs * n_stats * batch_size values, out[(observable * n_stats + statistic) * batch_size + lane], statistics in the order of
+ * stats; nothing of the size of the grid is allocated for the output on the host or on the device. The integrator is left,
+ * bit for bit, as by hy_tab_propagate_grid_obs(). HY_ERR_INVALID_ARGUMENT before anything runs: as for the _obs functions,
+ * and for a null or empty list of statistics, an unknown code and a statistic named twice. */
+#define HY_GRID_STAT_MIN 0
+#define HY_GRID_STAT_MAX 1
+#define HY_GRID_STAT_T_MIN 2
+#define HY_GRID_STAT_T_MAX 3
+#define HY_GRID_STAT_SUM 4
+#define HY_GRID_STAT_LAST 5
+#define HY_GRID_STAT_COUNT 6
+int hy_tab_propagate_grid_stats(hy_tab, const double *grid, size_t n_grid, uint64_t max_steps, const double *max_delta_ts,
+                                size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
+                                const int *stats, size_t n_stats, double *out);
+/* The same into a caller-owned device buffer d_out of n_obs * n_stats * batch_size doubles; no callback. */
+int hy_tab_propagate_grid_stats_device(hy_tab, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                       const double *max_delta_ts, size_t n_mdt, const hy_expr *obs, size_t n_obs,
+                                       const int *stats, size_t n_stats, double *d_out);
+/* INTERNAL hooks of the test suite, the counterparts of hy_grid_obs_source() / hy_tab_grid_obs_module() for the module which
+ * folds (hy_grid_post merges, hy_grid_obs0 starts the accumulators, hy_grid_unsample restores them). */
+char *hy_grid_stats_source(hy_sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, uint32_t order,
+                           int high_accuracy);
+int hy_tab_grid_stats_module(hy_tab, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
+                             const char **data, size_t *size);
 /* get_propagate_res(): (outcome, min |h|, max |h|, n_steps) per lane. */
 int hy_tab_get_propagate_res(hy_tab, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps);
 
