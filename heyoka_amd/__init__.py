@@ -1147,19 +1147,34 @@ def _grid_statistics(statistics, observables):
     return codes, (ctypes.c_int * max(len(codes), 1))(*codes)
 
 
+def _grid_sampling(observables, statistics, always_observables=False):
+    """What propagate_grid() and its relatives do with ``(observables, statistics)``. The call makes the Python-side checks of
+    the statistics; the function it returns converts the observables when its turn has come: (suffix of the name of the C
+    entry point - "", "_obs" or "_stats" -, the arguments of that entry point for the lists, the observables, the codes of the
+    statistics). ``always_observables``: there is no entry point without observables."""
+    codes = sarr = None
+    if statistics is not None:
+        codes, sarr = _grid_statistics(statistics, observables)
+
+    def lists():
+        if observables is None and not always_observables:
+            return "", (), None, None
+        obs, oarr = _handle_array(list(observables))
+        if statistics is None:
+            return "_obs", (oarr, len(obs)), obs, None
+        return "_stats", (oarr, len(obs), sarr, len(codes)), obs, codes
+
+    return lists
+
+
 def grid_observables_source(sys, observables, order=20, high_accuracy=False, statistics=None):
     """HIP source of the post-step module of propagate_grid() with the section of ``observables`` for the system ``sys`` at
     the Taylor order ``order``: no integrator, no GPU. ``HEYOKA_AMD_GRID_OBS=registers|staged`` overrides how the kernel
     holds the samples of a grid point (default: registers up to 64 state rows read, the staging buffer beyond).
     ``statistics``: the module which folds the observables into these statistics (see propagate_grid())."""
     s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
-    if statistics is not None:
-        codes, sarr = _grid_statistics(statistics, observables)
-    obs, oarr = _handle_array(list(observables))
-    if statistics is not None:
-        return take_str(check_handle(lib.hy_grid_stats_source(s._h, oarr, len(obs), sarr, len(codes), int(order),
-                                                              int(bool(high_accuracy)))))
-    return take_str(check_handle(lib.hy_grid_obs_source(s._h, oarr, len(obs), int(order), int(bool(high_accuracy)))))
+    sfx, largs, obs, _ = _grid_sampling(observables, statistics, True)()
+    return take_str(check_handle(getattr(lib, "hy_grid%s_source" % sfx)(s._h, *largs, int(order), int(bool(high_accuracy)))))
 
 
 class _angle_reducer:
@@ -1922,19 +1937,17 @@ class taylor_adaptive_batch:
         NaN values unless all are NaN, ``t_min`` / ``t_max`` are the first grid times at which they were attained, ``sum`` is
         one rounded addition per point, ``count`` the number of points reached. The integrator is left as by the call with
         ``observables`` alone."""
-        if statistics is not None:
-            codes, sarr = _grid_statistics(statistics, observables)
+        lists = _grid_sampling(observables, statistics)
         g = _f64(grid)
         if g.ndim == 1:
             g = np.repeat(g[:, None], self.batch_size, axis=1)
         g = np.ascontiguousarray(g)
         n_grid = g.shape[0]
-        if observables is not None:
-            obs, oarr = _handle_array(list(observables))
-        if statistics is not None:
+        sfx, largs, obs, codes = lists()
+        if codes is not None:
             out = np.empty((len(obs), len(codes), self.batch_size))
         else:
-            out = np.empty((n_grid, self.dim if observables is None else len(obs), self.batch_size))
+            out = np.empty((n_grid, self.dim if obs is None else len(obs), self.batch_size))
         if max_delta_t is None:
             mptr, mn, mkeep = None, 0, None
         else:
@@ -1942,15 +1955,8 @@ class taylor_adaptive_batch:
             mptr, mn = mkeep.ctypes.data, mkeep.size
         err = []
         descs, n_cbs, keep = self._callback_descs(callback, err)
-        if observables is None:
-            rc = lib.hy_tab_propagate_grid_cbs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
-                                               out.ctypes.data)
-        elif statistics is not None:
-            rc = lib.hy_tab_propagate_grid_stats(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
-                                                 oarr, len(obs), sarr, len(codes), out.ctypes.data)
-        else:
-            rc = lib.hy_tab_propagate_grid_obs(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn, descs, n_cbs,
-                                               oarr, len(obs), out.ctypes.data)
+        rc = getattr(lib, "hy_tab_propagate_grid" + (sfx or "_cbs"))(self._h, g.ctypes.data, n_grid, int(max_steps), mptr, mn,
+                                                                       descs, n_cbs, *largs, out.ctypes.data)
         del keep
         if err:
             raise err[0]
@@ -1965,8 +1971,7 @@ class taylor_adaptive_batch:
         propagate_grid()) the buffer holds n_grid * len(observables) * batch_size doubles, layout [point, observable, lane];
         with ``statistics`` as well, len(observables) * len(statistics) * batch_size doubles, layout [observable, statistic,
         lane]."""
-        if statistics is not None:
-            codes, sarr = _grid_statistics(statistics, observables)
+        lists = _grid_sampling(observables, statistics)
         g = np.ascontiguousarray(_f64(grid))
         scalar = g.ndim == 1
         if max_delta_t is None:
@@ -1974,32 +1979,19 @@ class taylor_adaptive_batch:
         else:
             mkeep = _f64(max_delta_t).reshape(-1)
             mptr, mn = mkeep.ctypes.data, mkeep.size
-        if observables is not None:
-            obs, oarr = _handle_array(list(observables))
-            if statistics is not None:
-                raise_for(lib.hy_tab_propagate_grid_stats_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
-                                                                 mptr, mn, oarr, len(obs), sarr, len(codes),
-                                                                 ctypes.c_void_p(int(out_ptr))))
-                return
-            raise_for(lib.hy_tab_propagate_grid_obs_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
-                                                           mptr, mn, oarr, len(obs), ctypes.c_void_p(int(out_ptr))))
-            return
-        raise_for(lib.hy_tab_propagate_grid_device(self._h, g.ctypes.data, g.shape[0], int(scalar), int(max_steps),
-                                                   mptr, mn, ctypes.c_void_p(int(out_ptr))))
+        sfx, largs, obs, _ = lists()
+        raise_for(getattr(lib, "hy_tab_propagate_grid%s_device" % sfx)(self._h, g.ctypes.data, g.shape[0], int(scalar),
+                                                                       int(max_steps), mptr, mn, *largs,
+                                                                       ctypes.c_void_p(int(out_ptr))))
 
     def grid_observables_module(self, observables, statistics=None):
         """(HIP source, gfx950 code object) of the post-step module of propagate_grid() with the section of ``observables``
         (kernels hy_grid_post, hy_grid_obs0, hy_grid_unsample) in this integrator: checked against its system and compiled
         on first use. No GPU is needed. ``statistics``: the module which folds them (see propagate_grid())."""
-        if statistics is not None:
-            codes, sarr = _grid_statistics(statistics, observables)
-        obs, oarr = _handle_array(list(observables))
+        sfx, largs, obs, _ = _grid_sampling(observables, statistics, True)()
         src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
-        if statistics is not None:
-            raise_for(lib.hy_tab_grid_stats_module(self._h, oarr, len(obs), sarr, len(codes), ctypes.byref(src),
-                                                   ctypes.byref(data), ctypes.byref(n)))
-            return take_str(src.value), ctypes.string_at(data.value, n.value)
-        raise_for(lib.hy_tab_grid_obs_module(self._h, oarr, len(obs), ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
+        raise_for(getattr(lib, "hy_tab_grid%s_module" % sfx)(self._h, *largs, ctypes.byref(src), ctypes.byref(data),
+                                                             ctypes.byref(n)))
         return take_str(src.value), ctypes.string_at(data.value, n.value)
 
     @property

@@ -138,6 +138,18 @@ int guarded(const F &f)
     }
 }
 
+// The same for the functions which return a pointer: f()'s, or null after an exception.
+template <typename F>
+auto guarded_ptr(const F &f) -> decltype(f())
+{
+    try {
+        return f();
+    } catch (...) {
+        handle_exception();
+        return nullptr;
+    }
+}
+
 std::string dc_to_string(const taylor_dc_t &dc)
 {
     std::ostringstream oss;
@@ -171,22 +183,21 @@ std::vector<double> expand_mdt(const double *p, std::size_t n, std::uint32_t bat
     return std::vector<double>(p, p + n);
 }
 
-detail::tab_core::cb_t wrap_cb(hy_tab tab, hy_step_callback cb, void *cb_data)
+detail::tab_core::step_hooks wrap_cb(hy_tab tab, hy_step_callback cb, void *cb_data)
 {
     if (cb == nullptr) {
         return {};
     }
-    return [tab, cb, cb_data]() { return cb(tab, cb_data) != 0; };
+    return {.call = [tab, cb, cb_data]() { return cb(tab, cb_data) != 0; }};
 }
 
 // A set of C step callbacks with optional pre-hooks (hy_step_callback_desc): every member runs at every step, the
-// results are and-ed (src/step_callback.cpp:108-127). Returns (call, pre_hook, reducer indices, whether the whole
-// set is library-side with at least one step action) for the core.
+// results are and-ed (src/step_callback.cpp:108-127). Returns the hooks of the core: call, pre_hook, reducer indices, whether
+// the whole set is library-side with at least one step action.
 // Members whose `call` is the library's hy_angle_reducer_call are recognised by address (like hy_event_counter_nt among the
 // event callbacks): the C++ object behind the handle is used directly - its exceptions reach the caller with their
 // messages -, and when every member is one the core learns the indices they reduce (tab_core::red_t).
-std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::red_t, bool> wrap_cbs(hy_tab tab, const hy_step_callback_desc *cbs,
-                                                                                             size_t n_cbs)
+detail::tab_core::step_hooks wrap_cbs(hy_tab tab, const hy_step_callback_desc *cbs, size_t n_cbs)
 {
     if (n_cbs == 0u || (n_cbs == 1u && cbs[0].call == nullptr)) {
         return {};
@@ -259,6 +270,132 @@ std::tuple<detail::tab_core::cb_t, detail::tab_core::pre_t, detail::tab_core::re
         };
     }
     return {std::move(call), std::move(pre), std::move(red), lib_cb};
+}
+
+// The tail of the hy_tab_*_module() functions: whichever of the three the caller asked for.
+void module_out(const detail::tab_core::module_view &m, char **source, const char **data, size_t *size)
+{
+    if (source != nullptr) {
+        *source = dup_str(m.source);
+    }
+    if (data != nullptr) {
+        *data = m.code.data();
+    }
+    if (size != nullptr) {
+        *size = m.code.size();
+    }
+}
+
+void check_tab(const char *fn, hy_tab t)
+{
+    if (t == nullptr) {
+        throw std::invalid_argument(std::string(fn) + "(): the integrator handle is null");
+    }
+}
+
+// ---- what propagate_grid() samples (grid_observables.hpp) ----
+// The lists a function fn of the C interface was given: none, observables (lists == 1), observables and statistics (2).
+struct c_sampling {
+    int lists = 0;
+    const hy_expr *obs = nullptr;
+    size_t n_obs = 0;
+    const int *stats = nullptr;
+    size_t n_stats = 0;
+};
+
+detail::grid_sampling sampling_from(const char *fn, const c_sampling &c)
+{
+    if (c.lists == 0) {
+        return {};
+    }
+    if (c.obs == nullptr && c.n_obs != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of observables is null");
+    }
+    std::vector<expression> ov;
+    for (size_t i = 0; i < c.n_obs; ++i) {
+        if (c.obs[i] == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the observable " + std::to_string(i) + " is a null expression");
+        }
+        ov.push_back(c.obs[i]->ex);
+    }
+    if (c.lists == 1) {
+        return detail::grid_sampling(std::move(ov));
+    }
+    if (c.stats == nullptr && c.n_stats != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of statistics is null");
+    }
+    return detail::grid_sampling(std::move(ov), detail::grid_statistics_from_codes(c.stats, c.n_stats));
+}
+
+// hy_tab_propagate_grid*() with the output on the host. The checks of the sampling against the system come before the
+// callbacks are touched (hooks_of()) and before anything runs.
+template <typename H>
+int propagate_grid_host(const char *fn, hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
+                        size_t n_mdt, const H &hooks_of, const c_sampling &c, double *out)
+{
+    return guarded([&] {
+        check_tab(fn, t);
+        auto gs = sampling_from(fn, c);
+        t->core.prepare_grid_sampling(gs);
+        const auto bs = t->core.get_batch_size();
+        const auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), {.max_steps = static_cast<std::size_t>(max_steps),
+                                                                             .max_delta_ts = expand_mdt(mdts, n_mdt, bs),
+                                                                             .hooks = hooks_of(),
+                                                                             .sampling = std::move(gs)});
+        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
+    });
+}
+
+// hy_tab_propagate_grid*_device(): the output in a device buffer of the caller's, no callbacks. scalar_grid: one grid for
+// all the systems.
+int propagate_grid_dev(const char *fn, hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                       const double *mdts, size_t n_mdt, const c_sampling &c, double *d_out)
+{
+    return guarded([&] {
+        check_tab(fn, t);
+        auto gs = sampling_from(fn, c);
+        t->core.prepare_grid_sampling(gs);
+        const auto bs = t->core.get_batch_size();
+        std::vector<double> g;
+        if (scalar_grid != 0) {
+            g.reserve(n_grid * bs);
+            for (size_t k = 0; k < n_grid; ++k) {
+                g.insert(g.end(), bs, grid[k]);
+            }
+        } else {
+            g = vec_from(grid, n_grid * bs);
+        }
+        if (d_out == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the device output pointer is null");
+        }
+        t->core.propagate_grid(std::move(g), {.max_steps = static_cast<std::size_t>(max_steps),
+                                              .max_delta_ts = expand_mdt(mdts, n_mdt, bs),
+                                              .d_out = d_out,
+                                              .sampling = std::move(gs)});
+    });
+}
+
+// hy_grid_{obs,stats}_source(): the post-step module of a sampling for a system, without an integrator.
+char *grid_source(const char *fn, hy_sys sys, const c_sampling &c, uint32_t order, int high_accuracy)
+{
+    return guarded_ptr([&] {
+        if (sys == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the system handle is null");
+        }
+        const auto gs = sampling_from(fn, c);
+        const auto svars = detail::state_variables_of(sys->sys);
+        // (Without an integrator there is no parameter array to check against: whatever the expressions use.)
+        const auto sec = detail::make_grid_obs_section(gs, svars, std::numeric_limits<std::uint32_t>::max());
+        return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
+    });
+}
+
+int grid_module(const char *fn, hy_tab t, const c_sampling &c, char **source, const char **data, size_t *size)
+{
+    return guarded([&] {
+        check_tab(fn, t);
+        module_out(t->core.grid_sampling_module(sampling_from(fn, c)), source, data, size);
+    });
 }
 
 } // namespace
@@ -1065,19 +1202,7 @@ int hy_tab_eval_taylor_map_cloud(hy_tab t, const double *d_delta, double *d_out,
 }
 int hy_tab_taylor_map_module(hy_tab t, char **source, const char **data, size_t *size)
 {
-    return guarded([&] {
-        const auto &src = t->core.taylor_map_source();
-        const auto &co = t->core.taylor_map_code_object();
-        if (source != nullptr) {
-            *source = dup_str(src);
-        }
-        if (data != nullptr) {
-            *data = co.data();
-        }
-        if (size != nullptr) {
-            *size = co.size();
-        }
-    });
+    return guarded([&] { module_out(t->core.taylor_map_module(), source, data, size); });
 }
 char *hy_taylor_map_source(uint32_t n_orig_sv, uint32_t n_args, uint32_t order, size_t lds_bytes, char **note)
 {
@@ -1258,19 +1383,7 @@ int hy_event_action_t(hy_tab t, int, uint32_t batch_idx, void *user)
 }
 int hy_tab_event_action_module(hy_tab t, char **source, const char **data, size_t *size)
 {
-    return guarded([&] {
-        const auto &src = t->core.event_action_source();
-        const auto &co = t->core.event_action_code_object();
-        if (source != nullptr) {
-            *source = dup_str(src);
-        }
-        if (data != nullptr) {
-            *data = co.data();
-        }
-        if (size != nullptr) {
-            *size = co.size();
-        }
-    });
+    return guarded([&] { module_out(t->core.event_action_module(), source, data, size); });
 }
 uint32_t hy_tab_n_event_actions(hy_tab t)
 {
@@ -1584,30 +1697,23 @@ int hy_tab_propagate_until_cbs(hy_tab t, const double *ts, size_t n_ts, uint64_t
                                const hy_step_callback_desc *cbs, size_t n_cbs, int wtc, int c_out)
 {
     return guarded([&] {
-        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
         t->core.propagate_until(vec_from(ts, n_ts), static_cast<std::size_t>(max_steps),
-                                expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red, lib_cb);
+                                expand_mdt(mdts, n_mdt, t->core.get_batch_size()), wrap_cbs(t, cbs, n_cbs), wtc != 0, c_out != 0);
     });
 }
 int hy_tab_propagate_for_cbs(hy_tab t, const double *dts, size_t n_dts, uint64_t max_steps, const double *mdts, size_t n_mdt,
                              const hy_step_callback_desc *cbs, size_t n_cbs, int wtc, int c_out)
 {
     return guarded([&] {
-        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
         t->core.propagate_for(vec_from(dts, n_dts), static_cast<std::size_t>(max_steps),
-                              expand_mdt(mdts, n_mdt, t->core.get_batch_size()), call, wtc != 0, c_out != 0, pre, red, lib_cb);
+                              expand_mdt(mdts, n_mdt, t->core.get_batch_size()), wrap_cbs(t, cbs, n_cbs), wtc != 0, c_out != 0);
     });
 }
 int hy_tab_propagate_grid_cbs(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
                               size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, double *out)
 {
-    return guarded([&] {
-        const auto bs = t->core.get_batch_size();
-        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
-        auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
-                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red, lib_cb);
-        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
-    });
+    return propagate_grid_host("hy_tab_propagate_grid_cbs", t, grid, n_grid, max_steps, mdts, n_mdt,
+                               [&] { return wrap_cbs(t, cbs, n_cbs); }, c_sampling{}, out);
 }
 // ---- callback::angle_reducer ----
 hy_angle_reducer hy_angle_reducer_new(const hy_expr *vars, size_t n)
@@ -1726,31 +1832,16 @@ int hy_step_action_call(hy_tab t, void *user)
 }
 char *hy_step_action_source(hy_sys sys, hy_step_action h)
 {
-    try {
+    return guarded_ptr([&] {
         const auto svars = detail::state_variables_of(sys->sys);
         // (Without an integrator there is no parameter array to check against: whatever the expressions use.)
         return dup_str(detail::make_step_action_source(
             detail::make_step_action_section(h->act, svars, std::numeric_limits<std::uint32_t>::max())));
-    } catch (...) {
-        handle_exception();
-        return nullptr;
-    }
+    });
 }
 int hy_tab_step_action_module(hy_tab t, hy_step_action h, char **source, const char **data, size_t *size)
 {
-    return guarded([&] {
-        const auto &src = t->core.step_action_source(h->act);
-        const auto &co = t->core.step_action_code_object(h->act);
-        if (source != nullptr) {
-            *source = dup_str(src);
-        }
-        if (data != nullptr) {
-            *data = co.data();
-        }
-        if (size != nullptr) {
-            *size = co.size();
-        }
-    });
+    return guarded([&] { module_out(t->core.step_action_module(h->act), source, data, size); });
 }
 uint64_t hy_tab_get_n_stopped_by_action(hy_tab t)
 {
@@ -1963,229 +2054,61 @@ int hy_cfunc_eval_device(hy_cfunc c, double *d_out, const double *d_in, const do
 int hy_tab_propagate_grid(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
                           size_t n_mdt, hy_step_callback cb, void *cb_data, double *out)
 {
-    return guarded([&] {
-        const auto bs = t->core.get_batch_size();
-        auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
-                                          expand_mdt(mdts, n_mdt, bs), wrap_cb(t, cb, cb_data));
-        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
-    });
+    return propagate_grid_host("hy_tab_propagate_grid", t, grid, n_grid, max_steps, mdts, n_mdt,
+                               [&] { return wrap_cb(t, cb, cb_data); }, c_sampling{}, out);
 }
 int hy_tab_propagate_grid_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
                                  const double *mdts, size_t n_mdt, double *d_out)
 {
-    return guarded([&] {
-        const auto bs = t->core.get_batch_size();
-        std::vector<double> g;
-        if (scalar_grid != 0) {
-            g.reserve(n_grid * bs);
-            for (size_t k = 0; k < n_grid; ++k) {
-                g.insert(g.end(), bs, grid[k]);
-            }
-        } else {
-            g = vec_from(grid, n_grid * bs);
-        }
-        if (d_out == nullptr) {
-            throw std::invalid_argument("hy_tab_propagate_grid_device(): the device output pointer is null");
-        }
-        t->core.propagate_grid(std::move(g), static_cast<std::size_t>(max_steps), expand_mdt(mdts, n_mdt, bs), {}, d_out);
-    });
+    return propagate_grid_dev("hy_tab_propagate_grid_device", t, grid, n_grid, scalar_grid, max_steps, mdts, n_mdt, c_sampling{},
+                              d_out);
 }
 // ---- grid observables (grid_observables.hpp) ----
-namespace
-{
-
-std::vector<expression> obs_from(const char *fn, const hy_expr *obs, size_t n_obs)
-{
-    if (obs == nullptr && n_obs != 0u) {
-        throw std::invalid_argument(std::string(fn) + "(): the array of observables is null");
-    }
-    std::vector<expression> ret;
-    for (size_t i = 0; i < n_obs; ++i) {
-        if (obs[i] == nullptr) {
-            throw std::invalid_argument(std::string(fn) + "(): the observable " + std::to_string(i) + " is a null expression");
-        }
-        ret.push_back(obs[i]->ex);
-    }
-    return ret;
-}
-
-void check_tab(const char *fn, hy_tab t)
-{
-    if (t == nullptr) {
-        throw std::invalid_argument(std::string(fn) + "(): the integrator handle is null");
-    }
-}
-
-} // namespace
-
 int hy_tab_propagate_grid_obs(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
                               size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
                               double *out)
 {
-    return guarded([&] {
-        check_tab("hy_tab_propagate_grid_obs", t);
-        const auto ov = obs_from("hy_tab_propagate_grid_obs", obs, n_obs);
-        // (The checks against the system come before the callbacks are touched and before anything runs.)
-        t->core.prepare_grid_observables(ov);
-        const auto bs = t->core.get_batch_size();
-        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
-        auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
-                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red, lib_cb, &ov);
-        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
-    });
+    return propagate_grid_host("hy_tab_propagate_grid_obs", t, grid, n_grid, max_steps, mdts, n_mdt,
+                               [&] { return wrap_cbs(t, cbs, n_cbs); }, {1, obs, n_obs}, out);
 }
 int hy_tab_propagate_grid_obs_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
                                      const double *mdts, size_t n_mdt, const hy_expr *obs, size_t n_obs, double *d_out)
 {
-    return guarded([&] {
-        check_tab("hy_tab_propagate_grid_obs_device", t);
-        const auto ov = obs_from("hy_tab_propagate_grid_obs_device", obs, n_obs);
-        t->core.prepare_grid_observables(ov);
-        const auto bs = t->core.get_batch_size();
-        std::vector<double> g;
-        if (scalar_grid != 0) {
-            g.reserve(n_grid * bs);
-            for (size_t k = 0; k < n_grid; ++k) {
-                g.insert(g.end(), bs, grid[k]);
-            }
-        } else {
-            g = vec_from(grid, n_grid * bs);
-        }
-        if (d_out == nullptr) {
-            throw std::invalid_argument("hy_tab_propagate_grid_obs_device(): the device output pointer is null");
-        }
-        t->core.propagate_grid(std::move(g), static_cast<std::size_t>(max_steps), expand_mdt(mdts, n_mdt, bs), {}, d_out, {}, {},
-                               false, &ov);
-    });
+    return propagate_grid_dev("hy_tab_propagate_grid_obs_device", t, grid, n_grid, scalar_grid, max_steps, mdts, n_mdt,
+                              {1, obs, n_obs}, d_out);
 }
 char *hy_grid_obs_source(hy_sys sys, const hy_expr *obs, size_t n_obs, uint32_t order, int high_accuracy)
 {
-    try {
-        if (sys == nullptr) {
-            throw std::invalid_argument("hy_grid_obs_source(): the system handle is null");
-        }
-        const auto ov = obs_from("hy_grid_obs_source", obs, n_obs);
-        const auto svars = detail::state_variables_of(sys->sys);
-        // (Without an integrator there is no parameter array to check against: whatever the expressions use.)
-        const auto sec = detail::make_grid_obs_section(ov, svars, std::numeric_limits<std::uint32_t>::max());
-        return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
-    } catch (...) {
-        handle_exception();
-        return nullptr;
-    }
+    return grid_source("hy_grid_obs_source", sys, {1, obs, n_obs}, order, high_accuracy);
 }
 int hy_tab_grid_obs_module(hy_tab t, const hy_expr *obs, size_t n_obs, char **source, const char **data, size_t *size)
 {
-    return guarded([&] {
-        check_tab("hy_tab_grid_obs_module", t);
-        const auto ov = obs_from("hy_tab_grid_obs_module", obs, n_obs);
-        const auto &src = t->core.grid_observables_source(ov);
-        const auto &co = t->core.grid_observables_code_object(ov);
-        if (source != nullptr) {
-            *source = dup_str(src);
-        }
-        if (data != nullptr) {
-            *data = co.data();
-        }
-        if (size != nullptr) {
-            *size = co.size();
-        }
-    });
+    return grid_module("hy_tab_grid_obs_module", t, {1, obs, n_obs}, source, data, size);
 }
 // ---- grid statistics (grid_observables.hpp) ----
-namespace
-{
-
-std::vector<grid_statistic> stats_from(const char *fn, const int *stats, size_t n_stats)
-{
-    if (stats == nullptr && n_stats != 0u) {
-        throw std::invalid_argument(std::string(fn) + "(): the array of statistics is null");
-    }
-    return detail::grid_statistics_from_codes(stats, n_stats);
-}
-
-} // namespace
-
 int hy_tab_propagate_grid_stats(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
                                 size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
                                 const int *stats, size_t n_stats, double *out)
 {
-    return guarded([&] {
-        check_tab("hy_tab_propagate_grid_stats", t);
-        const auto ov = obs_from("hy_tab_propagate_grid_stats", obs, n_obs);
-        const auto sv = stats_from("hy_tab_propagate_grid_stats", stats, n_stats);
-        // (The checks against the system come before the callbacks are touched and before anything runs.)
-        t->core.prepare_grid_statistics(ov, sv);
-        const auto bs = t->core.get_batch_size();
-        auto [call, pre, red, lib_cb] = wrap_cbs(t, cbs, n_cbs);
-        auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), static_cast<std::size_t>(max_steps),
-                                          expand_mdt(mdts, n_mdt, bs), call, nullptr, pre, red, lib_cb, &ov, &sv);
-        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
-    });
+    return propagate_grid_host("hy_tab_propagate_grid_stats", t, grid, n_grid, max_steps, mdts, n_mdt,
+                               [&] { return wrap_cbs(t, cbs, n_cbs); }, {2, obs, n_obs, stats, n_stats}, out);
 }
 int hy_tab_propagate_grid_stats_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
                                        const double *mdts, size_t n_mdt, const hy_expr *obs, size_t n_obs, const int *stats,
                                        size_t n_stats, double *d_out)
 {
-    return guarded([&] {
-        check_tab("hy_tab_propagate_grid_stats_device", t);
-        const auto ov = obs_from("hy_tab_propagate_grid_stats_device", obs, n_obs);
-        const auto sv = stats_from("hy_tab_propagate_grid_stats_device", stats, n_stats);
-        t->core.prepare_grid_statistics(ov, sv);
-        const auto bs = t->core.get_batch_size();
-        std::vector<double> g;
-        if (scalar_grid != 0) {
-            g.reserve(n_grid * bs);
-            for (size_t k = 0; k < n_grid; ++k) {
-                g.insert(g.end(), bs, grid[k]);
-            }
-        } else {
-            g = vec_from(grid, n_grid * bs);
-        }
-        if (d_out == nullptr) {
-            throw std::invalid_argument("hy_tab_propagate_grid_stats_device(): the device output pointer is null");
-        }
-        t->core.propagate_grid(std::move(g), static_cast<std::size_t>(max_steps), expand_mdt(mdts, n_mdt, bs), {}, d_out, {}, {},
-                               false, &ov, &sv);
-    });
+    return propagate_grid_dev("hy_tab_propagate_grid_stats_device", t, grid, n_grid, scalar_grid, max_steps, mdts, n_mdt,
+                              {2, obs, n_obs, stats, n_stats}, d_out);
 }
 char *hy_grid_stats_source(hy_sys sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, uint32_t order,
                            int high_accuracy)
 {
-    try {
-        if (sys == nullptr) {
-            throw std::invalid_argument("hy_grid_stats_source(): the system handle is null");
-        }
-        const auto ov = obs_from("hy_grid_stats_source", obs, n_obs);
-        const auto sv = stats_from("hy_grid_stats_source", stats, n_stats);
-        const auto svars = detail::state_variables_of(sys->sys);
-        auto sec = detail::make_grid_obs_section(ov, svars, std::numeric_limits<std::uint32_t>::max());
-        detail::set_grid_statistics(sec, sv);
-        return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
-    } catch (...) {
-        handle_exception();
-        return nullptr;
-    }
+    return grid_source("hy_grid_stats_source", sys, {2, obs, n_obs, stats, n_stats}, order, high_accuracy);
 }
 int hy_tab_grid_stats_module(hy_tab t, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
                              const char **data, size_t *size)
 {
-    return guarded([&] {
-        check_tab("hy_tab_grid_stats_module", t);
-        const auto ov = obs_from("hy_tab_grid_stats_module", obs, n_obs);
-        const auto sv = stats_from("hy_tab_grid_stats_module", stats, n_stats);
-        const auto &src = t->core.grid_statistics_source(ov, sv);
-        const auto &co = t->core.grid_statistics_code_object(ov, sv);
-        if (source != nullptr) {
-            *source = dup_str(src);
-        }
-        if (data != nullptr) {
-            *data = co.data();
-        }
-        if (size != nullptr) {
-            *size = co.size();
-        }
-    });
+    return grid_module("hy_tab_grid_stats_module", t, {2, obs, n_obs, stats, n_stats}, source, data, size);
 }
 int hy_tab_get_propagate_res(hy_tab t, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps)
 {

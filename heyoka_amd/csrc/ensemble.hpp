@@ -238,37 +238,16 @@ auto ensemble_propagate_tmpl(const taylor_adaptive_batch<double> &ta, const Time
             }
         }
         std::vector<std::tuple<step_callback_batch<double>, std::vector<double>>> res(n_iter);
-        if constexpr (kw::has_v<kw::observables_tag, KwArgs...>) {
-            // (kw::observables: every iteration returns n_grid * n_obs * batch_size values. The checks against the system
-            // come before the first iteration runs.)
-            const std::vector<expression> obs(kw::get(kw::observables, 0, kw_args...));
-            if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
-                // (kw::statistics: n_obs * n_stat * batch_size values per iteration.)
-                const std::vector<grid_statistic> stats(kw::get(kw::statistics, 0, kw_args...));
-                if (n_iter != 0u) {
-                    tas[0].core().prepare_grid_statistics(obs, stats);
-                }
-                ensemble_run_per_device(n_iter, n_dev, [&](std::size_t i) {
-                    res[i] = tas[i].propagate_grid(grid, kw::max_steps = max_steps, kw::max_delta_t = max_delta_ts,
-                                                   kw::callback = cb, kw::observables = obs, kw::statistics = stats);
-                });
-            } else {
-                if (n_iter != 0u) {
-                    tas[0].core().prepare_grid_observables(obs);
-                }
-                ensemble_run_per_device(n_iter, n_dev, [&](std::size_t i) {
-                    res[i] = tas[i].propagate_grid(grid, kw::max_steps = max_steps, kw::max_delta_t = max_delta_ts,
-                                                   kw::callback = cb, kw::observables = obs);
-                });
-            }
-        } else if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
-            throw std::invalid_argument(detail::grid_statistics_need_observables);
-        } else {
-            ensemble_run_per_device(n_iter, n_dev, [&](std::size_t i) {
-                res[i] = tas[i].propagate_grid(grid, kw::max_steps = max_steps, kw::max_delta_t = max_delta_ts,
-                                               kw::callback = cb);
-            });
+        // (kw::observables: every iteration returns n_grid * n_obs * batch_size values; with kw::statistics n_obs * n_stat *
+        // batch_size. The checks against the system come before the first iteration runs.)
+        const auto gs = detail::grid_sampling_from_kw(kw_args...);
+        if (n_iter != 0u) {
+            tas[0].core().prepare_grid_sampling(gs);
         }
+        ensemble_run_per_device(n_iter, n_dev, [&](std::size_t i) {
+            res[i] = tas[i].propagate_grid(grid, kw::max_steps = max_steps, kw::max_delta_t = max_delta_ts, kw::callback = cb,
+                                           kw::observables = gs.observables, kw::statistics = gs.statistics);
+        });
         if constexpr (kw::has_v<kw::gather_tag, KwArgs...>) {
             *kw::get(kw::gather, 0, kw_args...) = ensemble_gather_states(tas, 0);
         }

@@ -1,8 +1,6 @@
 // Terminal-event actions. See event_action.hpp.
 #include "event_action.hpp"
 
-#include <algorithm>
-#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -33,63 +31,32 @@ event_action_section make_event_action_section(const event_action &act, std::uin
     if (act.assignments.empty()) {
         throw std::invalid_argument("Cannot construct an event action from an empty list of assignments" + where);
     }
+    const section_wording w{
+        [&](std::size_t k, const std::string &v) {
+            return "The right-hand side of the assignment to '" + act.assignments[k].first.to_string()
+                   + "' in an event action uses the variable '" + v + "', which is not a state variable of the system" + where;
+        },
+        [&](std::uint32_t i, std::uint32_t n) {
+            return "An event action uses par[" + std::to_string(i) + "], but the system and its event equations have "
+                   + std::to_string(n) + " parameter(s)" + where;
+        }};
     event_action_section ret;
     ret.te_idx = te_idx;
+    ret.rows = assignment_rows(act.assignments, state_vars, w, "an event action", where);
     std::vector<expression> rhs;
-    std::set<std::string> names;
-    for (const auto &sv : state_vars) {
-        names.insert(sv.var_name());
+    for (const auto &a : act.assignments) {
+        rhs.push_back(a.second);
     }
-    for (const auto &[lhs, ex] : act.assignments) {
-        const auto it = std::find(state_vars.begin(), state_vars.end(), lhs);
-        if (!lhs.is_variable() || it == state_vars.end()) {
-            throw std::invalid_argument("The left-hand side '" + lhs.to_string()
-                                        + "' of an assignment of an event action is not a state variable of the system" + where);
-        }
-        const auto row = static_cast<std::uint32_t>(it - state_vars.begin());
-        if (std::find(ret.rows.begin(), ret.rows.end(), row) != ret.rows.end()) {
-            throw std::invalid_argument("The state variable '" + lhs.to_string()
-                                        + "' is assigned more than once by an event action" + where);
-        }
-        for (const auto &v : get_variables(ex)) {
-            if (names.count(v) == 0u) {
-                throw std::invalid_argument("The right-hand side of the assignment to '" + lhs.to_string()
-                                            + "' in an event action uses the variable '" + v
-                                            + "', which is not a state variable of the system" + where);
-            }
-        }
-        ret.rows.push_back(row);
-        rhs.push_back(ex);
-    }
-    const auto dc = function_decompose(rhs, state_vars);
-    ret.prog = make_program(dc, static_cast<std::uint32_t>(state_vars.size()), static_cast<std::uint32_t>(rhs.size()));
-    if (ret.prog.n_par > n_par) {
-        throw std::invalid_argument("An event action uses par[" + std::to_string(ret.prog.n_par - 1u)
-                                    + "], but the system and its event equations have " + std::to_string(n_par)
-                                    + " parameter(s)" + where);
-    }
+    static_cast<expr_section &>(ret) = make_expr_section(rhs, state_vars, n_par, w);
     return ret;
 }
 
-std::string emit_assignment_section(const taylor_program &p, const std::vector<std::uint32_t> &rows)
+std::string emit_assignment_section(const expr_section &sec, const std::vector<std::uint32_t> &rows)
 {
+    const auto &p = sec.prog;
     std::ostringstream src;
     const auto code = emit_order0(p, [](std::uint32_t i) { return "x" + std::to_string(i); });
-    // State rows the section reads: the operands of its elementary functions and the outputs which are plain copies.
-    std::set<std::uint32_t> reads;
-    for (const auto &n : p.nodes) {
-        for (const auto &o : n.args) {
-            if (o.type == operand::kind::uvar && o.idx < p.n_eq) {
-                reads.insert(o.idx);
-            }
-        }
-    }
-    for (const auto &d : p.sv_defs) {
-        if (d.type == operand::kind::uvar && d.idx < p.n_eq) {
-            reads.insert(d.idx);
-        }
-    }
-    for (const auto r : reads) {
+    for (const auto r : sec.reads) {
         src << "const double x" << r << " = a.state[(u64)" << r << "u * N + s];\n";
     }
     for (std::uint32_t i = 0; i < p.n_par; ++i) {
@@ -138,7 +105,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_ev_action(const hy_eva_args
     switch (oc) {
 )HIP";
     for (const auto &sec : sections) {
-        src << "case " << sec.te_idx << ": {\n" << emit_assignment_section(sec.prog, sec.rows);
+        src << "case " << sec.te_idx << ": {\n" << emit_assignment_section(sec, sec.rows);
         src << "break;\n}\n";
     }
     src << "default:\nbreak;\n}\n}\n";

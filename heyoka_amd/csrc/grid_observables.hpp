@@ -22,24 +22,34 @@
 #pragma once
 
 #include <cstdint>
+#include <optional>
 #include <string>
 #include <vector>
 
-#include "decompose.hpp"
+#include "expr_section.hpp"
 #include "expression.hpp"
 #include "kw.hpp"
 
 namespace heyoka_amd::detail
 {
 
-// Observables checked against a system: the state rows they read (sorted), their decomposition as a function of ALL the
-// state variables, and how the kernel holds the samples of a grid point.
-struct grid_obs_section {
-    std::vector<std::uint32_t> rows;
+// What propagate_grid() samples: nothing but the state (both absent), a list of observables, or the statistics of a list of
+// observables. The construction is the one place which rejects statistics without observables
+// (grid_statistics_need_observables) and checks the list of statistics (check_grid_statistics()).
+struct grid_sampling {
+    std::optional<std::vector<expression>> observables;
+    std::optional<std::vector<grid_statistic>> statistics;
+
+    grid_sampling() = default;
+    explicit grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats = {});
+};
+
+// Observables checked against a system: their section (expr_section.hpp: `reads` are the rows the kernel samples) and how
+// the kernel holds the samples of a grid point.
+struct grid_obs_section : expr_section {
     std::uint32_t n_obs = 0;
     // false: registers (the rows are named scalars), true: staged (the rows go through hy_grid_args::stage).
     bool staged = false;
-    taylor_program prog;
     // Grid statistics, empty: none. n_slots: accumulators per lane, the n_obs * stats.size() of the output first.
     std::vector<grid_statistic> stats;
     std::uint32_t n_slots = 0;
@@ -48,21 +58,22 @@ struct grid_obs_section {
 // The largest number of rows held in registers: see DESIGN 4.3e for the budget.
 inline constexpr std::uint32_t grid_obs_max_register_rows = 64;
 
-// std::invalid_argument for an empty list, a variable which is not a state variable, a par[i] beyond n_par. The way of
-// holding the samples follows from the number of rows unless HEYOKA_AMD_GRID_OBS=registers|staged says otherwise.
-grid_obs_section make_grid_obs_section(const std::vector<expression> &obs, const std::vector<expression> &state_vars,
-                                       std::uint32_t n_par);
+// The section of gs.observables, with gs.statistics if there are any. std::invalid_argument for an empty list, a variable
+// which is not a state variable, a par[i] beyond n_par. The way of holding the samples follows from the number of rows
+// unless HEYOKA_AMD_GRID_OBS=registers|staged says otherwise.
+grid_obs_section make_grid_obs_section(const grid_sampling &gs, const std::vector<expression> &state_vars, std::uint32_t n_par);
 
 // make_grid_source() (taylor_adaptive_batch.hpp) with the section: hy_grid_post samples the rows of the section only and
 // stores HY_NOUT columns per grid point, hy_grid_unsample clears HY_NOUT columns, hy_grid_obs0 computes row 0 from the
 // current state. The other kernels of the module are those of the plain module.
-// With statistics in the section (set_grid_statistics()): hy_grid_post folds the HY_NOUT values of a grid point into the
-// HY_NSLOT accumulators of the lane instead of storing them, hy_grid_obs0 starts the accumulators, hy_grid_unsample puts
-// them back from their shadow copy. Without statistics the text is, byte for byte, the one of a section without the field.
+// With statistics in the section: hy_grid_post folds the HY_NOUT values of a grid point into the HY_NSLOT accumulators of
+// the lane instead of storing them, hy_grid_obs0 starts the accumulators, hy_grid_unsample puts them back from their shadow
+// copy. Without statistics the text is, byte for byte, the one of a section without the field.
 std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool high_accuracy, const grid_obs_section *sec);
 
-// The key of the module of a list of observables inside an integrator: their text and the way of holding the samples.
-std::string grid_obs_key(const std::vector<expression> &obs);
+// The key of the module of gs (with observables) inside an integrator: the text of the observables, the way of holding the
+// samples and the statistics.
+std::string grid_obs_key(const grid_sampling &gs);
 
 // ---- grid statistics ----
 inline constexpr const char *grid_statistic_names[] = {"min", "max", "t_min", "t_max", "sum", "last", "count"};
@@ -72,11 +83,7 @@ inline constexpr int n_grid_statistics = 7;
 std::vector<grid_statistic> grid_statistics_from_codes(const int *codes, std::size_t n);
 // The same checks on a list which is already typed (an enumerator may have been cast from anything).
 void check_grid_statistics(const std::vector<grid_statistic> &stats);
-// sec with the statistics: make_grid_source() then emits the variant which folds (checks as above).
-void set_grid_statistics(grid_obs_section &sec, const std::vector<grid_statistic> &stats);
-// grid_obs_key() of the module with statistics.
-std::string grid_obs_key(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats);
-// The message of the front ends for statistics without observables.
+// The message of grid_sampling for statistics without observables.
 inline constexpr const char *grid_statistics_need_observables = "The statistics of propagate_grid() need a list of observables";
 
 } // namespace heyoka_amd::detail

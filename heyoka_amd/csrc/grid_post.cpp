@@ -9,69 +9,32 @@
 namespace heyoka_amd::detail
 {
 
-grid_obs_section make_grid_obs_section(const std::vector<expression> &obs, const std::vector<expression> &state_vars,
-                                       std::uint32_t n_par)
+grid_sampling::grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats)
+    : observables(std::move(obs)), statistics(std::move(stats))
 {
-    if (obs.empty()) {
-        throw std::invalid_argument("The list of observables of propagate_grid() is empty");
-    }
-    std::set<std::string> names;
-    for (const auto &sv : state_vars) {
-        names.insert(sv.var_name());
-    }
-    for (std::size_t o = 0; o < obs.size(); ++o) {
-        for (const auto &v : get_variables(obs[o])) {
-            if (names.count(v) == 0u) {
-                throw std::invalid_argument("The observable " + std::to_string(o) + " of propagate_grid() uses the variable '" + v
-                                            + "', which is not a state variable of the system");
-            }
+    if (statistics) {
+        if (!observables) {
+            throw std::invalid_argument(grid_statistics_need_observables);
         }
+        check_grid_statistics(*statistics);
     }
-    grid_obs_section ret;
-    ret.n_obs = static_cast<std::uint32_t>(obs.size());
-    const auto dc = function_decompose(obs, state_vars);
-    ret.prog = make_program(dc, static_cast<std::uint32_t>(state_vars.size()), ret.n_obs);
-    if (ret.prog.n_par > n_par) {
-        throw std::invalid_argument("An observable of propagate_grid() uses par[" + std::to_string(ret.prog.n_par - 1u)
-                                    + "], but the integrator has " + std::to_string(n_par) + " parameter(s)");
-    }
-    // State rows the section reads: the operands of its elementary functions and the outputs which are plain copies.
-    std::set<std::uint32_t> reads;
-    for (const auto &n : ret.prog.nodes) {
-        for (const auto &a : n.args) {
-            if (a.type == operand::kind::uvar && a.idx < ret.prog.n_eq) {
-                reads.insert(a.idx);
-            }
-        }
-    }
-    for (const auto &d : ret.prog.sv_defs) {
-        if (d.type == operand::kind::uvar && d.idx < ret.prog.n_eq) {
-            reads.insert(d.idx);
-        }
-    }
-    ret.rows.assign(reads.begin(), reads.end());
-    ret.staged = ret.rows.size() > grid_obs_max_register_rows;
-    if (const char *env = std::getenv("HEYOKA_AMD_GRID_OBS")) {
-        const std::string mode(env);
-        if (mode == "registers") {
-            ret.staged = false;
-        } else if (mode == "staged") {
-            ret.staged = true;
-        } else if (!mode.empty()) {
-            throw std::invalid_argument("Invalid value '" + mode + "' of HEYOKA_AMD_GRID_OBS: 'registers' or 'staged'");
-        }
-    }
-    return ret;
 }
 
-std::string grid_obs_key(const std::vector<expression> &obs)
+std::string grid_obs_key(const grid_sampling &gs)
 {
     std::string key;
-    for (const auto &ex : obs) {
+    for (const auto &ex : gs.observables.value()) {
         key += ex.to_string() + ";";
     }
     const char *env = std::getenv("HEYOKA_AMD_GRID_OBS");
-    return key + "|" + (env != nullptr ? env : "");
+    key += std::string("|") + (env != nullptr ? env : "");
+    if (gs.statistics) {
+        key += "|statistics:";
+        for (const auto s : *gs.statistics) {
+            key += std::to_string(static_cast<int>(s)) + ",";
+        }
+    }
+    return key;
 }
 
 // ---- grid statistics ----
@@ -134,20 +97,40 @@ std::vector<stat_slots> grid_stat_slots(std::uint32_t n_obs, const std::vector<g
 
 } // namespace
 
-void set_grid_statistics(grid_obs_section &sec, const std::vector<grid_statistic> &stats)
+grid_obs_section make_grid_obs_section(const grid_sampling &gs, const std::vector<expression> &state_vars, std::uint32_t n_par)
 {
-    check_grid_statistics(stats);
-    sec.stats = stats;
-    (void)grid_stat_slots(sec.n_obs, stats, sec.n_slots);
-}
-
-std::string grid_obs_key(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats)
-{
-    auto key = grid_obs_key(obs) + "|statistics:";
-    for (const auto s : stats) {
-        key += std::to_string(static_cast<int>(s)) + ",";
+    const auto &obs = gs.observables.value();
+    if (obs.empty()) {
+        throw std::invalid_argument("The list of observables of propagate_grid() is empty");
     }
-    return key;
+    const section_wording w{
+        [](std::size_t o, const std::string &v) {
+            return "The observable " + std::to_string(o) + " of propagate_grid() uses the variable '" + v
+                   + "', which is not a state variable of the system";
+        },
+        [](std::uint32_t i, std::uint32_t n) {
+            return "An observable of propagate_grid() uses par[" + std::to_string(i) + "], but the integrator has "
+                   + std::to_string(n) + " parameter(s)";
+        }};
+    grid_obs_section ret;
+    static_cast<expr_section &>(ret) = make_expr_section(obs, state_vars, n_par, w);
+    ret.n_obs = static_cast<std::uint32_t>(obs.size());
+    ret.staged = ret.reads.size() > grid_obs_max_register_rows;
+    if (const char *env = std::getenv("HEYOKA_AMD_GRID_OBS")) {
+        const std::string mode(env);
+        if (mode == "registers") {
+            ret.staged = false;
+        } else if (mode == "staged") {
+            ret.staged = true;
+        } else if (!mode.empty()) {
+            throw std::invalid_argument("Invalid value '" + mode + "' of HEYOKA_AMD_GRID_OBS: 'registers' or 'staged'");
+        }
+    }
+    if (gs.statistics) {
+        ret.stats = *gs.statistics;
+        (void)grid_stat_slots(ret.n_obs, ret.stats, ret.n_slots);
+    }
+    return ret;
 }
 
 namespace
@@ -201,9 +184,9 @@ std::string grid_obs_device_functions(const grid_obs_section &sec)
         },
         &lit_names);
     std::ostringstream src;
-    src << "\n// The state rows the observables read.\n#define HY_NROWS " << sec.rows.size() << "u\n__device__ const unsigned hy_obs_rows[HY_NROWS] = {";
-    for (std::size_t j = 0; j < sec.rows.size(); ++j) {
-        src << (j != 0u ? ", " : "") << sec.rows[j] << "u";
+    src << "\n// The state rows the observables read.\n#define HY_NROWS " << sec.reads.size() << "u\n__device__ const unsigned hy_obs_rows[HY_NROWS] = {";
+    for (std::size_t j = 0; j < sec.reads.size(); ++j) {
+        src << (j != 0u ? ", " : "") << sec.reads[j] << "u";
     }
     src << "};\n";
     const bool folds = !sec.stats.empty();
@@ -227,7 +210,7 @@ __device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 
     if (sec.staged) {
         src << ", const double *stg";
     } else {
-        for (const auto r : sec.rows) {
+        for (const auto r : sec.reads) {
             src << ", const double x" << r;
         }
     }
@@ -311,7 +294,7 @@ std::string grid_obs_call(const grid_obs_section &sec, const char *outp, const c
     if (sec.staged) {
         ret += std::string(", ") + stg;
     } else {
-        for (std::size_t j = 0; j < sec.rows.size(); ++j) {
+        for (std::size_t j = 0; j < sec.reads.size(); ++j) {
             ret += ", " + std::string(xs) + "[" + std::to_string(j) + "]";
         }
     }
@@ -704,7 +687,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
             src << "    double xs[HY_NROWS];\n";
         }
         std::size_t n_obs0 = 0;
-        for (const auto r : sec->rows) {
+        for (const auto r : sec->reads) {
             if (sec->staged) {
                 src << "    stg[(u64)" << r << "u * N] = a.state[(u64)" << r << "u * N + i];\n";
             } else {

@@ -1,9 +1,7 @@
 // step_action. See step_action.hpp.
 #include "step_action.hpp"
 
-#include <algorithm>
 #include <ostream>
-#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -64,57 +62,30 @@ bool step_action::operator()(taylor_adaptive_batch<double> &ta)
 namespace detail
 {
 
-std::vector<expression> state_variables_of(const tab_core::sys_t &sys)
-{
-    std::vector<expression> ret;
-    for (const auto &eq : sys) {
-        ret.push_back(eq.first);
-    }
-    return ret;
-}
-
 step_action_section make_step_action_section(const step_action &act, const std::vector<expression> &state_vars,
                                              std::uint32_t n_par)
 {
+    const auto &asg = act.get_assignments();
+    const section_wording w{
+        [&](std::size_t k, const std::string &v) {
+            return (k < asg.size() ? "The right-hand side of the assignment to '" + asg[k].first.to_string() + "'"
+                                   : std::string("The stop condition"))
+                   + " of a step action uses the variable '" + v + "', which is not a state variable of the system";
+        },
+        [](std::uint32_t i, std::uint32_t n) {
+            return "A step action uses par[" + std::to_string(i) + "], but the integrator has " + std::to_string(n) + " parameter(s)";
+        }};
     step_action_section ret;
+    ret.rows = assignment_rows(asg, state_vars, w, "a step action");
     std::vector<expression> fn;
-    std::set<std::string> names;
-    for (const auto &sv : state_vars) {
-        names.insert(sv.var_name());
-    }
-    const auto check_vars = [&](const expression &ex, const std::string &what) {
-        for (const auto &v : get_variables(ex)) {
-            if (names.count(v) == 0u) {
-                throw std::invalid_argument(what + " of a step action uses the variable '" + v
-                                            + "', which is not a state variable of the system");
-            }
-        }
-    };
-    for (const auto &[lhs, ex] : act.get_assignments()) {
-        const auto it = std::find(state_vars.begin(), state_vars.end(), lhs);
-        if (!lhs.is_variable() || it == state_vars.end()) {
-            throw std::invalid_argument("The left-hand side '" + lhs.to_string()
-                                        + "' of an assignment of a step action is not a state variable of the system");
-        }
-        const auto row = static_cast<std::uint32_t>(it - state_vars.begin());
-        if (std::find(ret.rows.begin(), ret.rows.end(), row) != ret.rows.end()) {
-            throw std::invalid_argument("The state variable '" + lhs.to_string() + "' is assigned more than once by a step action");
-        }
-        check_vars(ex, "The right-hand side of the assignment to '" + lhs.to_string() + "'");
-        ret.rows.push_back(row);
-        fn.push_back(ex);
+    for (const auto &a : asg) {
+        fn.push_back(a.second);
     }
     if (act.get_stop_when()) {
-        check_vars(*act.get_stop_when(), "The stop condition");
         fn.push_back(*act.get_stop_when());
         ret.has_cond = true;
     }
-    const auto dc = function_decompose(fn, state_vars);
-    ret.prog = make_program(dc, static_cast<std::uint32_t>(state_vars.size()), static_cast<std::uint32_t>(fn.size()));
-    if (ret.prog.n_par > n_par) {
-        throw std::invalid_argument("A step action uses par[" + std::to_string(ret.prog.n_par - 1u) + "], but the integrator has "
-                                    + std::to_string(n_par) + " parameter(s)");
-    }
+    static_cast<expr_section &>(ret) = make_expr_section(fn, state_vars, n_par, w);
     return ret;
 }
 
@@ -137,7 +108,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_step_action(const hy_sa_arg
     if (s >= N) return;
     if (a.last_h[s] == 0.0) return;
 )HIP";
-    src << emit_assignment_section(p, sec.rows);
+    src << emit_assignment_section(sec, sec.rows);
     if (sec.has_cond) {
         src << "const bool stop = !(r" << sec.rows.size() << " == 0.0);\n";
         src << R"HIP(const u64 m = __builtin_amdgcn_ballot_w64(stop);

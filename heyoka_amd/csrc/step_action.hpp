@@ -34,7 +34,7 @@
 #include <utility>
 #include <vector>
 
-#include "decompose.hpp"
+#include "expr_section.hpp"
 #include "expression.hpp"
 #include "kernel_args.hpp"
 #include "taylor_adaptive_batch.hpp"
@@ -73,12 +73,12 @@ std::ostream &operator<<(std::ostream &, const step_action &);
 namespace detail
 {
 
-// An action checked against a system: the rows of the state it assigns and the decomposition of its right-hand sides,
-// followed by the condition (has_cond: the last output), as a function of ALL the state variables.
-struct step_action_section {
+// An action checked against a system: the section (expr_section.hpp) of its right-hand sides, followed by the condition
+// (has_cond: the last output), and the rows of the state it assigns. The checks are those of assignment_rows() and
+// make_expr_section().
+struct step_action_section : expr_section {
     std::vector<std::uint32_t> rows;
     bool has_cond = false;
-    taylor_program prog;
 };
 
 step_action_section make_step_action_section(const step_action &act, const std::vector<expression> &state_vars,
@@ -88,9 +88,6 @@ step_action_section make_step_action_section(const step_action &act, const std::
 // of last_h, then one straight-line section - loads of the state rows it reads, parameters and time, the right-hand
 // sides and the condition, the stores, the stop flag.
 std::string make_step_action_source(const step_action_section &sec);
-
-// The state variables of a system, in order.
-std::vector<expression> state_variables_of(const tab_core::sys_t &sys);
 
 } // namespace detail
 

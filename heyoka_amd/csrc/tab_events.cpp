@@ -529,7 +529,7 @@ void tab_core::impl::ev_apply_on_device(ev_step &s)
             log_fill_states(log_rows, ra.total, s.log_ub);
         }
     }
-    if (any && act_cmod) {
+    if (any && act.cm) {
         // Terminal-event actions: hy_ev_native has given the first terminal event of a system its cooldown and the
         // continuing outcome `index`; the rows of the log (a terminal row copies the state) are written. One lane per
         // system, the systems without such an outcome leave after one load.
@@ -899,20 +899,12 @@ std::pair<double, std::uint64_t> tab_core::get_event_action_kernel_ms() const
     return {m_impl->act_ms, m_impl->act_timed};
 }
 
-const std::string &tab_core::event_action_source() const
+tab_core::module_view tab_core::event_action_module() const
 {
-    if (!m_impl->act_cmod) {
+    if (!m_impl->act.cm) {
         throw std::invalid_argument("This integrator has no event actions: no action kernel was compiled");
     }
-    return m_impl->act_source;
-}
-
-const std::vector<char> &tab_core::event_action_code_object() const
-{
-    if (!m_impl->act_cmod) {
-        throw std::invalid_argument("This integrator has no event actions: no action kernel was compiled");
-    }
-    return m_impl->act_cmod->code;
+    return {m_impl->act.source, m_impl->act.cm->code};
 }
 
 void tab_core::apply_event_action(const event_action &act, std::uint32_t batch_idx)

@@ -56,6 +56,39 @@ struct scoped_value {
     }
 };
 
+// The module of a generated section inside an integrator: its HIP source, the compiled code object (it lives in the
+// process-wide cache) and the module loaded on the integrator's device at the first launch.
+struct section_module {
+    std::string source;
+    std::shared_ptr<const compiled_module> cm;
+    std::unique_ptr<aux_module> dm;
+
+    aux_module &loaded(int device)
+    {
+        if (!dm) {
+            dm = std::make_unique<aux_module>(cm, device);
+        }
+        return *dm;
+    }
+};
+
+// The entry of key in a map of section modules; on first use make(entry) checks the section against the system and
+// generates the source, which is compiled here. Nothing is ever dropped: a copy of the integrator starts with empty maps.
+template <typename M, typename F>
+typename M::mapped_type &find_or_build(M &map, const std::string &key, const char *label, const F &make)
+{
+    auto it = map.find(key);
+    if (it == map.end()) {
+        typename M::mapped_type v;
+        make(v);
+        const stopwatch sw;
+        v.cm = hiprtc_compile_source(v.source);
+        log_message(log_level::trace, std::string(label) + ": kernel compilation runtime: " + sw.str());
+        it = map.emplace(key, std::move(v)).first;
+    }
+    return it->second;
+}
+
 struct tab_core::impl {
     sys_t sys;
     taylor_dc_t dc;
@@ -168,27 +201,16 @@ struct tab_core::impl {
     // ---- step_action (step_action.hpp) ----
     // The modules of the actions this integrator has met, keyed by the text of the action: checked against the system,
     // generated and compiled on first use (the code objects live in the process-wide cache), loaded at the first launch.
-    struct sa_variant {
+    struct sa_module : section_module {
         step_action_section sec;
-        std::string source;
-        std::shared_ptr<const compiled_module> cm;
-        std::unique_ptr<aux_module> dm;
     };
-    std::map<std::string, sa_variant> sa_variants;
-    sa_variant &get_sa_variant(const step_action &act)
+    std::map<std::string, sa_module> sa_modules;
+    sa_module &get_sa_module(const step_action &act)
     {
-        const auto key = act.to_string();
-        auto it = sa_variants.find(key);
-        if (it == sa_variants.end()) {
-            sa_variant v;
+        return find_or_build(sa_modules, act.to_string(), "step_action", [&](sa_module &v) {
             v.sec = make_step_action_section(act, state_variables_of(sys), prog.n_par);
             v.source = make_step_action_source(v.sec);
-            const detail::stopwatch sw;
-            v.cm = hiprtc_compile_source(v.source);
-            detail::log_message(log_level::trace, "step_action: kernel compilation runtime: " + sw.str());
-            it = sa_variants.emplace(key, std::move(v)).first;
-        }
-        return it->second;
+        });
     }
     // The counter of the stop condition; systems retired by it in the running / last sweep loop; the grid indices of the
     // running propagate_grid() loop (a system retired by the action is through its grid); every member of the callback of
@@ -303,35 +325,17 @@ struct tab_core::impl {
     // live in the process-wide cache), loaded at the first launch. Nothing is ever dropped: an integrator which meets
     // generated observables without end keeps a section, a source text and a loaded module for each of them. The intended
     // use is a handful of lists per integrator; a copy of the integrator starts with an empty map.
-    struct go_variant {
+    // (One module per (observables, statistics): with statistics, the module which folds)
+    struct go_module : section_module {
         grid_obs_section sec;
-        std::string source;
-        std::shared_ptr<const compiled_module> cm;
-        std::unique_ptr<aux_module> dm;
     };
-    std::map<std::string, go_variant> go_variants;
-    // (stats != nullptr: the module which folds the observables into grid statistics, DESIGN 4.3f - one module per
-    // (observables, statistics).)
-    go_variant &get_go_variant(const std::vector<expression> &obs, const std::vector<grid_statistic> *stats = nullptr)
+    std::map<std::string, go_module> go_modules;
+    go_module &get_go_module(const grid_sampling &gs)
     {
-        if (stats != nullptr) {
-            check_grid_statistics(*stats);
-        }
-        const auto key = stats != nullptr ? grid_obs_key(obs, *stats) : grid_obs_key(obs);
-        auto it = go_variants.find(key);
-        if (it == go_variants.end()) {
-            go_variant v;
-            v.sec = make_grid_obs_section(obs, state_variables_of(sys), prog.n_par);
-            if (stats != nullptr) {
-                set_grid_statistics(v.sec, *stats);
-            }
+        return find_or_build(go_modules, grid_obs_key(gs), "grid observables", [&](go_module &v) {
+            v.sec = make_grid_obs_section(gs, state_variables_of(sys), prog.n_par);
             v.source = make_grid_source(order, dim, high_accuracy, &v.sec);
-            const detail::stopwatch sw;
-            v.cm = hiprtc_compile_source(v.source);
-            detail::log_message(log_level::trace, "grid observables: kernel compilation runtime: " + sw.str());
-            it = go_variants.emplace(key, std::move(v)).first;
-        }
-        return it->second;
+        });
     }
 
     // ---- event detection (see event_detection.hpp) ----
@@ -427,22 +431,18 @@ struct tab_core::impl {
     // One section of the kernel hy_ev_action per terminal event with an action; the module is compiled with the
     // integrator and loaded at the first step which needs it.
     std::vector<event_action_section> act_sections;
-    std::string act_source;
-    std::shared_ptr<const compiled_module> act_cmod;
-    mutable std::unique_ptr<aux_module> act_mod;
+    mutable section_module act;
     // Systems [first, first + count): by their outcomes (force < 0) or by the section of the terminal event `force`.
     void launch_event_action(std::uint64_t first, std::uint64_t count, long long force) const
     {
-        if (!act_mod) {
-            act_mod = std::make_unique<aux_module>(act_cmod, device);
-        }
+        auto &act_mod = act.loaded(device);
         const eva_kargs ka{d_outcome.as<long long>(), d_state.as<double>(), d_pars.as<double>(), d_thi.as<double>(), N, first, count, force};
         if (ev_timing) {
             // (Event timing on: the duration of the kernel from HIP events, see get_event_action_kernel_ms().)
-            act_ms += act_mod->launch_timed("hy_ev_action", count, 256, ka, stream);
+            act_ms += act_mod.launch_timed("hy_ev_action", count, 256, ka, stream);
             ++act_timed;
         } else {
-            act_mod->launch("hy_ev_action", count, 256, ka, stream);
+            act_mod.launch("hy_ev_action", count, 256, ka, stream);
         }
     }
     mutable double act_ms = 0;

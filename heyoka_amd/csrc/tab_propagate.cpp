@@ -91,12 +91,11 @@ void tab_core::finish_device_propagate(const std::vector<double> &ts, std::size_
     d.rollback_to_snapshot();
     const scoped_value<bool> guard(d.force_lockstep, true);
     // (cb: the fused angle reduction falls back to the callback after every sweep; its pre_hook() has run already.)
-    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, false);
+    propagate_until(ts, max_steps, max_delta_ts, {.call = cb}, wtc, false);
 }
 
 void tab_core::propagate_for(const std::vector<double> &delta_ts, std::size_t max_steps,
-                             const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                             const pre_t &pre, const red_t &red, bool lib_cb)
+                             const std::vector<double> &max_delta_ts, const step_hooks &hooks, bool wtc, bool c_out)
 {
     auto &d = *m_impl;
     if (delta_ts.size() != 1u && delta_ts.size() != d.N) {
@@ -116,14 +115,14 @@ void tab_core::propagate_for(const std::vector<double> &delta_ts, std::size_t ma
     // NOTE: double-length final times travel as a vector of size 2 * N: a form accepted only from here (a public
     // propagate_until() call with any size other than N throws like the reference).
     const scoped_value<bool> guard(d.dl_times_ok, true);
-    propagate_until(ts, max_steps, max_delta_ts, cb, wtc, c_out, pre, red, lib_cb);
+    propagate_until(ts, max_steps, max_delta_ts, hooks, wtc, c_out);
 }
 
 // Reference: propagate_until_impl(), src/taylor_adaptive_batch.cpp:1137-1534.
 void tab_core::propagate_until(const std::vector<double> &ts_, std::size_t max_steps,
-                               const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                               const pre_t &pre, const red_t &red, bool lib_cb)
+                               const std::vector<double> &max_delta_ts, const step_hooks &hooks, bool wtc, bool c_out)
 {
+    const auto &[cb, pre, red, lib_cb] = hooks;
     auto &d = *m_impl;
     const auto N = d.N;
     d.cb_is_library = cb && lib_cb;
@@ -382,10 +381,12 @@ std::optional<c_out_core> tab_core::take_c_output()
 
 void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                           const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
-                                          const std::vector<double> &max_delta_ts, std::size_t max_steps,
-                                          double *d_out, const cb_t &cb, const std::vector<expression> *obs,
-                                          const std::vector<grid_statistic> *stats)
+                                          const std::vector<double> &max_delta_ts, const grid_call &call)
 {
+    const auto max_steps = call.max_steps;
+    double *const d_out = call.d_out;
+    const auto &cb = call.hooks.call;
+    const auto &stats = call.sampling.statistics;
     auto &d = *m_impl;
     const auto N = d.N;
     const auto dim = d.dim;
@@ -409,13 +410,10 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     // Grid statistics: the variant of that module which folds. Its output buffer holds the accumulators of the
     // lanes, n_slots * N doubles with those of the result first, and their shadow copy behind them - whatever the caller gets,
     // host vector or device buffer, is the first n_obs * n_stat * N of them, copied at the end.
-    auto *const gov = obs != nullptr ? &d.get_go_variant(*obs, stats) : nullptr;
-    const bool folds = stats != nullptr;
+    auto *const gov = call.sampling.observables ? &d.get_go_module(call.sampling) : nullptr;
+    const bool folds = stats.has_value();
     const std::size_t n_res = folds ? gov->sec.n_obs * stats->size() * N : 0u;
-    if (gov != nullptr && !gov->dm) {
-        gov->dm = std::make_unique<aux_module>(gov->cm, d.device);
-    }
-    aux_module &sample_mod = gov != nullptr ? *gov->dm : *d.grid_mod;
+    aux_module &sample_mod = gov != nullptr ? gov->loaded(d.device) : *d.grid_mod;
     const std::size_t n_col = gov != nullptr ? gov->sec.n_obs : dim;
     device_buffer b_stage((gov != nullptr && gov->sec.staged) ? static_cast<std::size_t>(dim) * N * dsz : 0u, d.device);
 
@@ -634,7 +632,7 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                 + " grid intervals"
                 + (n_rollbacks != 0u ? ", a non-finite lane: rolled back to the start of the grid and redone in single-step sweeps"
                                      : "")
-                + (gov != nullptr ? ", " + std::to_string(gov->sec.n_obs) + " observables over " + std::to_string(gov->sec.rows.size())
+                + (gov != nullptr ? ", " + std::to_string(gov->sec.n_obs) + " observables over " + std::to_string(gov->sec.reads.size())
                                         + " of " + std::to_string(dim) + " state rows, samples held "
                                         + (gov->sec.staged ? "in the staging buffer" : "in registers")
                                   : std::string{})
@@ -666,11 +664,14 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
 // Reference: propagate_grid_impl(), src/taylor_adaptive_batch.cpp:1546-2055. Host-driven lock-step loop:
 // single-step kernel launches (always with the Taylor coefficients) interleaved with dense-output launches.
 // grid[point * N + lane]; return value ret[(point * dim + var) * N + lane], NaN where not reached.
-std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size_t max_steps,
-                                             const std::vector<double> &max_delta_ts_, const cb_t &cb, double *d_out,
-                                             const pre_t &pre, const red_t &red, bool lib_cb,
-                                             const std::vector<expression> *obs, const std::vector<grid_statistic> *stats)
+std::vector<double> tab_core::propagate_grid(std::vector<double> grid, const grid_call &call)
 {
+    const auto max_steps = call.max_steps;
+    const auto &max_delta_ts_ = call.max_delta_ts;
+    double *const d_out = call.d_out;
+    const auto &[cb, pre, red, lib_cb] = call.hooks;
+    const auto &stats = call.sampling.statistics;
+    const bool with_obs = call.sampling.observables.has_value();
     auto &d = *m_impl;
     const auto N = d.N;
     const auto dim = d.dim;
@@ -678,10 +679,7 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
 
     // Grid observables: the checks against the system before anything runs; n_col columns per grid point.
     // (... and the statistics: retval is the reduced output, NaN and a count of zero until the loop has run.)
-    if (stats != nullptr && obs == nullptr) {
-        throw std::invalid_argument(grid_statistics_need_observables);
-    }
-    const std::size_t n_col = obs != nullptr ? d.get_go_variant(*obs, stats).sec.n_obs : dim;
+    const std::size_t n_col = with_obs ? d.get_go_module(call.sampling).sec.n_obs : dim;
 
     if (grid.empty()) {
         throw std::invalid_argument(
@@ -754,9 +752,9 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     if (d_out != nullptr && cb) {
         throw std::invalid_argument("propagate_grid() with a device output buffer does not support callbacks");
     }
-    std::vector<double> retval(d_out != nullptr ? 0u : (stats != nullptr ? n_col * stats->size() * N : grid.size() * n_col),
+    std::vector<double> retval(d_out != nullptr ? 0u : (stats ? n_col * stats->size() * N : grid.size() * n_col),
                                std::numeric_limits<double>::quiet_NaN());
-    if (stats != nullptr && d_out == nullptr) {
+    if (stats && d_out == nullptr) {
         for (std::size_t k = 0; k < stats->size(); ++k) {
             if ((*stats)[k] == grid_statistic::count) {
                 for (std::size_t o = 0; o < n_col; ++o) {
@@ -768,7 +766,7 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     std::vector<double> pgrid_tmp(gp, gp + N);
 
     // Propagate up to the first grid point (absorbs the low part of the double-length time).
-    propagate_until(pgrid_tmp, max_steps, max_delta_ts, {}, true, false);
+    propagate_until(pgrid_tmp, max_steps, max_delta_ts, step_hooks{}, true, false);
     d.fetch_prop_res();
     if (std::any_of(d.prop_res.begin(), d.prop_res.end(),
                     [](const auto &t) { return std::get<0>(t) != taylor_outcome::time_limit; })) {
@@ -783,7 +781,7 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     if (d_out == nullptr) {
         d.to_host();
         // (With observables row 0 is computed on the device, hy_grid_obs0.)
-        if (obs == nullptr) {
+        if (!with_obs) {
             std::copy(d.state.begin(), d.state.end(), retval.begin());
         }
     } else {
@@ -811,41 +809,22 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, std::size
     // (A pure angle_reducer callback runs hy_angle_reduce after every sweep: no fused grid launches.)
     d.cb_is_library = cb && lib_cb;
     d.last_cb_path = cb ? (d.cb_is_library ? 4 : (red ? 2 : 1)) : 0;
-    propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, max_steps, d_out, cb, obs, stats);
+    propagate_grid_device_loop(grid, retval, rem, t_dir, max_delta_ts, call);
     return retval;
 }
 
-// ---- grid observables ----
-void tab_core::prepare_grid_observables(const std::vector<expression> &obs)
+// ---- grid observables and statistics ----
+void tab_core::prepare_grid_sampling(const grid_sampling &gs)
 {
-    (void)m_impl->get_go_variant(obs);
+    if (gs.observables) {
+        (void)m_impl->get_go_module(gs);
+    }
 }
 
-const std::string &tab_core::grid_observables_source(const std::vector<expression> &obs)
+tab_core::module_view tab_core::grid_sampling_module(const grid_sampling &gs)
 {
-    return m_impl->get_go_variant(obs).source;
-}
-
-const std::vector<char> &tab_core::grid_observables_code_object(const std::vector<expression> &obs)
-{
-    return m_impl->get_go_variant(obs).cm->code;
-}
-
-// ---- grid statistics ----
-void tab_core::prepare_grid_statistics(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats)
-{
-    (void)m_impl->get_go_variant(obs, &stats);
-}
-
-const std::string &tab_core::grid_statistics_source(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats)
-{
-    return m_impl->get_go_variant(obs, &stats).source;
-}
-
-const std::vector<char> &tab_core::grid_statistics_code_object(const std::vector<expression> &obs,
-                                                               const std::vector<grid_statistic> &stats)
-{
-    return m_impl->get_go_variant(obs, &stats).cm->code;
+    const auto &m = m_impl->get_go_module(gs);
+    return {m.source, m.cm->code};
 }
 
 // ---- callback::angle_reducer ----
@@ -894,7 +873,7 @@ bool tab_core::apply_step_action(const step_action &act)
 {
     auto &d = *m_impl;
     // (The checks against the system, the first time; the kernel from then on.)
-    auto &var = d.get_sa_variant(act);
+    auto &var = d.get_sa_module(act);
     // The state is never downloaded: when the host mirror is the newer copy (or a mutable pointer to it is out) it is
     // uploaded first, like before any kernel. A device which has not run a step yet holds no last_h: the mirror's.
     const bool fresh_device = !d.dmod;
@@ -918,9 +897,7 @@ bool tab_core::apply_step_action(const step_action &act)
                                                             : "the device copy was current: nothing moved")
                                                   + ")");
     }
-    if (!var.dm) {
-        var.dm = std::make_unique<aux_module>(var.cm, d.device);
-    }
+    auto &mod = var.loaded(d.device);
     const bool cond = var.sec.has_cond;
     const bool indep = cond && d.retired_ptr != nullptr;
     if (cond) {
@@ -942,10 +919,10 @@ bool tab_core::apply_step_action(const step_action &act)
                      d.sa_n_grid,
                      0u};
     if (d.ev_timing) {
-        d.sa_ms += var.dm->launch_timed("hy_step_action", d.N, 256, a, d.stream);
+        d.sa_ms += mod.launch_timed("hy_step_action", d.N, 256, a, d.stream);
         ++d.sa_timed;
     } else {
-        var.dm->launch("hy_step_action", d.N, 256, a, d.stream);
+        mod.launch("hy_step_action", d.N, 256, a, d.stream);
     }
     // The device copy of the state is the newer one; the mirrors somebody holds follow, as after any kernel.
     d.dev_newer = true;
@@ -965,7 +942,7 @@ bool tab_core::apply_step_action(const step_action &act)
 
 void tab_core::prepare_step_action(const step_action &act)
 {
-    (void)m_impl->get_sa_variant(act);
+    (void)m_impl->get_sa_module(act);
 }
 
 std::uint64_t tab_core::get_n_stopped_by_action() const
@@ -973,14 +950,10 @@ std::uint64_t tab_core::get_n_stopped_by_action() const
     return m_impl->n_stopped_by_action;
 }
 
-const std::string &tab_core::step_action_source(const step_action &act)
+tab_core::module_view tab_core::step_action_module(const step_action &act)
 {
-    return m_impl->get_sa_variant(act).source;
-}
-
-const std::vector<char> &tab_core::step_action_code_object(const step_action &act)
-{
-    return m_impl->get_sa_variant(act).cm->code;
+    const auto &m = m_impl->get_sa_module(act);
+    return {m.source, m.cm->code};
 }
 
 std::pair<double, std::uint64_t> tab_core::get_step_action_kernel_ms() const

@@ -284,18 +284,15 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
     }
     {
         // Terminal-event actions: checked against the system, one section each, the kernel in a module of its own.
-        std::vector<expression> svars;
-        for (const auto &eq : sys) {
-            svars.push_back(eq.first);
-        }
+        const auto svars = state_variables_of(sys);
         for (std::size_t e = 0; e < d.tes.size(); ++e) {
             if (d.tes[e].action) {
                 d.act_sections.push_back(make_event_action_section(*d.tes[e].action, static_cast<std::uint32_t>(e), svars, d.prog.n_par));
             }
         }
         if (!d.act_sections.empty()) {
-            d.act_source = make_event_action_source(d.act_sections);
-            d.act_cmod = hiprtc_compile_source(d.act_source);
+            d.act.source = make_event_action_source(d.act_sections);
+            d.act.cm = hiprtc_compile_source(d.act.source);
         }
     }
     if (d.ev_has_rec) {
@@ -367,8 +364,8 @@ tab_core::tab_core(const tab_core &o) : m_impl(o.m_impl ? std::make_unique<impl>
     d.evr_cmod = s.evr_cmod;
     d.drow_cmod = s.drow_cmod;
     d.act_sections = s.act_sections;
-    d.act_source = s.act_source;
-    d.act_cmod = s.act_cmod;
+    d.act.source = s.act.source;
+    d.act.cm = s.act.cm;
     d.var = s.var;
     d.tstate = s.tstate;
     d.state = s.state;
@@ -898,13 +895,13 @@ void tab_core::set_device(int device)
     }
     d.evr_mod.reset();
     d.drow_mod.reset();
-    d.act_mod.reset();
-    for (auto &[k, v] : d.sa_variants) {
+    d.act.dm.reset();
+    for (auto &[k, v] : d.sa_modules) {
         (void)k;
         v.dm.reset();
     }
     d.d_sa_cnt = {};
-    for (auto &[k, v] : d.go_variants) {
+    for (auto &[k, v] : d.go_modules) {
         (void)k;
         v.dm.reset();
     }

@@ -217,39 +217,46 @@ public:
     // update - one launch, cb is not invoked - whenever there is no continuous output, there are no events and the generator
     // of the stepper implements the variant; otherwise cb runs after every sweep of the lock-step loop as usual.
     using red_t = std::function<std::vector<std::uint32_t>()>;
-    // lib_cb: every member of the callback is a step_action (step_action.hpp) or an angle_reducer, with at least one action -
-    // cb applies all of them on the device (get_last_callback_path() == 4).
+    // The step callback of a propagate_*() as the core sees it: call (empty: none), pre and red as above; lib: every member
+    // of the callback is a step_action (step_action.hpp) or an angle_reducer, with at least one action - call applies all of
+    // them on the device (get_last_callback_path() == 4).
+    struct step_hooks {
+        cb_t call = {};
+        pre_t pre = {};
+        red_t red = {};
+        bool lib = false;
+    };
     void propagate_until(const std::vector<double> &ts, std::size_t max_steps, const std::vector<double> &max_delta_ts,
-                         const cb_t &cb, bool wtc, bool c_out, const pre_t &pre = {}, const red_t &red = {}, bool lib_cb = false);
+                         const step_hooks &hooks, bool wtc, bool c_out);
     void propagate_for(const std::vector<double> &delta_ts, std::size_t max_steps,
-                       const std::vector<double> &max_delta_ts, const cb_t &cb, bool wtc, bool c_out,
-                       const pre_t &pre = {}, const red_t &red = {}, bool lib_cb = false);
-    std::vector<double> propagate_grid(std::vector<double> grid, std::size_t max_steps,
-                                       const std::vector<double> &max_delta_ts, const cb_t &cb,
-                                       double *d_out = nullptr, const pre_t &pre = {}, const red_t &red = {},
-                                       bool lib_cb = false, const std::vector<expression> *obs = nullptr,
-                                       const std::vector<grid_statistic> *stats = nullptr);
-    // ---- grid observables (grid_observables.hpp) ----
-    // obs != nullptr in propagate_grid(): the output has one column per observable - ret[(point * n_obs + o) * N + lane] -,
-    // bit for bit cfunc(obs, vars = state variables) of the state sample, the parameters and the grid time of the row; NaN
-    // in every column of a row which was not reached. Everything else is as without observables.
-    // The checks against the system (std::invalid_argument: an empty list, a variable which is not a state variable, a
-    // par[i] the integrator does not have) and the compilation of the module. No GPU is needed.
-    void prepare_grid_observables(const std::vector<expression> &obs);
-    // HIP source and gfx950 code object of the post-step module with the section of obs (compiled on first use).
-    [[nodiscard]] const std::string &grid_observables_source(const std::vector<expression> &obs);
-    [[nodiscard]] const std::vector<char> &grid_observables_code_object(const std::vector<expression> &obs);
-    // ---- grid statistics (grid_observables.hpp) ----
-    // stats != nullptr in propagate_grid() (only with obs; std::invalid_argument otherwise, and for an empty list, an unknown
-    // code or a statistic named twice): the observables are folded over the grid points every system reaches, the return
-    // value is ret[(o * n_stat + k) * N + lane] (d_out: that many doubles), and nothing of the size of the grid is allocated
-    // for the output. The integrator is left, bit for bit, as by the call with obs alone.
-    // The counterparts of the three functions above.
-    void prepare_grid_statistics(const std::vector<expression> &obs, const std::vector<grid_statistic> &stats);
-    [[nodiscard]] const std::string &grid_statistics_source(const std::vector<expression> &obs,
-                                                            const std::vector<grid_statistic> &stats);
-    [[nodiscard]] const std::vector<char> &grid_statistics_code_object(const std::vector<expression> &obs,
-                                                                       const std::vector<grid_statistic> &stats);
+                       const std::vector<double> &max_delta_ts, const step_hooks &hooks, bool wtc, bool c_out);
+    // The arguments of propagate_grid() next to the grid. d_out: the output goes to this device buffer and the return value
+    // is empty (no callbacks then). sampling (grid_observables.hpp):
+    //   - observables: the output has one column per observable - ret[(point * n_obs + o) * N + lane] -, bit for bit
+    //     cfunc(obs, vars = state variables) of the state sample, the parameters and the grid time of the row; NaN in every
+    //     column of a row which was not reached. Everything else is as without observables;
+    //   - statistics as well: the observables are folded over the grid points every system reaches, the return value is
+    //     ret[(o * n_stat + k) * N + lane] (d_out: that many doubles), and nothing of the size of the grid is allocated for
+    //     the output. The integrator is left, bit for bit, as by the call with the observables alone.
+    struct grid_call {
+        std::size_t max_steps = 0;
+        std::vector<double> max_delta_ts = {};
+        step_hooks hooks = {};
+        double *d_out = nullptr;
+        grid_sampling sampling = {};
+    };
+    std::vector<double> propagate_grid(std::vector<double> grid, const grid_call &call);
+    // The first meeting of an integrator with the observables of a sampling (nothing to do without): the checks against the
+    // system (std::invalid_argument: an empty list, a variable which is not a state variable, a par[i] the integrator does
+    // not have) and the compilation of the post-step module with their section. No GPU is needed.
+    void prepare_grid_sampling(const grid_sampling &gs);
+    // HIP source and gfx950 code object of a generated module of this integrator.
+    struct module_view {
+        const std::string &source;
+        const std::vector<char> &code;
+    };
+    // The post-step module of a sampling with observables (compiled on first use).
+    [[nodiscard]] module_view grid_sampling_module(const grid_sampling &gs);
     // x -= 2 pi floor(x / 2 pi) on the state variables idx (sorted, < get_dim()) of every system - what the call operator
     // of callback::angle_reducer does: kernel hy_angle_reduce on the integrator's stream over the device-resident state
     // (no download, no switch to eager synchronisation), or on the host mirror when that is the newer copy.
@@ -270,21 +277,19 @@ public:
     // Systems retired by the stop condition of a step_action in the last call which went through a sweep loop
     // (config::batch_semantics == 3; they are not counted by get_n_retired()).
     [[nodiscard]] std::uint64_t get_n_stopped_by_action() const;
-    // HIP source and gfx950 code object of the module of an action for this integrator (compiled on first use; no GPU needed).
-    [[nodiscard]] const std::string &step_action_source(const step_action &act);
-    [[nodiscard]] const std::vector<char> &step_action_code_object(const step_action &act);
+    // The module of an action for this integrator (compiled on first use; no GPU needed).
+    [[nodiscard]] module_view step_action_module(const step_action &act);
     // With set_event_timing(true): (sum of the durations of the hy_step_action launches in ms, number of timed launches).
     [[nodiscard]] std::pair<double, std::uint64_t> get_step_action_kernel_ms() const;
     // HIP source of the stepper variant with the reduction of idx fused in (empty + the reason if the generator declines),
     // and the seconds its last compilation took (0: never compiled / cached).
     [[nodiscard]] std::string get_angle_reduce_variant_source(const std::vector<std::uint32_t> &idx, std::string &why_not) const;
     [[nodiscard]] double get_angle_reduce_compile_seconds() const;
-    // Device-resident loop of propagate_grid(): see tab_propagate.cpp.
+    // Device-resident loop of propagate_grid(), see tab_propagate.cpp: the call, and what propagate_grid() worked out from
+    // it (max_delta_ts: one per system).
     void propagate_grid_device_loop(const std::vector<double> &grid, std::vector<double> &retval,
                                     const std::vector<dfloat> &rem, const std::vector<int> &t_dir,
-                                    const std::vector<double> &max_delta_ts, std::size_t max_steps,
-                                    double *d_out, const cb_t &cb, const std::vector<expression> *obs = nullptr,
-                                    const std::vector<grid_statistic> *stats = nullptr);
+                                    const std::vector<double> &max_delta_ts, const grid_call &call);
     // ---- events (reference: taylor.hpp:1008-1014) ----
     [[nodiscard]] bool with_events() const;
     [[nodiscard]] const std::vector<core_t_event> &get_t_events() const;
@@ -341,15 +346,14 @@ public:
     [[nodiscard]] bool get_event_log_states() const;
     [[nodiscard]] bool has_event_recorders() const;
     [[nodiscard]] const std::vector<char> &event_log_code_object(int which) const;
-    // Terminal-event actions (event_action.hpp): their number, the HIP source and the gfx950 code object of
-    // the action module (kernel hy_ev_action; std::invalid_argument without actions), and what the marker callback of
+    // Terminal-event actions (event_action.hpp): their number, the action module (kernel hy_ev_action;
+    // std::invalid_argument without actions), and what the marker callback of
     // the C ABI does when it is called directly - the action (one of this integrator's) applied to one system.
     [[nodiscard]] std::uint32_t get_n_event_actions() const;
     // With set_event_timing(true): the launches of hy_ev_action run between two HIP events - (sum of the kernel durations
     // in ms, number of timed launches) since the construction.
     [[nodiscard]] std::pair<double, std::uint64_t> get_event_action_kernel_ms() const;
-    [[nodiscard]] const std::string &event_action_source() const;
-    [[nodiscard]] const std::vector<char> &event_action_code_object() const;
+    [[nodiscard]] module_view event_action_module() const;
     void apply_event_action(const event_action &act, std::uint32_t batch_idx);
     // ---- variational integrators (reference: taylor.hpp is_variational() ... eval_taylor_map(); taylor_map.hpp) ----
     [[nodiscard]] bool is_variational() const noexcept;
@@ -366,8 +370,8 @@ public:
     // n_samples displacements per system (kernel hy_tmap_cloud): d_delta[(sys * n_args + a) * n_samples + m], or one cloud
     // for all the systems, d_delta[a * n_samples + m]; d_out[(sys * n_orig_sv + i) * n_samples + m]. Asynchronous.
     void eval_taylor_map_cloud(const double *d_delta, double *d_out, std::uint64_t n_samples, bool shared);
-    [[nodiscard]] const std::string &taylor_map_source() const;
-    [[nodiscard]] const std::vector<char> &taylor_map_code_object() const;
+    // The module of the Taylor map (std::invalid_argument with the reason when there is none).
+    [[nodiscard]] module_view taylor_map_module() const;
     // Mark the device copies as modified by the caller (e.g. initial conditions written by a kernel).
     void mark_device_modified();
     void set_stream(void *hip_stream);
@@ -403,13 +407,30 @@ std::vector<double> make_vector_from(double x);
 // empty otherwise. Defined in angle_reducer.cpp.
 tab_core::red_t angle_reducer_indices_of(step_cb_wrap<taylor_adaptive_batch<double>> &cb);
 // cb holds a step_action (step_action.hpp), or a set whose members all are step_actions or callback::angle_reducers with
-// at least one action: every member is applied on the device (the lib_cb argument of tab_core::propagate_*()). Defined in
+// at least one action: every member is applied on the device (tab_core::step_hooks::lib). Defined in
 // step_action.cpp.
 bool callback_is_library_action(const step_cb_wrap<taylor_adaptive_batch<double>> &cb);
 // What a front end does with the callback of a propagate_*() before it calls the core: the step_actions in it, at any depth
 // of nested sets, meet the integrator (tab_core::prepare_step_action(): std::invalid_argument before anything runs).
-// Returns callback_is_library_action(cb), false for an empty cb: the lib_cb argument of the core.
+// Returns callback_is_library_action(cb), false for an empty cb: step_hooks::lib of the core.
 bool prepare_step_actions(tab_core &core, const step_cb_wrap<taylor_adaptive_batch<double>> &cb);
+
+// kw::observables and kw::statistics of a front end as the value the core takes: statistics without observables throw at
+// run time (grid_sampling). Either may also be a std::optional of its list - how ensemble_propagate_grid_batch() passes
+// them on.
+template <typename... KwArgs>
+grid_sampling grid_sampling_from_kw(const KwArgs &...kw_args)
+{
+    std::optional<std::vector<expression>> obs;
+    std::optional<std::vector<grid_statistic>> stats;
+    if constexpr (kw::has_v<kw::observables_tag, KwArgs...>) {
+        obs = kw::get(kw::observables, 0, kw_args...);
+    }
+    if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
+        stats = kw::get(kw::statistics, 0, kw_args...);
+    }
+    return grid_sampling(std::move(obs), std::move(stats));
+}
 
 // HIP source of the post-step kernel of the device-resident propagate_grid() loop (exposed for the build-time
 // compilation check).
@@ -676,8 +697,16 @@ class taylor_adaptive_batch<double>
         return cfg;
     }
 
+    // What the keyword arguments of a propagate_*() say; user_cb is handed back to the caller.
+    struct propagate_ops {
+        std::size_t max_steps;
+        std::vector<double> max_delta_ts;
+        detail::tab_core::step_hooks hooks;
+        std::shared_ptr<step_callback_batch<double>> user_cb;
+        bool wtc, c_out;
+    };
     template <typename... KwArgs>
-    auto propagate_common_ops(KwArgs &&...kw_args)
+    propagate_ops propagate_common_ops(KwArgs &&...kw_args)
     {
         static_assert(kw::all_named_v<KwArgs...>);
         const auto max_steps = static_cast<std::size_t>(kw::get(kw::max_steps, 0, kw_args...));
@@ -711,21 +740,18 @@ class taylor_adaptive_batch<double>
                 *user_cb = step_callback_batch<double>(step_callback_batch_set<double>(std::move(v)));
             }
         }
-        detail::tab_core::cb_t cb;
-        detail::tab_core::pre_t pre;
-        detail::tab_core::red_t red;
+        detail::tab_core::step_hooks hooks;
         if (*user_cb) {
-            cb = [this, user_cb]() { return (*user_cb)(*this); };
-            pre = [this, user_cb]() { user_cb->pre_hook(*this); };
+            hooks.call = [this, user_cb]() { return (*user_cb)(*this); };
+            hooks.pre = [this, user_cb]() { user_cb->pre_hook(*this); };
             // (The library's own angle_reducer is recognised by type: the core may apply it inside the propagate kernel.)
-            red = detail::angle_reducer_indices_of(*user_cb);
+            hooks.red = detail::angle_reducer_indices_of(*user_cb);
         }
         // (The step_actions in the callback meet the integrator now; lib: the whole callback is library-side.)
-        const bool lib = detail::prepare_step_actions(m_core, *user_cb);
+        hooks.lib = detail::prepare_step_actions(m_core, *user_cb);
         const auto wtc = static_cast<bool>(kw::get(kw::write_tc, false, kw_args...));
         const auto c_out = static_cast<bool>(kw::get(kw::c_output, false, kw_args...));
-        return std::tuple{max_steps, std::move(max_delta_ts), std::move(cb), std::move(user_cb), wtc, c_out, std::move(pre),
-                          std::move(red), lib};
+        return {max_steps, std::move(max_delta_ts), std::move(hooks), std::move(user_cb), wtc, c_out};
     }
 
 public:
@@ -1071,62 +1097,50 @@ public:
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_until(const std::vector<double> &ts,
                                                                            KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        const auto ops = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_until(ts, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
-        return {make_c_out(), std::move(*user_cb)};
+        m_core.propagate_until(ts, ops.max_steps, ops.max_delta_ts, ops.hooks, ops.wtc, ops.c_out);
+        return {make_c_out(), std::move(*ops.user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_until(double t, KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        const auto ops = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_until(std::vector<double>{t}, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
-        return {make_c_out(), std::move(*user_cb)};
+        m_core.propagate_until(std::vector<double>{t}, ops.max_steps, ops.max_delta_ts, ops.hooks, ops.wtc, ops.c_out);
+        return {make_c_out(), std::move(*ops.user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_for(const std::vector<double> &dts,
                                                                          KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        const auto ops = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_for(dts, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
-        return {make_c_out(), std::move(*user_cb)};
+        m_core.propagate_for(dts, ops.max_steps, ops.max_delta_ts, ops.hooks, ops.wtc, ops.c_out);
+        return {make_c_out(), std::move(*ops.user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<std::optional<continuous_output_batch<double>>, step_callback_batch<double>> propagate_for(double dt, KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        const auto ops = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        m_core.propagate_for(std::vector<double>{dt}, max_steps, mdts, cb, wtc, c_out, pre, red, lib);
-        return {make_c_out(), std::move(*user_cb)};
+        m_core.propagate_for(std::vector<double>{dt}, ops.max_steps, ops.max_delta_ts, ops.hooks, ops.wtc, ops.c_out);
+        return {make_c_out(), std::move(*ops.user_cb)};
     }
     template <typename... KwArgs>
     std::tuple<step_callback_batch<double>, std::vector<double>> propagate_grid(std::vector<double> grid,
                                                                                KwArgs &&...kw_args)
     {
-        auto [max_steps, mdts, cb, user_cb, wtc, c_out, pre, red, lib] = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
+        auto ops = propagate_common_ops(std::forward<KwArgs>(kw_args)...);
         m_core.set_callback_context(this);
-        if constexpr (kw::has_v<kw::observables_tag, KwArgs...>) {
-            // (kw::observables: the checks against the system come before anything runs.)
-            const std::vector<expression> obs(kw::get(kw::observables, 0, kw_args...));
-            if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
-                // (kw::statistics: the return value is ret[(observable * n_stat + statistic) * batch_size + lane].)
-                const std::vector<grid_statistic> stats(kw::get(kw::statistics, 0, kw_args...));
-                m_core.prepare_grid_statistics(obs, stats);
-                auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib, &obs, &stats);
-                return {std::move(*user_cb), std::move(ret)};
-            } else {
-                m_core.prepare_grid_observables(obs);
-                auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib, &obs);
-                return {std::move(*user_cb), std::move(ret)};
-            }
-        } else if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
-            throw std::invalid_argument(detail::grid_statistics_need_observables);
-        } else {
-            auto ret = m_core.propagate_grid(std::move(grid), max_steps, mdts, cb, nullptr, pre, red, lib);
-            return {std::move(*user_cb), std::move(ret)};
-        }
+        // (kw::observables, kw::statistics: the checks against the system come before anything runs.)
+        auto gs = detail::grid_sampling_from_kw(kw_args...);
+        m_core.prepare_grid_sampling(gs);
+        auto ret = m_core.propagate_grid(std::move(grid), {.max_steps = ops.max_steps,
+                                                           .max_delta_ts = std::move(ops.max_delta_ts),
+                                                           .hooks = std::move(ops.hooks),
+                                                           .sampling = std::move(gs)});
+        return {std::move(*ops.user_cb), std::move(ret)};
     }
 
     // MI355X extensions.

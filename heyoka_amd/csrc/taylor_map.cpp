@@ -366,19 +366,13 @@ const std::vector<double> &tab_core::get_tstate() const
     return m_impl->tstate;
 }
 
-const std::string &tab_core::taylor_map_source() const
+tab_core::module_view tab_core::taylor_map_module() const
 {
     check_variational(*this, "taylor_map_source");
-    return m_impl->var->tmap_source;
-}
-
-const std::vector<char> &tab_core::taylor_map_code_object() const
-{
-    check_variational(*this, "taylor_map_code_object");
     if (!m_impl->var->tmap_cmod) {
         throw not_implemented_error(m_impl->var->tmap_why);
     }
-    return m_impl->var->tmap_cmod->code;
+    return {m_impl->var->tmap_source, m_impl->var->tmap_cmod->code};
 }
 
 void tab_core::eval_taylor_map_device(const double *d_in, double *d_out)

@@ -74,13 +74,14 @@ static void host_checks()
                  "The observable 0 of propagate_grid() uses the variable 'w', which is not a state variable of the system");
     // The module: two columns, both rows, the three kernels; the same text for a copy.
     const auto obs = observables();
-    const auto &src = ta.core().grid_observables_source(obs);
+    const detail::grid_sampling gs(obs);
+    const auto &src = ta.core().grid_sampling_module(gs).source;
     CHECK(src.find("#define HY_NOUT 2u") != std::string::npos);
     CHECK(src.find("hy_grid_post(") != std::string::npos && src.find("hy_grid_obs0(") != std::string::npos
           && src.find("hy_grid_unsample(") != std::string::npos);
-    CHECK(!ta.core().grid_observables_code_object(obs).empty());
+    CHECK(!ta.core().grid_sampling_module(gs).code.empty());
     auto tb = ta;
-    CHECK(tb.core().grid_observables_source(obs) == src);
+    CHECK(tb.core().grid_sampling_module(gs).source == src);
     std::puts("HOST OK");
 }
 

@@ -85,15 +85,17 @@ static void host_checks()
                  "The statistics of propagate_grid() need a list of observables");
     // The module: the three kernels, 14 accumulators per lane; t_min alone keeps the minimum in a hidden slot; another module
     // than the one of the observables alone, and the same text for a copy.
-    const auto &src = ta.core().grid_statistics_source(obs, all_stats);
+    const detail::grid_sampling folded(obs, all_stats);
+    const auto &src = ta.core().grid_sampling_module(folded).source;
     CHECK(src.find("#define HY_NOUT 2u") != std::string::npos && src.find("#define HY_NSLOT 14u") != std::string::npos);
     CHECK(src.find("hy_grid_post(") != std::string::npos && src.find("hy_grid_obs0(") != std::string::npos
           && src.find("hy_grid_unsample(") != std::string::npos);
-    CHECK(ta.core().grid_statistics_source(obs, {gs::t_min}).find("#define HY_NSLOT 4u") != std::string::npos);
-    CHECK(src != ta.core().grid_observables_source(obs));
-    CHECK(!ta.core().grid_statistics_code_object(obs, all_stats).empty());
+    CHECK(ta.core().grid_sampling_module(detail::grid_sampling(obs, std::vector<gs>{gs::t_min})).source.find("#define HY_NSLOT 4u")
+          != std::string::npos);
+    CHECK(src != ta.core().grid_sampling_module(detail::grid_sampling(obs)).source);
+    CHECK(!ta.core().grid_sampling_module(folded).code.empty());
     auto tb = ta;
-    CHECK(tb.core().grid_statistics_source(obs, all_stats) == src);
+    CHECK(tb.core().grid_sampling_module(folded).source == src);
     std::puts("HOST OK");
 }
 
