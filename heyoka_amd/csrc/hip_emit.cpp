@@ -388,6 +388,103 @@ __device__ __forceinline__ bool hy_finite(double x)
     return ret;
 }
 
+// The bookkeeping around a step, once for the steppers with one system-loop and one step-loop per kernel (unrolled, first
+// wave-cluster generator, block, HBM-tape table, staged table): the step / propagate_until contract of the reference for
+// hy_kargs::mode 0 (one step, limit a.lim), 1 (propagate to tfin, a.lim the optional max_delta_t), 2 (raw stepper) and
+// 4 (stepper with events: the caller leaves the loop before HY_STEP_ADVANCE and stores last_h alone). The end of a step is
+// HY_STEP_TAIL in prelude(); this block stays out of prelude() because the auxiliary kernels include that and not this.
+// Every stepper writes it right behind prelude(). The fragments share their local names (a, t_hi, t_lo, h, lim, rem, tfin,
+// ...) with HY_STEP_TAIL and with each other, so they are macros, not functions. The pipelined / pair generator
+// (hip_emit_cluster2*.cpp) has a loop of another shape and does not use them.
+const std::string &step_loop_source()
+{
+    static const std::string ret = R"HIP(
+// Is the remaining time non-negative (reference: src/taylor_adaptive_batch.cpp:1272)? Two spellings which compile to
+// different code: the staged table stepper uses HY_DIR_SELECT, the other four HY_DIR_BRANCHY. Which stepper has which is
+// what its code object was built from before the fragments were shared, not a preference: changing one changes a kernel.
+#define HY_DIR_BRANCHY(R) (((R).hi > 0.0) || ((R).hi == 0.0 && (R).lo >= 0.0))
+#define HY_DIR_SELECT(R) (((R).hi > 0.0) | (((R).hi == 0.0) & ((R).lo >= 0.0)))
+
+// Limits of system S (reference: src/taylor_adaptive_batch.cpp:1264-1273): mode 1 - final time, remaining time, direction
+// and the optional max_delta_t; any other mode - the signed limit of the single step.
+#define HY_STEP_LIMITS(S, DIR)                                                                                         \
+    hy_df tfin, rem;                                                                                                   \
+    tfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;                                                          \
+    bool t_dir = true;                                                                                                 \
+    double mdt = __builtin_inf();                                                                                      \
+    double step_lim = 0.0;                                                                                             \
+    if (a.mode == 1) {                                                                                                 \
+        tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[S] : a.tfin_s_hi;                                                 \
+        tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[S] : a.tfin_s_lo;                                                 \
+        hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;                                                                    \
+        rem = hy_df_sub(tfin, tcur);                                                                                   \
+        t_dir = DIR(rem);                                                                                              \
+        if (a.lim != nullptr) mdt = a.lim[S];                                                                          \
+    } else {                                                                                                           \
+        step_lim = a.lim[S];                                                                                           \
+    }
+
+// What HY_STEP_TAIL counts.
+#define HY_STEP_COUNTERS                                                                                               \
+    u64 n_steps = 0, iter = 0;                                                                                         \
+    double min_h = __builtin_inf(), max_h = 0.0, last_h = 0.0;                                                         \
+    i64 outcome = HY_OC_SUCCESS;
+
+// Time limit for this step (reference: src/taylor_adaptive_batch.cpp:1378-1387).
+// NOTE: selects, not an if/else on the (per-lane) direction: see the note on HY_LIBM1.
+#define HY_STEP_LIM                                                                                                    \
+    double lim;                                                                                                        \
+    if (a.mode == 1) {                                                                                                 \
+        hy_df m; m.lo = 0.0;                                                                                           \
+        m.hi = t_dir ? mdt : -mdt;                                                                                     \
+        const bool lt_fwd = hy_df_lt(rem, m), lt_bwd = hy_df_lt(m, rem);                                               \
+        const bool rem_first = (t_dir & lt_fwd) | (!t_dir & lt_bwd);                                                   \
+        lim = rem_first ? rem.hi : m.hi;                                                                               \
+    } else {                                                                                                           \
+        lim = step_lim;                                                                                                \
+    }
+
+// Step size from the infinity norms m0, mo, mom1 of the orders 0, p, p - 1 and the limit (taylor_determine_h(),
+// src/taylor_00.cpp:102-273). INV_P = 1 / p, INV_PM1 = 1 / (p - 1), RHOFAC = emit_detail::rhofac(p).
+#define HY_STEP_SIZE(INV_P, INV_PM1, RHOFAC)                                                                           \
+    const double num_rho = (m0 <= 1.0) ? 1.0 : m0;                                                                     \
+    const double rho_o = hy_root(num_rho / mo, INV_P);                                                                 \
+    const double rho_om1 = hy_root(num_rho / mom1, INV_PM1);                                                           \
+    const double rho_m = hy_min(rho_o, rho_om1);                                                                       \
+    double h = rho_m * RHOFAC;                                                                                         \
+    h = hy_min(h, fabs(lim));                                                                                          \
+    h = (lim < 0.0) ? -h : h;
+
+// The time after the step, in double-length arithmetic (reference: src/taylor_adaptive_batch.cpp:702-727).
+#define HY_STEP_ADVANCE                                                                                                \
+    {                                                                                                                  \
+        hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;                                                                    \
+        hy_df hh; hh.hi = h; hh.lo = 0.0;                                                                              \
+        const hy_df nt = hy_df_add(tcur, hh);                                                                          \
+        t_hi = nt.hi; t_lo = nt.lo;                                                                                    \
+    }                                                                                                                  \
+    last_h = h;
+
+// The results of system S, the state apart; which lanes store them is the caller's business. Raw stepper ABI (mode 2):
+// the time is left alone and the step taken is returned through the (in/out) limits array.
+#define HY_STEP_RESULT(S)                                                                                              \
+    if (a.mode != 2) {                                                                                                 \
+        a.time_hi[S] = t_hi;                                                                                           \
+        a.time_lo[S] = t_lo;                                                                                           \
+    } else {                                                                                                           \
+        const_cast<double *>(a.lim)[S] = last_h;                                                                       \
+    }                                                                                                                  \
+    a.last_h[S] = last_h;                                                                                              \
+    a.outcome[S] = outcome;                                                                                            \
+    if (a.mode == 1) {                                                                                                 \
+        a.min_h[S] = min_h;                                                                                            \
+        a.max_h[S] = max_h;                                                                                            \
+        a.n_steps[S] = n_steps;                                                                                        \
+    }
+)HIP";
+    return ret;
+}
+
 // Scaling + safety factor of the step-size selector, folded on the host in double precision
 // (reference: taylor_determine_h_rhofac(), src/taylor_00.cpp:84-94).
 double rhofac(std::uint32_t order)
@@ -554,39 +651,7 @@ std::string emit_unrolled_kernel(const taylor_program &p, const emit_options &op
     } else if (!reg_jets) {
         os << "double *jet = a.tc + s;\n";
     }
-    os << R"HIP(
-hy_df tfin, rem;
-tfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;
-bool t_dir = true;
-double mdt = __builtin_inf();
-double step_lim = 0.0;
-if (a.mode == 1) {
-    tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[s] : a.tfin_s_hi;
-    tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[s] : a.tfin_s_lo;
-    hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-    rem = hy_df_sub(tfin, tcur);
-    t_dir = (rem.hi > 0.0) || (rem.hi == 0.0 && rem.lo >= 0.0);
-    if (a.lim != nullptr) mdt = a.lim[s];
-} else {
-    step_lim = a.lim[s];
-}
-u64 n_steps = 0, iter = 0;
-double min_h = __builtin_inf(), max_h = 0.0, last_h = 0.0;
-i64 outcome = HY_OC_SUCCESS;
-for (;;) {
-// Time limit for this step (reference: src/taylor_adaptive_batch.cpp:1378-1387).
-double lim;
-if (a.mode == 1) {
-    hy_df m; m.lo = 0.0;
-    // NOTE: selects, not an if/else on the (per-lane) direction: see the note on HY_LIBM1.
-    m.hi = t_dir ? mdt : -mdt;
-    const bool lt_fwd = hy_df_lt(rem, m), lt_bwd = hy_df_lt(m, rem);
-    const bool rem_first = (t_dir & lt_fwd) | (!t_dir & lt_bwd);
-    lim = rem_first ? rem.hi : m.hi;
-} else {
-    lim = step_lim;
-}
-)HIP";
+    os << "HY_STEP_LIMITS(s, HY_DIR_BRANCHY)\nHY_STEP_COUNTERS\nfor (;;) {\nHY_STEP_LIM\n";
     if (stream_tc || !reg_jets) {
         // NOTE: the (order + 1) * n_eq store addresses are invariants of the step loop: left alone, the compiler hoists
         // all of them into registers (2 per address). Laundering the base pointer once per step makes them per-step values.
@@ -884,17 +949,8 @@ if (a.mode == 1) {
 
     }
 
-    // ---- Bookkeeping (reference: src/taylor_adaptive_batch.cpp:702-727, :1402-1460). ----
-    os << R"HIP(
-{
-    hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-    hy_df hh; hh.hi = h; hh.lo = 0.0;
-    const hy_df nt = hy_df_add(tcur, hh);
-    t_hi = nt.hi; t_lo = nt.lo;
-}
-last_h = h;
-bool nf = !(hy_finite(t_hi) & hy_finite(t_lo));
-)HIP";
+    // ---- Bookkeeping (emit_detail::step_loop_source(), HY_STEP_TAIL). ----
+    os << "HY_STEP_ADVANCE\nbool nf = !(hy_finite(t_hi) & hy_finite(t_lo));\n";
     for (std::uint32_t i = 0; i < n_eq; ++i) {
         os << "nf = nf | !hy_finite(x" << i << ");\n";
     }
@@ -908,23 +964,7 @@ HY_STEP_TAIL(nf, true)
     for (std::uint32_t i = 0; i < n_eq; ++i) {
         os << "a.state[(u64)" << i << "u * N + s] = x" << i << ";\n";
     }
-    os << R"HIP(
-if (a.mode != 2) {
-    a.time_hi[s] = t_hi;
-    a.time_lo[s] = t_lo;
-} else {
-    // Raw stepper ABI: the step taken is returned through the (in/out) limits array.
-    const_cast<double *>(a.lim)[s] = last_h;
-}
-a.last_h[s] = last_h;
-a.outcome[s] = outcome;
-if (a.mode == 1) {
-    a.min_h[s] = min_h;
-    a.max_h[s] = max_h;
-    a.n_steps[s] = n_steps;
-}
-}
-)HIP";
+    os << "HY_STEP_RESULT(s)\n}\n";
 
     n_stmt += e.n_stmt;
     return os.str();
@@ -950,7 +990,7 @@ std::uint64_t reg_jet_estimate(const taylor_program &p, std::uint32_t order, boo
 emitted_module emit_unrolled(const taylor_program &p, const emit_options &opts)
 {
     std::ostringstream src;
-    src << prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << rules_source(p);
+    src << prelude() << step_loop_source() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << rules_source(p);
     emit_dout(src, p, opts);
 
     emitted_module ret;

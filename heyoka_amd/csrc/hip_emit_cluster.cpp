@@ -2115,7 +2115,7 @@ emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts
 
     // ===================== module text =====================
     std::ostringstream src;
-    src << prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source);
+    src << prelude() << emit_detail::step_loop_source() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source);
     emit_detail::emit_dout(src, p, opts);
 
     src << emit_detail::wsync_macro;
@@ -2204,36 +2204,10 @@ double t_hi = a.time_hi[s], t_lo = a.time_lo[s];
         src << "double xs" << r << " = a.state[(u64)svi" << r << " * N + s];\n";
     }
     src << R"HIP(
-hy_df tfin, rem;
-tfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;
-bool t_dir = true;
-double mdt = __builtin_inf();
-double step_lim = 0.0;
-if (a.mode == 1) {
-    tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[s] : a.tfin_s_hi;
-    tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[s] : a.tfin_s_lo;
-    hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-    rem = hy_df_sub(tfin, tcur);
-    t_dir = (rem.hi > 0.0) || (rem.hi == 0.0 && rem.lo >= 0.0);
-    if (a.lim != nullptr) mdt = a.lim[s];
-} else {
-    step_lim = a.lim[s];
-}
-u64 n_steps = 0, iter = 0;
-double min_h = __builtin_inf(), max_h = 0.0, last_h = 0.0;
-i64 outcome = HY_OC_SUCCESS;
+HY_STEP_LIMITS(s, HY_DIR_BRANCHY)
+HY_STEP_COUNTERS
 for (;;) {
-double lim;
-if (a.mode == 1) {
-    hy_df m; m.lo = 0.0;
-    // NOTE: selects, not an if/else on the (per-lane) direction: see the note on HY_LIBM1.
-    m.hi = t_dir ? mdt : -mdt;
-    const bool lt_fwd = hy_df_lt(rem, m), lt_bwd = hy_df_lt(m, rem);
-    const bool rem_first = (t_dir & lt_fwd) | (!t_dir & lt_bwd);
-    lim = rem_first ? rem.hi : m.hi;
-} else {
-    lim = step_lim;
-}
+HY_STEP_LIM
 )HIP";
     src << body.str();
 
@@ -2243,13 +2217,8 @@ if (a.mode == 1) {
         src << "mo = hy_max(mo, __shfl_xor(mo, " << m << ", 64));\n";
         src << "mom1 = hy_max(mom1, __shfl_xor(mom1, " << m << ", 64));\n";
     }
-    src << "const double num_rho = (m0 <= 1.0) ? 1.0 : m0;\n";
-    src << "const double rho_o = hy_root(num_rho / mo, " << fp_literal(1. / static_cast<double>(order)) << ");\n";
-    src << "const double rho_om1 = hy_root(num_rho / mom1, " << fp_literal(1. / static_cast<double>(order - 1u))
-        << ");\n";
-    src << "const double rho_m = hy_min(rho_o, rho_om1);\n";
-    src << "double h = rho_m * " << fp_literal(rhofac(order)) << ";\n";
-    src << "h = hy_min(h, fabs(lim));\nh = (lim < 0.0) ? -h : h;\n";
+    src << "HY_STEP_SIZE(" << fp_literal(1. / static_cast<double>(order)) << ", " << fp_literal(1. / static_cast<double>(order - 1u))
+        << ", " << fp_literal(rhofac(order)) << ")\n";
 
     // State update from the scratch jets.
     src << "asm volatile(\"\" ::: \"memory\");\n";
@@ -2273,13 +2242,7 @@ if (a.mode == 1) {
         }
     }
     src << R"HIP(
-{
-    hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-    hy_df hh; hh.hi = h; hh.lo = 0.0;
-    const hy_df nt = hy_df_add(tcur, hh);
-    t_hi = nt.hi; t_lo = nt.lo;
-}
-last_h = h;
+HY_STEP_ADVANCE
 int nfi = !(hy_finite(t_hi) && hy_finite(t_lo)) ? 1 : 0;
 )HIP";
     for (std::uint32_t r = 0; r < sv_rounds; ++r) {
@@ -2307,19 +2270,7 @@ HY_STEP_TAIL(nfi != 0, l == 0u && live)
     }
     src << R"HIP(
 if (l == 0u && live) {
-    if (a.mode != 2) {
-        a.time_hi[s] = t_hi;
-        a.time_lo[s] = t_lo;
-    } else {
-        const_cast<double *>(a.lim)[s] = last_h;
-    }
-    a.last_h[s] = last_h;
-    a.outcome[s] = outcome;
-    if (a.mode == 1) {
-        a.min_h[s] = min_h;
-        a.max_h[s] = max_h;
-        a.n_steps[s] = n_steps;
-    }
+    HY_STEP_RESULT(s)
 }
 }
 }

@@ -27,6 +27,9 @@ namespace heyoka_amd::emit_detail
 
 // Common device-side prelude: argument block, outcome codes, double-length arithmetic, helpers.
 const std::string &prelude();
+// The bookkeeping around a step (limits, counters, time advance, result stores) as macros next to the prelude's
+// HY_STEP_TAIL: written right behind prelude() by the steppers which use them.
+const std::string &step_loop_source();
 // "#define name (value)" for the kernels: every outcome code in a source comes from the enumerators through this.
 std::string outcome_define(const char *name, taylor_outcome oc);
 

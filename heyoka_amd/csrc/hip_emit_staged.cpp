@@ -1050,7 +1050,7 @@ emitted_module emit_staged(const taylor_program &p, const emit_options &opts, st
 
     // ---- module text ----
     std::ostringstream src;
-    src << emit_detail::prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
+    src << emit_detail::prelude() << emit_detail::step_loop_source() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
     emit_detail::emit_dout(src, p, opts);
     src << emit_detail::wsync_macro;
     {
@@ -1162,38 +1162,13 @@ for (;;) {
     }
     src << R"HIP(
     double t_hi = a.time_hi[s], t_lo = a.time_lo[s];
-    hy_df tfin, rem;
-    tfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;
-    bool t_dir = true;
-    double mdt = __builtin_inf();
-    double step_lim = 0.0;
-    if (a.mode == 1) {
-        tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[s] : a.tfin_s_hi;
-        tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[s] : a.tfin_s_lo;
-        hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-        rem = hy_df_sub(tfin, tcur);
-        t_dir = (rem.hi > 0.0) | ((rem.hi == 0.0) & (rem.lo >= 0.0));
-        if (a.lim != nullptr) mdt = a.lim[s];
-    } else {
-        step_lim = a.lim[s];
-    }
+    HY_STEP_LIMITS(s, HY_DIR_SELECT)
     HY_SYNC();
     for (unsigned i = lane; i < HY_N_EQ; i += HY_LANES) hy_sv(i, 0u) = a.state[(u64)i * N + s];
     HY_SYNC();
-    u64 n_steps = 0, iter = 0;
-    double min_h = __builtin_inf(), max_h = 0.0, last_h = 0.0;
-    i64 outcome = HY_OC_SUCCESS;
+    HY_STEP_COUNTERS
     for (;;) {
-        double lim;
-        if (a.mode == 1) {
-            hy_df m; m.lo = 0.0;
-            m.hi = t_dir ? mdt : -mdt;
-            const bool lt_fwd = hy_df_lt(rem, m), lt_bwd = hy_df_lt(m, rem);
-            const bool rem_first = (t_dir & lt_fwd) | (!t_dir & lt_bwd);
-            lim = rem_first ? rem.hi : m.hi;
-        } else {
-            lim = step_lim;
-        }
+        HY_STEP_LIM
         c.t_hi = t_hi;
         // ---- order 0 ----
 )HIP";
@@ -1233,13 +1208,7 @@ for (;;) {
             m0 = hy_max(m0, hy_red[3u * w]); mo = hy_max(mo, hy_red[3u * w + 1u]); mom1 = hy_max(mom1, hy_red[3u * w + 2u]);
         }
 #endif
-        const double num_rho = (m0 <= 1.0) ? 1.0 : m0;
-        const double rho_o = hy_root(num_rho / mo, 1.0 / (double)HY_ORDER);
-        const double rho_om1 = hy_root(num_rho / mom1, 1.0 / (double)(HY_ORDER - 1u));
-        const double rho_m = hy_min(rho_o, rho_om1);
-        double h = rho_m * HY_RHOFAC;
-        h = hy_min(h, fabs(lim));
-        h = (lim < 0.0) ? -h : h;
+        HY_STEP_SIZE(1.0 / (double)HY_ORDER, 1.0 / (double)(HY_ORDER - 1u), HY_RHOFAC)
 
         if (a.tc != nullptr) {
             for (unsigned q = lane; q < HY_N_EQ * (HY_ORDER + 1u); q += HY_LANES) {
@@ -1293,13 +1262,7 @@ for (;;) {
         nf = __builtin_amdgcn_ballot_w64(nf) != 0ull;
         HY_WSYNC();
 #endif
-        {
-            hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-            hy_df hh; hh.hi = h; hh.lo = 0.0;
-            const hy_df nt = hy_df_add(tcur, hh);
-            t_hi = nt.hi; t_lo = nt.lo;
-        }
-        last_h = h;
+        HY_STEP_ADVANCE
         nf = nf | !(hy_finite(t_hi) & hy_finite(t_lo));
         HY_STEP_TAIL(nf, lane == 0u)
     }
@@ -1311,19 +1274,7 @@ for (;;) {
         continue;
     }
     for (unsigned i = lane; i < HY_N_EQ; i += HY_LANES) a.state[(u64)i * N + s] = hy_lds_tape[i * HY_P];
-    if (a.mode != 2) {
-        a.time_hi[s] = t_hi;
-        a.time_lo[s] = t_lo;
-    } else {
-        const_cast<double *>(a.lim)[s] = last_h;
-    }
-    a.last_h[s] = last_h;
-    a.outcome[s] = outcome;
-    if (a.mode == 1) {
-        a.min_h[s] = min_h;
-        a.max_h[s] = max_h;
-        a.n_steps[s] = n_steps;
-    }
+    HY_STEP_RESULT(s)
 }
 }
 )HIP";

@@ -580,38 +580,12 @@ extern "C" __global__ void __launch_bounds__(256, 4) hy_taylor(const hy_kargs a)
     for (u64 s = tid; s < N; s += T) {
         c.s = s;
         double t_hi = a.time_hi[s], t_lo = a.time_lo[s];
-        hy_df tfin, rem;
-        tfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;
-        bool t_dir = true;
-        double mdt = __builtin_inf();
-        double step_lim = 0.0;
-        if (a.mode == 1) {
-            tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[s] : a.tfin_s_hi;
-            tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[s] : a.tfin_s_lo;
-            hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-            rem = hy_df_sub(tfin, tcur);
-            t_dir = (rem.hi > 0.0) || (rem.hi == 0.0 && rem.lo >= 0.0);
-            if (a.lim != nullptr) mdt = a.lim[s];
-        } else {
-            step_lim = a.lim[s];
-        }
+        HY_STEP_LIMITS(s, HY_DIR_BRANCHY)
         // The order-0 row of the tape doubles as the current state.
         for (unsigned i = 0; i < HY_N_EQ; ++i) hy_tp(c, 0, i) = a.state[(u64)i * N + s];
-        u64 n_steps = 0, iter = 0;
-        double min_h = __builtin_inf(), max_h = 0.0, last_h = 0.0;
-        i64 outcome = HY_OC_SUCCESS;
+        HY_STEP_COUNTERS
         for (;;) {
-            double lim;
-            if (a.mode == 1) {
-                hy_df m; m.lo = 0.0;
-                // NOTE: selects, not an if/else on the (per-lane) direction: see the note on HY_LIBM1.
-                m.hi = t_dir ? mdt : -mdt;
-                const bool lt_fwd = hy_df_lt(rem, m), lt_bwd = hy_df_lt(m, rem);
-                const bool rem_first = (t_dir & lt_fwd) | (!t_dir & lt_bwd);
-                lim = rem_first ? rem.hi : m.hi;
-            } else {
-                lim = step_lim;
-            }
+            HY_STEP_LIM
             c.t_hi = t_hi;
             hy_nodes_order(c, 0);
             for (unsigned k = 1; k < HY_ORDER; ++k) {
@@ -641,13 +615,7 @@ extern "C" __global__ void __launch_bounds__(256, 4) hy_taylor(const hy_kargs a)
                 mom1 = hy_max(mom1, fabs(hy_tp(c, HY_ORDER - 1u, hy_ev_u[e])));
             }
 #endif
-            const double num_rho = (m0 <= 1.0) ? 1.0 : m0;
-            const double rho_o = hy_root(num_rho / mo, 1.0 / (double)HY_ORDER);
-            const double rho_om1 = hy_root(num_rho / mom1, 1.0 / (double)(HY_ORDER - 1u));
-            const double rho_m = hy_min(rho_o, rho_om1);
-            double h = rho_m * HY_RHOFAC;
-            h = hy_min(h, fabs(lim));
-            h = (lim < 0.0) ? -h : h;
+            HY_STEP_SIZE(1.0 / (double)HY_ORDER, 1.0 / (double)(HY_ORDER - 1u), HY_RHOFAC)
 
             if (a.tc != nullptr) {
                 for (unsigned i = 0; i < HY_N_EQ; ++i)
@@ -691,13 +659,7 @@ extern "C" __global__ void __launch_bounds__(256, 4) hy_taylor(const hy_kargs a)
                 hy_tp(c, 0, i) = res;
                 nf = nf | !hy_finite(res);
             }
-            {
-                hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
-                hy_df hh; hh.hi = h; hh.lo = 0.0;
-                const hy_df nt = hy_df_add(tcur, hh);
-                t_hi = nt.hi; t_lo = nt.lo;
-            }
-            last_h = h;
+            HY_STEP_ADVANCE
             nf = nf | !(hy_finite(t_hi) & hy_finite(t_lo));
             HY_STEP_TAIL(nf, true)
         }
@@ -706,19 +668,7 @@ extern "C" __global__ void __launch_bounds__(256, 4) hy_taylor(const hy_kargs a)
             continue;
         }
         for (unsigned i = 0; i < HY_N_EQ; ++i) a.state[(u64)i * N + s] = hy_tp(c, 0, i);
-        if (a.mode != 2) {
-            a.time_hi[s] = t_hi;
-            a.time_lo[s] = t_lo;
-        } else {
-            const_cast<double *>(a.lim)[s] = last_h;
-        }
-        a.last_h[s] = last_h;
-        a.outcome[s] = outcome;
-        if (a.mode == 1) {
-            a.min_h[s] = min_h;
-            a.max_h[s] = max_h;
-            a.n_steps[s] = n_steps;
-        }
+        HY_STEP_RESULT(s)
     }
 }
 )HIP";
@@ -971,7 +921,7 @@ emitted_module emit_table(const taylor_program &p, const emit_options &opts)
     }
 
     std::ostringstream src;
-    src << emit_detail::prelude() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
+    src << emit_detail::prelude() << emit_detail::step_loop_source() << (opts.angle_reduce.empty() ? "" : angle_reduce_helper_source) << emit_detail::rules_source(p);
     emit_detail::emit_dout(src, p, opts);
     table_detail::emit_tables_and_rules(src, p, opts, "", "64u");
     src << table_hbm_kernel_code;

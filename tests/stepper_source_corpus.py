@@ -1,20 +1,33 @@
 #!/usr/bin/env python
 """Fingerprints of the generated steppers, for refactors of the generators: `python tests/stepper_source_corpus.py OUT`
 constructs a corpus of integrators (no GPU is needed: the generator is host code and hiprtc cross-compiles) and writes one
-JSON line per entry with hip_source_mode, the sha256 of hip_source and of code_object, lanes_per_system and the statement
-count as hip_source_mode prints them. Generation and compilation are deterministic, so a change which is meant to leave
-every kernel as it is is one after which this file is byte for byte the file of the parent commit (`diff` is the check;
-no hash file is committed - it would have to change with every kernel improvement). Not collected by pytest.
+JSON line per entry with hip_source_mode, three hashes, lanes_per_system and the statement count as hip_source_mode prints
+them. Generation and compilation are deterministic; no hash file is committed (it would have to change with every kernel
+improvement): write the file at the parent commit and at the result and `diff` the two. Not collected by pytest.
 
-The corpus: the wave-cluster families of tests/test_batch_independence.py, the outer Solar System under every switch of
-the pipelined / lane-pair / one-lane-per-pair generator (hip_emit_cluster2*.cpp), its stepper with events under the
-switches of the event path, and the systems which take the retries of emit_hip_module() (block mode with and without the
-v2 cluster phase, linearised accelerations, multi-class plans)."""
+What each hash is good for:
+- hip_source_sha256 (the generated text): a generator this change is not meant to touch emits the same text, comments
+  included - the whole line of such an entry is identical.
+- device_code_sha256 (the contents of the ELF sections .text, .rodata and .note of the code object, in this order: the
+  instructions, the constant tables, the kernel descriptors' metadata - registers, LDS, scratch, arguments): the check of a
+  change which moves or rewrites source text and is meant to leave the machine code alone. Comments, macro names and the
+  names of static symbols do not reach it.
+- code_object_sha256 (the whole file): changes with any edit of the text, a comment included (the symbol hash tables
+  differ), so it says no more than hip_source_sha256 unless the text is identical - then it pins the compiler.
+
+The corpus: the families of tests/test_batch_independence.py (block_v2_nbody64 is left out: it alone compiles for minutes),
+the outer Solar System under every switch of the pipelined / lane-pair / one-lane-per-pair generator
+(hip_emit_cluster2*.cpp), its stepper with events under the switches of the event path, the systems which take the retries
+of emit_hip_module() (block mode with and without the v2 cluster phase, linearised accelerations, multi-class plans), the
+first wave-cluster generator with one class of clusters (cluster_kernel="v1"), and the straight-line, HBM-tape and staged
+steppers with events (HY_N_EV > 0, mode 4), without compensated summation and with a fused angle reduction."""
 import hashlib
 import json
 import os
 import re
+import struct
 import sys
+import types
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 for p_ in (os.path.join(HERE, "emu"), os.path.join(os.path.dirname(HERE), "oracle"), os.path.dirname(HERE), HERE):
@@ -75,7 +88,46 @@ def corpus():
     # The dispatch of emit_hip_module().
     out += [family("block_v2"), family("block_centres"), family("multi_class")]
     out.append(("equal_masses_linearised", lambda: hy.taylor_adaptive_batch(hy.model.nbody(6), None, N, high_accuracy=True), None))
+    # The steppers with one copy of the step loop each (emit_detail::step_loop_source()).
+    out += [family(n) for n in ("unrolled", "unrolled_two_waves", "unrolled_register_jets", "staged", "staged_functions", "table_hbm",
+                                "table_hbm_functions")]
+    out.append(("cluster_v1", lambda: outer(cluster_kernel="v1"), None))
+    hbm = {"HEYOKA_AMD_TABLE_LDS": "0"}
+    out.append(("events:unrolled", lambda: tan(**_tan_events()), None))
+    out.append(("events:staged", lambda: outer_ev(emitter="table"), None))
+    out.append(("events:table_hbm", lambda: outer_ev(emitter="table"), hbm))
+    out.append(("table_hbm:high_accuracy=False", lambda: outer(emitter="table", high_accuracy=False), hbm))
+    for tag, kw, env in (("unrolled", {}, None), ("staged", {"emitter": "table"}, None), ("table_hbm", {"emitter": "table"}, hbm)):
+        out.append(("angle_reduce:" + tag, lambda kw=kw: fused_angle_reduce(tan(**kw), [1]), env))
     return out
+
+
+def tan(**kw):
+    return hy.taylor_adaptive_batch(tbi.tan_system(hy), None, N, **kw)
+
+
+def _tan_events():
+    x, y = hy.make_vars("x", "y")
+    return dict(nt_events=[hy.nt_event(x - 0.1, lambda *a: None)], t_events=[hy.t_event(x + y, lambda *a: True)])
+
+
+def fused_angle_reduce(ta, idx):
+    """The variant of ta's stepper with callback::angle_reducer fused in, as an object with the three attributes main() reads."""
+    src, why = ta.angle_reduce_variant_source(idx)
+    assert src, why
+    return types.SimpleNamespace(hip_source=src, code_object=hy.hiprtc_compile(src), hip_source_mode=ta.hip_source_mode + " [angle_reduce]")
+
+
+def device_code(elf):
+    """The contents of the sections .text, .rodata and .note of an ELF64 (little-endian) file, concatenated in this order."""
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
+    assert elf[:6] == b"\x7fELF\x02\x01" and shentsize == 64, "not an ELF64 little-endian file"
+    hdr = [struct.unpack_from("<IIQQQQ", elf, shoff + 64 * i) for i in range(shnum)]  # name, type, flags, addr, offset, size
+    strtab = elf[hdr[shstrndx][4]:hdr[shstrndx][4] + hdr[shstrndx][5]]
+    by_name = {strtab[h[0]:strtab.index(b"\0", h[0])].decode(): elf[h[4]:h[4] + h[5]] for h in hdr if h[1] != 8}  # (8: SHT_NOBITS)
+    assert ".text" in by_name and ".note" in by_name, sorted(by_name)
+    return b"".join(by_name.get(n, b"") for n in (".text", ".rodata", ".note"))
 
 
 def main(path):
@@ -89,6 +141,7 @@ def main(path):
             stmts = re.search(r"statements: (\d+)", mode)
             f.write(json.dumps({"entry": name, "hip_source_mode": mode, "hip_source_sha256": sha(ta.hip_source.encode()),
                                 "code_object_sha256": sha(bytes(ta.code_object)),
+                                "device_code_sha256": sha(device_code(bytes(ta.code_object))),
                                 "lanes_per_system": int(lanes.group(1)) if lanes else None,
                                 "statements": int(stmts.group(1)) if stmts else None}, sort_keys=True) + "\n")
             f.flush()
