@@ -29,7 +29,7 @@ enum class emit_mode { unrolled, cluster, table, block };
 //   HEYOKA_AMD_NO_PAIR_EVENTS         close-encounter events through the generic statements, not on the lanes of their pairs
 //   HEYOKA_AMD_NO_REFILL              one-lane-per-pair kernel: whole groups of systems from the queue, no per-system refill
 //   HEYOKA_AMD_BLOCK_V2=0             block mode: generic cluster phase
-//   HEYOKA_AMD_BLOCK_OPTS             block mode, v2 cluster phase: items switched one by one (see hip_emit_block.cpp)
+//   HEYOKA_AMD_BLOCK_OPTS             block mode: items switched one by one, separated by ',' or ':' (the list: hip_emit_block_gen.hpp)
 //   HEYOKA_AMD_NO_STATE_ALIASES       planner: no alias u variables for state variables in history position
 //   HEYOKA_AMD_CLUSTER_V1             first-generation cluster generator
 //   HEYOKA_AMD_MULTI_CLASS=0          planner: no multi-class plans (clusters of several shapes / levels)
@@ -57,8 +57,8 @@ struct dev_switches {
     // (-1: automatic - 270 with the folded histories of the default arithmetic, 200 otherwise.)
     int reg_jets_max = -1;
     std::string v5_opts, v5_pad;
-    // HEYOKA_AMD_BLOCK_OPTS: comma-separated items of the v2 cluster phase of block mode switched one by one (A/B harness,
-    // timing experiments - see hip_emit_block.cpp).
+    // HEYOKA_AMD_BLOCK_OPTS: items of block mode switched one by one (A/B harness, timing experiments), separated by ',' or
+    // ':'; emit_block() parses the string once (block_switches, hip_emit_block_gen.hpp: the list of the switches).
     std::string block_opts;
     static dev_switches from_env();
 };
@@ -133,7 +133,7 @@ struct emitted_module {
     // of emit_options::cluster_kernel - 1 (first generation, multi-class), 2 (pipelined), 3 (lane pairs), 5 (one lane per
     // pair). The dispatch in emit_hip_module() reads this, never the prose of `notes`.
     int cluster_generation = 0;
-    // Block mode: the cluster phase is the rolled "v2 cluster phase" (see hip_emit_block.cpp).
+    // Block mode: the cluster phase is the rolled "v2 cluster phase" (the pair phase, see hip_emit_block_pair.cpp).
     bool block_v2_phase = false;
     // Cluster mode: doubles of jet scratch needed per resident wave.
     std::uint64_t scratch_per_wave = 0;

@@ -15,8 +15,9 @@ What each hash is good for:
 - code_object_sha256 (the whole file): changes with any edit of the text, a comment included (the symbol hash tables
   differ), so it says no more than hip_source_sha256 unless the text is identical - then it pins the compiler.
 
-The corpus: the families of tests/test_batch_independence.py (block_v2_nbody64 is left out: it alone compiles for minutes),
-the outer Solar System under every switch of the pipelined / lane-pair / one-lane-per-pair generator
+The corpus: the families of tests/test_batch_independence.py, the block-mode generator (hip_emit_block*.cpp) on nbody(12),
+nbody(64) and nbody(80) - one, four and seven rounds per lane - under every switch of HEYOKA_AMD_BLOCK_OPTS and on the
+systems which keep it on its generic cluster phase, the outer Solar System under every switch of the pipelined / lane-pair / one-lane-per-pair generator
 (hip_emit_cluster2*.cpp), its stepper with events under the switches of the event path, the systems which take the retries
 of emit_hip_module() (block mode with and without the v2 cluster phase, linearised accelerations, multi-class plans), the
 first wave-cluster generator with one class of clusters (cluster_kernel="v1"), and the straight-line, HBM-tape and staged
@@ -86,7 +87,8 @@ def corpus():
                      ("one_lane=0", {"HEYOKA_AMD_ONE_LANE": "0"}), ("one_lane=0,pair_split=0", {"HEYOKA_AMD_ONE_LANE": "0", "HEYOKA_AMD_PAIR_SPLIT": "0"})):
         out.append(("events:" + tag, outer_ev, env))
     # The dispatch of emit_hip_module().
-    out += [family("block_v2"), family("block_centres"), family("multi_class")]
+    out += [family("block_v2"), family("block_centres"), family("multi_class"), family("block_v2_nbody64")]
+    out += block_corpus()
     out.append(("equal_masses_linearised", lambda: hy.taylor_adaptive_batch(hy.model.nbody(6), None, N, high_accuracy=True), None))
     # The steppers with one copy of the step loop each (emit_detail::step_loop_source()).
     out += [family(n) for n in ("unrolled", "unrolled_two_waves", "unrolled_register_jets", "staged", "staged_functions", "table_hbm",
@@ -99,6 +101,32 @@ def corpus():
     out.append(("table_hbm:high_accuracy=False", lambda: outer(emitter="table", high_accuracy=False), hbm))
     for tag, kw, env in (("unrolled", {}, None), ("staged", {"emitter": "table"}, None), ("table_hbm", {"emitter": "table"}, hbm)):
         out.append(("angle_reduce:" + tag, lambda kw=kw: fused_angle_reduce(tan(**kw), [1]), env))
+    return out
+
+
+BLOCK_SWITCHES = ("nopad", "perm", "licm", "bs=64", "M=3", "reg_high", "reg_high=2", "div", "split", "xpf", "unpacked", "noglueperm",
+                  "nofuse", "dbuf", "G=1", "D=2", "D=1", "hand=2", "hoist", "keepdz", "hoist=0", "keepdz=0", "nopp", "nopp=0", "exp=1",
+                  "exp=2", "exp=3", "exp=4", "exp=5", "exp=34", "nopad,licm,bs=64")
+
+
+def block_corpus():
+    """The block-mode generator: 66 clusters on 128 lanes (one round), 2016 on 512 (two wavefronts per SIMD, four rounds), 3160
+    (seven rounds, the lean variant); the first two under every switch; what keeps nbody(12) off the v2 cluster phase."""
+    def nbody(n, **kw):
+        def make(**kw2):
+            kw2.setdefault("high_accuracy", True)
+            return hy.taylor_adaptive_batch(hy.model.nbody(n, **kw), None, N, **kw2)
+        return make
+
+    out = [("block:nbody%d" % n, nbody(n), None) for n in (12, 64, 80)]
+    for n in (12, 64):
+        out += [("block:nbody%d:%s" % (n, sw), nbody(n), {"HEYOKA_AMD_BLOCK_OPTS": sw}) for sw in BLOCK_SWITCHES]
+    out.append(("block:nbody12:v2=0", nbody(12), {"HEYOKA_AMD_BLOCK_V2": "0"}))
+    out.append(("block:nbody12:exact_division", lambda: nbody(12)(exact_division=True), None))
+    out.append(("block:nbody12:high_accuracy=False", lambda: nbody(12)(high_accuracy=False), None))
+    out.append(("block:nbody12:distinct_masses", nbody(12, masses=[1.0 + 0.125 * i for i in range(12)]), None))
+    out.append(("block:nbody12:runtime_masses", nbody(12, masses=[hy.par[i] for i in range(12)]), None))
+    out.append(("block:nbody8:emitter=block", lambda: nbody(8)(emitter="block"), None))
     return out
 
 
@@ -130,10 +158,12 @@ def device_code(elf):
     return b"".join(by_name.get(n, b"") for n in (".text", ".rodata", ".note"))
 
 
-def main(path):
+def main(path, only=""):
     sha = lambda b: hashlib.sha256(b).hexdigest()
     with open(path, "w") as f:
         for name, make, env in corpus():
+            if only not in name:
+                continue
             with tbi._env(env):
                 ta = make()
             mode = ta.hip_source_mode
@@ -149,6 +179,6 @@ def main(path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 2:
-        sys.exit("usage: stepper_source_corpus.py OUTPUT.jsonl")
-    main(sys.argv[1])
+    if len(sys.argv) not in (2, 3):
+        sys.exit("usage: stepper_source_corpus.py OUTPUT.jsonl [only the entries whose name contains this]")
+    main(*sys.argv[1:])
