@@ -65,6 +65,8 @@ __all__ = [
     "step_action_source",
     "grid_observables_source",
     "GRID_STATISTICS",
+    "ENSEMBLE_STATISTICS",
+    "ensemble_accumulators",
     "event_log",
     "callback",
     "diff",
@@ -1147,19 +1149,79 @@ def _grid_statistics(statistics, observables):
     return codes, (ctypes.c_int * max(len(codes), 1))(*codes)
 
 
-def _grid_sampling(observables, statistics, always_observables=False):
+ENSEMBLE_STATISTICS = ("count", "min", "max", "sum", "sum_sq", "mean")
+
+
+def _ensemble_statistics(ensemble_statistics, observables=(), statistics=None):
+    """The HY_ENS_STAT_* codes of a list of names as a C array: (codes, array), with the checks of _grid_statistics()."""
+    if observables is None:
+        raise ValueError("The ensemble statistics of propagate_grid() need a list of observables")
+    if statistics is not None:
+        raise ValueError("The ensemble statistics of propagate_grid() cannot be combined with statistics over the grid")
+    codes = []
+    for s in ensemble_statistics:
+        if s not in ENSEMBLE_STATISTICS:
+            raise ValueError("The ensemble statistic %r of propagate_grid() is unknown: one of %s"
+                             % (s, ", ".join(ENSEMBLE_STATISTICS)))
+        codes.append(ENSEMBLE_STATISTICS.index(s))
+    return codes, (ctypes.c_int * max(len(codes), 1))(*codes)
+
+
+class ensemble_accumulators:
+    """The accumulators of the ensemble statistics of propagate_grid() for ``n_grid`` points and ``n_obs``
+    observables: ``.raw``, their 64-bit words - integers which integer additions and min / max of keys update, so that nothing
+    depends on the order in which the values arrive -, ``.values``, the ndarray ``(n_grid, n_obs, n_stat)`` of the statistics in
+    the order of the list, rounded once from the words, ``.merge(other)``, which adds the accumulators of another part of the
+    ensemble (at most 2**30 values per grid point and observable over everything merged), and ``.add(g, o, y)``, the host
+    twin of what the kernel does with one value. A new object holds no value."""
+
+    def __init__(self, n_grid, n_obs, statistics):
+        self.statistics = tuple(statistics)
+        self._codes, self._sarr = _ensemble_statistics(self.statistics)
+        self.n_grid, self.n_obs = int(n_grid), int(n_obs)
+        n = lib.hy_grid_ens_acc_words(self.n_grid, self.n_obs, self._sarr, len(self._codes))
+        if n == 0 and self.n_grid * self.n_obs != 0:
+            raise_for(lib.hy_last_error_code() or 4)
+        self.raw = np.zeros(n, dtype=np.uint64)
+        raise_for(lib.hy_grid_ens_init(self.raw.ctypes.data, *self._shape_args()))
+
+    def _shape_args(self):
+        return self.n_grid, self.n_obs, self._sarr, len(self._codes)
+
+    def add(self, g, o, y):
+        raise_for(lib.hy_grid_ens_add(self.raw.ctypes.data, *self._shape_args(), int(g), int(o), float(y)))
+        return self
+
+    def merge(self, other):
+        if (other.n_grid, other.n_obs, other.statistics) != (self.n_grid, self.n_obs, self.statistics):
+            raise ValueError("Ensemble accumulators of different shapes or statistics cannot be merged")
+        raise_for(lib.hy_grid_ens_merge(self.raw.ctypes.data, other.raw.ctypes.data, *self._shape_args()))
+        return self
+
+    @property
+    def values(self):
+        out = np.empty((self.n_grid, self.n_obs, len(self._codes)))
+        raise_for(lib.hy_grid_ens_finish(self.raw.ctypes.data, *self._shape_args(), out.ctypes.data))
+        return out
+
+
+def _grid_sampling(observables, statistics, always_observables=False, ensemble_statistics=None):
     """What propagate_grid() and its relatives do with ``(observables, statistics)``. The call makes the Python-side checks of
     the statistics; the function it returns converts the observables when its turn has come: (suffix of the name of the C
-    entry point - "", "_obs" or "_stats" -, the arguments of that entry point for the lists, the observables, the codes of the
-    statistics). ``always_observables``: there is no entry point without observables."""
+    entry point - "", "_obs", "_stats" or "_ens" -, the arguments of that entry point for the lists, the observables, the codes
+    of the statistics). ``always_observables``: there is no entry point without observables."""
     codes = sarr = None
-    if statistics is not None:
+    if ensemble_statistics is not None:
+        codes, sarr = _ensemble_statistics(ensemble_statistics, observables, statistics)
+    elif statistics is not None:
         codes, sarr = _grid_statistics(statistics, observables)
 
     def lists():
         if observables is None and not always_observables:
             return "", (), None, None
         obs, oarr = _handle_array(list(observables))
+        if ensemble_statistics is not None:
+            return "_ens", (oarr, len(obs), sarr, len(codes)), obs, codes
         if statistics is None:
             return "_obs", (oarr, len(obs)), obs, None
         return "_stats", (oarr, len(obs), sarr, len(codes)), obs, codes
@@ -1167,13 +1229,15 @@ def _grid_sampling(observables, statistics, always_observables=False):
     return lists
 
 
-def grid_observables_source(sys, observables, order=20, high_accuracy=False, statistics=None):
+def grid_observables_source(sys, observables, order=20, high_accuracy=False, statistics=None, ensemble_statistics=None):
     """HIP source of the post-step module of propagate_grid() with the section of ``observables`` for the system ``sys`` at
     the Taylor order ``order``: no integrator, no GPU. ``HEYOKA_AMD_GRID_OBS=registers|staged`` overrides how the kernel
     holds the samples of a grid point (default: registers up to 64 state rows read, the staging buffer beyond).
-    ``statistics``: the module which folds the observables into these statistics (see propagate_grid())."""
+    ``statistics``: the module which folds the observables into these statistics (see propagate_grid());
+    ``ensemble_statistics``: the module which merges them across the systems (``HEYOKA_AMD_GRID_ENS=peratomic``: without the
+    aggregation per wavefront)."""
     s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
-    sfx, largs, obs, _ = _grid_sampling(observables, statistics, True)()
+    sfx, largs, obs, _ = _grid_sampling(observables, statistics, True, ensemble_statistics)()
     return take_str(check_handle(getattr(lib, "hy_grid%s_source" % sfx)(s._h, *largs, int(order), int(bool(high_accuracy)))))
 
 
@@ -1923,7 +1987,8 @@ class taylor_adaptive_batch:
     def propagate_for(self, delta_t, max_steps=0, max_delta_t=None, callback=None, write_tc=False, c_output=False):
         return self._propagate(lib.hy_tab_propagate_for, delta_t, max_steps, max_delta_t, callback, write_tc, c_output)
 
-    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None, observables=None, statistics=None):
+    def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None, observables=None, statistics=None,
+                       ensemble_statistics=None):
         """propagate_grid(): ``(callback, out)`` with ``out[point, var, lane]``, NaN where not reached. ``observables`` (an
         MI355X extension): a list of expressions over the state variables, ``par[...]`` and ``hy.time`` -
         ``out[point, observable, lane]`` then holds, bit for bit, ``cfunc(observables, vars=state variables)`` of the state
@@ -1936,15 +2001,26 @@ class taylor_adaptive_batch:
         statistic, lane]`` is returned; nothing of the size of the grid is allocated for the output. ``min`` / ``max`` ignore
         NaN values unless all are NaN, ``t_min`` / ``t_max`` are the first grid times at which they were attained, ``sum`` is
         one rounded addition per point, ``count`` the number of points reached. The integrator is left as by the call with
-        ``observables`` alone."""
-        lists = _grid_sampling(observables, statistics)
+        ``observables`` alone.
+
+        ``ensemble_statistics`` (only with ``observables``, not with ``statistics``): a list of names out of ``count, min,
+        max, sum, sum_sq, mean`` - the observables are folded ACROSS the systems per grid point, over the values which are
+        not NaN, and ``(callback, acc)`` is returned with ``acc`` an ``ensemble_accumulators``: ``acc.values[point, observable,
+        statistic]``. ``sum`` and ``sum_sq`` are the exact sums rounded once, ``min`` / ``max`` order ``-0.0 < +0.0``: the same
+        bits for any order of the systems, any loop and any sharding of the ensemble (``acc.merge(other)``). With per-lane
+        grids a point is a row of the grid. The integrator is left as by the call with ``observables`` alone."""
+        lists = _grid_sampling(observables, statistics, False, ensemble_statistics)
         g = _f64(grid)
         if g.ndim == 1:
             g = np.repeat(g[:, None], self.batch_size, axis=1)
         g = np.ascontiguousarray(g)
         n_grid = g.shape[0]
         sfx, largs, obs, codes = lists()
-        if codes is not None:
+        acc = None
+        if sfx == "_ens":
+            acc = ensemble_accumulators(n_grid, len(obs), ensemble_statistics)
+            out = acc.raw
+        elif codes is not None:
             out = np.empty((len(obs), len(codes), self.batch_size))
         else:
             out = np.empty((n_grid, self.dim if obs is None else len(obs), self.batch_size))
@@ -1962,16 +2038,18 @@ class taylor_adaptive_batch:
             raise err[0]
         self._raise_cb_errors()
         raise_for(rc)
-        return callback, out
+        return callback, (out if acc is None else acc)
 
-    def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None, observables=None, statistics=None):
+    def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None, observables=None, statistics=None,
+                              ensemble_statistics=None):
         """propagate_grid() with the samples written to a caller-owned device buffer (``out_ptr``: device address of
         n_grid * dim * batch_size doubles, layout [point, var, lane]); ``grid``: 1-D (shared by all the lanes) or
         (n_grid, batch_size). Nothing of that size is materialised on the host. With ``observables`` (see
         propagate_grid()) the buffer holds n_grid * len(observables) * batch_size doubles, layout [point, observable, lane];
         with ``statistics`` as well, len(observables) * len(statistics) * batch_size doubles, layout [observable, statistic,
-        lane]."""
-        lists = _grid_sampling(observables, statistics)
+        lane]; with ``ensemble_statistics`` instead, the 64-bit words of the accumulators, as many as
+        ``ensemble_accumulators(n_grid, len(observables), ensemble_statistics).raw`` has."""
+        lists = _grid_sampling(observables, statistics, False, ensemble_statistics)
         g = np.ascontiguousarray(_f64(grid))
         scalar = g.ndim == 1
         if max_delta_t is None:
@@ -1984,11 +2062,12 @@ class taylor_adaptive_batch:
                                                                        int(max_steps), mptr, mn, *largs,
                                                                        ctypes.c_void_p(int(out_ptr))))
 
-    def grid_observables_module(self, observables, statistics=None):
+    def grid_observables_module(self, observables, statistics=None, ensemble_statistics=None):
         """(HIP source, gfx950 code object) of the post-step module of propagate_grid() with the section of ``observables``
         (kernels hy_grid_post, hy_grid_obs0, hy_grid_unsample) in this integrator: checked against its system and compiled
-        on first use. No GPU is needed. ``statistics``: the module which folds them (see propagate_grid())."""
-        sfx, largs, obs, _ = _grid_sampling(observables, statistics, True)()
+        on first use. No GPU is needed. ``statistics``: the module which folds them (see propagate_grid());
+        ``ensemble_statistics``: the module which merges them across the systems."""
+        sfx, largs, obs, _ = _grid_sampling(observables, statistics, True, ensemble_statistics)()
         src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
         raise_for(getattr(lib, "hy_tab_grid%s_module" % sfx)(self._h, *largs, ctypes.byref(src), ctypes.byref(data),
                                                              ctypes.byref(n)))

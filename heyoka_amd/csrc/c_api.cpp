@@ -294,7 +294,8 @@ void check_tab(const char *fn, hy_tab t)
 }
 
 // ---- what propagate_grid() samples (grid_observables.hpp) ----
-// The lists a function fn of the C interface was given: none, observables (lists == 1), observables and statistics (2).
+// The lists a function fn of the C interface was given: none, observables (lists == 1), observables and statistics (2),
+// observables and ensemble statistics (3: stats holds HY_ENS_STAT_* codes).
 struct c_sampling {
     int lists = 0;
     const hy_expr *obs = nullptr;
@@ -324,6 +325,9 @@ detail::grid_sampling sampling_from(const char *fn, const c_sampling &c)
     if (c.stats == nullptr && c.n_stats != 0u) {
         throw std::invalid_argument(std::string(fn) + "(): the array of statistics is null");
     }
+    if (c.lists == 3) {
+        return detail::grid_sampling(std::move(ov), {}, detail::ensemble_statistics_from_codes(c.stats, c.n_stats));
+    }
     return detail::grid_sampling(std::move(ov), detail::grid_statistics_from_codes(c.stats, c.n_stats));
 }
 
@@ -338,11 +342,19 @@ int propagate_grid_host(const char *fn, hy_tab t, const double *grid, size_t n_g
         auto gs = sampling_from(fn, c);
         t->core.prepare_grid_sampling(gs);
         const auto bs = t->core.get_batch_size();
+        // (Ensemble statistics: out receives the words of the accumulators, not their values.)
+        std::vector<std::uint64_t> raw;
+        const bool ens = gs.ensemble.has_value();
         const auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), {.max_steps = static_cast<std::size_t>(max_steps),
                                                                              .max_delta_ts = expand_mdt(mdts, n_mdt, bs),
                                                                              .hooks = hooks_of(),
-                                                                             .sampling = std::move(gs)});
-        std::memcpy(out, ret.data(), ret.size() * sizeof(double));
+                                                                             .sampling = std::move(gs),
+                                                                             .ens_raw = ens ? &raw : nullptr});
+        if (ens) {
+            std::memcpy(out, raw.data(), raw.size() * sizeof(std::uint64_t));
+        } else {
+            std::memcpy(out, ret.data(), ret.size() * sizeof(double));
+        }
     });
 }
 
@@ -388,6 +400,16 @@ char *grid_source(const char *fn, hy_sys sys, const c_sampling &c, uint32_t orde
         const auto sec = detail::make_grid_obs_section(gs, svars, std::numeric_limits<std::uint32_t>::max());
         return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
     });
+}
+
+// hy_grid_ens_*(): the layout of the records of a list of HY_ENS_STAT_* codes.
+detail::ens_layout ens_layout_from(const char *fn, const int *stats, size_t n_stats, std::vector<ensemble_statistic> &list)
+{
+    if (stats == nullptr && n_stats != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of statistics is null");
+    }
+    list = detail::ensemble_statistics_from_codes(stats, n_stats);
+    return detail::ens_layout_of(list);
 }
 
 int grid_module(const char *fn, hy_tab t, const c_sampling &c, char **source, const char **data, size_t *size)
@@ -2109,6 +2131,78 @@ int hy_tab_grid_stats_module(hy_tab t, const hy_expr *obs, size_t n_obs, const i
                              const char **data, size_t *size)
 {
     return grid_module("hy_tab_grid_stats_module", t, {2, obs, n_obs, stats, n_stats}, source, data, size);
+}
+// ---- ensemble statistics (grid_ensemble.hpp) ----
+int hy_tab_propagate_grid_ens(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts, size_t n_mdt,
+                              const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs, const int *stats,
+                              size_t n_stats, uint64_t *acc)
+{
+    return propagate_grid_host("hy_tab_propagate_grid_ens", t, grid, n_grid, max_steps, mdts, n_mdt,
+                               [&] { return wrap_cbs(t, cbs, n_cbs); }, {3, obs, n_obs, stats, n_stats},
+                               reinterpret_cast<double *>(acc));
+}
+int hy_tab_propagate_grid_ens_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                     const double *mdts, size_t n_mdt, const hy_expr *obs, size_t n_obs, const int *stats,
+                                     size_t n_stats, uint64_t *d_acc)
+{
+    return propagate_grid_dev("hy_tab_propagate_grid_ens_device", t, grid, n_grid, scalar_grid, max_steps, mdts, n_mdt,
+                              {3, obs, n_obs, stats, n_stats}, reinterpret_cast<double *>(d_acc));
+}
+char *hy_grid_ens_source(hy_sys sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, uint32_t order,
+                         int high_accuracy)
+{
+    return grid_source("hy_grid_ens_source", sys, {3, obs, n_obs, stats, n_stats}, order, high_accuracy);
+}
+int hy_tab_grid_ens_module(hy_tab t, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
+                           const char **data, size_t *size)
+{
+    return grid_module("hy_tab_grid_ens_module", t, {3, obs, n_obs, stats, n_stats}, source, data, size);
+}
+size_t hy_grid_ens_acc_words(size_t n_grid, size_t n_obs, const int *stats, size_t n_stats)
+{
+    size_t ret = 0;
+    guarded([&] {
+        std::vector<ensemble_statistic> list;
+        ret = n_grid * n_obs * ens_layout_from("hy_grid_ens_acc_words", stats, n_stats, list).words;
+    });
+    return ret;
+}
+int hy_grid_ens_init(uint64_t *acc, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats)
+{
+    return guarded([&] {
+        std::vector<ensemble_statistic> list;
+        const auto v = detail::ens_init(ens_layout_from("hy_grid_ens_init", stats, n_stats, list), n_grid * n_obs);
+        std::memcpy(acc, v.data(), v.size() * sizeof(std::uint64_t));
+    });
+}
+int hy_grid_ens_add(uint64_t *acc, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats, size_t g, size_t o, double y)
+{
+    return guarded([&] {
+        std::vector<ensemble_statistic> list;
+        const auto l = ens_layout_from("hy_grid_ens_add", stats, n_stats, list);
+        if (g >= n_grid || o >= n_obs) {
+            throw std::invalid_argument("hy_grid_ens_add(): the record (" + std::to_string(g) + ", " + std::to_string(o)
+                                        + ") is outside the accumulators");
+        }
+        static_assert(sizeof(uint64_t) == sizeof(std::uint64_t));
+        detail::ens_add(l, reinterpret_cast<std::uint64_t *>(acc) + (g * n_obs + o) * l.words, y);
+    });
+}
+int hy_grid_ens_merge(uint64_t *dst, const uint64_t *src, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats)
+{
+    return guarded([&] {
+        std::vector<ensemble_statistic> list;
+        const auto l = ens_layout_from("hy_grid_ens_merge", stats, n_stats, list);
+        detail::ens_merge(l, dst, src, n_grid * n_obs);
+    });
+}
+int hy_grid_ens_finish(const uint64_t *acc, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats, double *out)
+{
+    return guarded([&] {
+        std::vector<ensemble_statistic> list;
+        const auto l = ens_layout_from("hy_grid_ens_finish", stats, n_stats, list);
+        detail::ens_finish(l, list, acc, n_grid * n_obs, out);
+    });
 }
 int hy_tab_get_propagate_res(hy_tab t, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps)
 {

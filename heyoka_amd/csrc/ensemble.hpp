@@ -244,10 +244,29 @@ auto ensemble_propagate_tmpl(const taylor_adaptive_batch<double> &ta, const Time
         if (n_iter != 0u) {
             tas[0].core().prepare_grid_sampling(gs);
         }
+        // (kw::ensemble_statistics: every iteration returns the n_grid * n_obs * n_stat values of its own systems; the words
+        // of its accumulators are merged - integer additions, min / max of keys: the order does not matter - into
+        // kw::ensemble_result, if given.)
+        std::vector<std::vector<std::uint64_t>> ens_raw(gs.ensemble ? n_iter : 0u);
         ensemble_run_per_device(n_iter, n_dev, [&](std::size_t i) {
             res[i] = tas[i].propagate_grid(grid, kw::max_steps = max_steps, kw::max_delta_t = max_delta_ts, kw::callback = cb,
-                                           kw::observables = gs.observables, kw::statistics = gs.statistics);
+                                           kw::observables = gs.observables, kw::statistics = gs.statistics,
+                                           kw::ensemble_statistics = gs.ensemble,
+                                           kw::ensemble_raw = gs.ensemble ? &ens_raw[i] : nullptr);
         });
+        if constexpr (kw::has_v<kw::ensemble_result_tag, KwArgs...>) {
+            std::vector<double> &merged = *kw::get(kw::ensemble_result, 0, kw_args...);
+            merged.clear();
+            if (gs.ensemble && n_iter != 0u) {
+                const auto lay = detail::ens_layout_of(*gs.ensemble);
+                const auto n_rec = ens_raw[0].size() / lay.words;
+                for (std::size_t i = 1; i < n_iter; ++i) {
+                    detail::ens_merge(lay, ens_raw[0].data(), ens_raw[i].data(), n_rec);
+                }
+                merged.resize(n_rec * gs.ensemble->size());
+                detail::ens_finish(lay, *gs.ensemble, ens_raw[0].data(), n_rec, merged.data());
+            }
+        }
         if constexpr (kw::has_v<kw::gather_tag, KwArgs...>) {
             *kw::get(kw::gather, 0, kw_args...) = ensemble_gather_states(tas, 0);
         }

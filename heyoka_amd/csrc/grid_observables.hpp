@@ -28,6 +28,7 @@
 
 #include "expr_section.hpp"
 #include "expression.hpp"
+#include "grid_ensemble.hpp"
 #include "kw.hpp"
 
 namespace heyoka_amd::detail
@@ -36,12 +37,16 @@ namespace heyoka_amd::detail
 // What propagate_grid() samples: nothing but the state (both absent), a list of observables, or the statistics of a list of
 // observables. The construction is the one place which rejects statistics without observables
 // (grid_statistics_need_observables) and checks the list of statistics (check_grid_statistics()).
+// ... or the statistics of a list of observables across the ensemble per grid point (grid_ensemble.hpp): rejected
+// here without observables, together with statistics over the grid, and when check_ensemble_statistics() says so.
 struct grid_sampling {
     std::optional<std::vector<expression>> observables;
     std::optional<std::vector<grid_statistic>> statistics;
+    std::optional<std::vector<ensemble_statistic>> ensemble;
 
     grid_sampling() = default;
-    explicit grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats = {});
+    explicit grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats = {},
+                           std::optional<std::vector<ensemble_statistic>> ens = {});
 };
 
 // Observables checked against a system: their section (expr_section.hpp: `reads` are the rows the kernel samples) and how
@@ -53,6 +58,11 @@ struct grid_obs_section : expr_section {
     // Grid statistics, empty: none. n_slots: accumulators per lane, the n_obs * stats.size() of the output first.
     std::vector<grid_statistic> stats;
     std::uint32_t n_slots = 0;
+    // Ensemble statistics, empty: none. The records of ens_layout, and whether the lanes of a wavefront are aggregated ahead
+    // of the atomics (HEYOKA_AMD_GRID_ENS=peratomic: they are not).
+    std::vector<ensemble_statistic> ens;
+    ens_layout ens_rec;
+    bool ens_aggregate = true;
 };
 
 // The largest number of rows held in registers: see DESIGN 4.3e for the budget.
@@ -69,10 +79,13 @@ grid_obs_section make_grid_obs_section(const grid_sampling &gs, const std::vecto
 // With statistics in the section: hy_grid_post folds the HY_NOUT values of a grid point into the HY_NSLOT accumulators of
 // the lane instead of storing them, hy_grid_obs0 starts the accumulators, hy_grid_unsample puts them back from their shadow
 // copy. Without statistics the text is, byte for byte, the one of a section without the field.
+// With ensemble statistics in the section: hy_grid_post and hy_grid_obs0 merge the HY_NOUT values of a grid point into the
+// records (g * HY_NOUT + o) of HY_ENS_WORDS 64-bit words behind `out`, which do not depend on the number of lanes; there is no
+// hy_grid_unsample - the host keeps a copy of the records where samples may be taken back.
 std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool high_accuracy, const grid_obs_section *sec);
 
 // The key of the module of gs (with observables) inside an integrator: the text of the observables, the way of holding the
-// samples and the statistics.
+// samples and the statistics (over the grid, or across the ensemble with the way of merging, HEYOKA_AMD_GRID_ENS).
 std::string grid_obs_key(const grid_sampling &gs);
 
 // ---- grid statistics ----

@@ -9,9 +9,19 @@
 namespace heyoka_amd::detail
 {
 
-grid_sampling::grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats)
-    : observables(std::move(obs)), statistics(std::move(stats))
+grid_sampling::grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats,
+                             std::optional<std::vector<ensemble_statistic>> ens)
+    : observables(std::move(obs)), statistics(std::move(stats)), ensemble(std::move(ens))
 {
+    if (ensemble) {
+        if (!observables) {
+            throw std::invalid_argument(ensemble_statistics_need_observables);
+        }
+        if (statistics) {
+            throw std::invalid_argument(ensemble_statistics_exclude_statistics);
+        }
+        check_ensemble_statistics(*ensemble);
+    }
     if (statistics) {
         if (!observables) {
             throw std::invalid_argument(grid_statistics_need_observables);
@@ -33,6 +43,14 @@ std::string grid_obs_key(const grid_sampling &gs)
         for (const auto s : *gs.statistics) {
             key += std::to_string(static_cast<int>(s)) + ",";
         }
+    }
+    if (gs.ensemble) {
+        key += "|ensemble:";
+        for (const auto s : *gs.ensemble) {
+            key += std::to_string(static_cast<int>(s)) + ",";
+        }
+        const char *ens_env = std::getenv("HEYOKA_AMD_GRID_ENS");
+        key += std::string("|") + (ens_env != nullptr ? ens_env : "");
     }
     return key;
 }
@@ -130,6 +148,18 @@ grid_obs_section make_grid_obs_section(const grid_sampling &gs, const std::vecto
         ret.stats = *gs.statistics;
         (void)grid_stat_slots(ret.n_obs, ret.stats, ret.n_slots);
     }
+    if (gs.ensemble) {
+        ret.ens = *gs.ensemble;
+        ret.ens_rec = ens_layout_of(ret.ens);
+        if (const char *env = std::getenv("HEYOKA_AMD_GRID_ENS")) {
+            const std::string mode(env);
+            if (mode == "peratomic") {
+                ret.ens_aggregate = false;
+            } else if (!mode.empty() && mode != "aggregate") {
+                throw std::invalid_argument("Invalid value '" + mode + "' of HEYOKA_AMD_GRID_ENS: 'aggregate' or 'peratomic'");
+            }
+        }
+    }
     return ret;
 }
 
@@ -184,13 +214,22 @@ std::string grid_obs_device_functions(const grid_obs_section &sec)
         },
         &lit_names);
     std::ostringstream src;
-    src << "\n// The state rows the observables read.\n#define HY_NROWS " << sec.reads.size() << "u\n__device__ const unsigned hy_obs_rows[HY_NROWS] = {";
+    src << "\n// The state rows the observables read.\n#define HY_NROWS " << sec.reads.size() << "u\n__device__ const unsigned hy_obs_rows["
+        << (sec.reads.empty() ? "1" : "HY_NROWS") << "] = {";
     for (std::size_t j = 0; j < sec.reads.size(); ++j) {
         src << (j != 0u ? ", " : "") << sec.reads[j] << "u";
     }
-    src << "};\n";
+    // (Observables of the parameters and the time alone read no row: no array of length zero.)
+    src << (sec.reads.empty() ? "0u" : "") << "};\n";
     const bool folds = !sec.stats.empty();
-    if (folds) {
+    const bool ens = !sec.ens.empty();
+    if (ens) {
+        src << ens_device_text(sec.ens_rec, sec.ens_aggregate) << R"HIP(
+// The observables of lane i at grid point g and time t_hi, merged into the records (g * HY_NOUT + o) behind outp, the start of
+// the output (stg points to the staged samples of the lane).
+__device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 i, const u64 N, double *outp, const unsigned g, const double t_hi
+)HIP";
+    } else if (folds) {
         src << R"HIP(
 // Grid statistics: the accumulators of a lane are the slots out[s * N + i], s < HY_NSLOT - those of the output first -, and
 // out[(HY_NSLOT + s) * N + i] is their shadow copy.
@@ -225,6 +264,17 @@ __device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 
         src << d;
     }
     src << code.body;
+    if (ens) {
+        // The merge, behind the last value of the section, as with the grid statistics: the values are opaque to the backend.
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            src << "double y" << o << " = " << code.outs[o] << ";\nasm volatile(\"\" : \"+v\"(y" << o << "));\n";
+        }
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            src << "hy_ens_merge((u64 *)outp + ((u64)g * HY_NOUT + " << o << "u) * HY_ENS_WORDS, y" << o << ");\n";
+        }
+        src << "}\n";
+        return src.str();
+    }
     if (!folds) {
         for (std::size_t o = 0; o < code.outs.size(); ++o) {
             src << "outp[((u64)g * HY_NOUT + " << o << "u) * N] = " << code.outs[o] << ";\n";
@@ -550,7 +600,9 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         // would hold a pair of SGPRs each across the whole loop, next to the literals of the section, which are moved ahead
         // of the loop as well - the wave has 102 SGPRs, and 512 VGPRs per lane at 256 lanes per workgroup.
         src << "    const double *tc0 = a.tc + i;\n    asm volatile(\"\" : \"+v\"(tc0));\n";
-        src << "    double *out0 = a.out + i;\n    asm volatile(\"\" : \"+v\"(out0));\n";
+        if (sec->ens.empty()) {
+            src << "    double *out0 = a.out + i;\n    asm volatile(\"\" : \"+v\"(out0));\n";
+        }
         if (sec->staged) {
             src << "    double *stg = a.stage + i;\n    asm volatile(\"\" : \"+v\"(stg));\n";
         }
@@ -597,7 +649,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         src << "        const double *tcb = tc0;\n        asm volatile(\"\" : \"+v\"(tcb));\n";
         src << "        u64 Ns = N;\n        asm volatile(\"\" : \"+s\"(Ns));\n";
         if (!sec->staged) {
-            src << "        double xs[HY_NROWS];\n#pragma unroll\n";
+            src << "        double xs[" << (sec->reads.empty() ? "1" : "HY_NROWS") << "];\n#pragma unroll\n";
         }
         src << R"HIP(        for (unsigned j = 0; j < HY_NROWS; ++j) {
             const unsigned v = hy_obs_rows[j];
@@ -610,7 +662,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         } else {
             src << "            xs[j] = res;\n            __builtin_amdgcn_sched_barrier(0);\n        }\n";
         }
-        src << "        " << grid_obs_call(*sec, "out0", "stg", "xs", "g", "tg.hi");
+        src << "        " << grid_obs_call(*sec, sec->ens.empty() ? "out0" : "a.out", "stg", "xs", "g", "tg.hi");
     }
     src << R"HIP(        ++g;
     }
@@ -646,6 +698,12 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
     }
 }
 )HIP";
+    } else if (sec != nullptr && !sec->ens.empty()) {
+        // (Ensemble statistics: the records are restored by the host from its copy, there is no hy_grid_unsample.)
+        src << R"HIP(
+// Row 0 into the records: the observables of the current state at the first grid time (at the start of the call and again
+// after a rollback, into records in their start state).
+)HIP";
     } else {
         src << R"HIP(
 // A sweep in which a lane went non-finite: the reference leaves its loop right after that step, before the dense output of
@@ -666,7 +724,8 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
 )HIP";
     }
     if (sec != nullptr) {
-        if (!sec->stats.empty()) {
+        if (!sec->ens.empty()) {
+        } else if (!sec->stats.empty()) {
             src << "\n// The start of the accumulators: the observables of the current state at the first grid time (at the start of "
                    "the call and\n// again after a rollback).\n";
         } else {
@@ -684,7 +743,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
         if (sec->staged) {
             src << "    double *stg = a.stage + i;\n";
         } else {
-            src << "    double xs[HY_NROWS];\n";
+            src << "    double xs[" << (sec->reads.empty() ? "1" : "HY_NROWS") << "];\n";
         }
         std::size_t n_obs0 = 0;
         for (const auto r : sec->reads) {
@@ -694,7 +753,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
                 src << "    xs[" << n_obs0++ << "] = a.state[(u64)" << r << "u * N + i];\n";
             }
         }
-        src << "    " << grid_obs_call(*sec, "a.out + i", "stg", "xs", "0u", "a.grid[i]") << "}\n";
+        src << "    " << grid_obs_call(*sec, sec->ens.empty() ? "a.out + i" : "a.out", "stg", "xs", "0u", "a.grid[i]") << "}\n";
     }
     return src.str();
 }

@@ -17,6 +17,9 @@ namespace heyoka_amd
 // The statistics of the grid observables (kw::statistics, grid_observables.hpp). The values are the HY_GRID_STAT_* codes of the
 // C interface.
 enum class grid_statistic : int { min = 0, max = 1, t_min = 2, t_max = 3, sum = 4, last = 5, count = 6 };
+// The statistics across the ensemble per grid point (kw::ensemble_statistics, grid_ensemble.hpp). The values are the
+// HY_ENS_STAT_* codes of the C interface.
+enum class ensemble_statistic : int { count = 0, min = 1, max = 2, sum = 3, sum_sq = 4, mean = 5 };
 
 namespace kw
 {
@@ -75,6 +78,15 @@ HEYOKA_AMD_KWARG(observables);
 // ... and kw::statistics = std::vector<grid_statistic>{...}, only together with kw::observables: the observables are folded over
 // the grid points a system reaches, and the output is out[(observable * n_stat + statistic) * N + lane] (grid_observables.hpp).
 HEYOKA_AMD_KWARG(statistics);
+// ... or kw::ensemble_statistics = std::vector<ensemble_statistic>{...}, only together with kw::observables and not with
+// kw::statistics: the observables are folded ACROSS the systems per grid point, exactly (grid_ensemble.hpp), and the output is
+// out[(point * n_obs + observable) * n_stat + statistic]. ensemble_propagate_grid_batch(): kw::ensemble_result = &vec
+// (std::vector<double> *) receives the values of the accumulators merged over all the iterations. propagate_grid():
+// kw::ensemble_raw = &words (std::vector<std::uint64_t> *) receives the words of the accumulators, for those who merge by hand
+// (detail::ens_merge() / ens_finish(), grid_ensemble.hpp).
+HEYOKA_AMD_KWARG(ensemble_statistics);
+HEYOKA_AMD_KWARG(ensemble_result);
+HEYOKA_AMD_KWARG(ensemble_raw);
 // Events (reference: include/heyoka/events.hpp:87-100).
 HEYOKA_AMD_KWARG(direction);
 HEYOKA_AMD_KWARG(cooldown);

@@ -413,13 +413,20 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     auto *const gov = call.sampling.observables ? &d.get_go_module(call.sampling) : nullptr;
     const bool folds = stats.has_value();
     const std::size_t n_res = folds ? gov->sec.n_obs * stats->size() * N : 0u;
+    // Ensemble statistics: the variant which merges into the records of the grid points, n_grid * n_obs records
+    // of ens_rec.words 64-bit words whatever the number of systems, with a copy of the same size behind them: the records
+    // as they were before the samples of a sweep which may be taken back.
+    const bool ens = call.sampling.ensemble.has_value();
+    const std::size_t ens_words = ens ? static_cast<std::size_t>(n_grid) * gov->sec.n_obs * gov->sec.ens_rec.words : 0u;
+    const auto ens_start = ens ? ens_init(gov->sec.ens_rec, static_cast<std::size_t>(n_grid) * gov->sec.n_obs) : std::vector<std::uint64_t>{};
     aux_module &sample_mod = gov != nullptr ? gov->loaded(d.device) : *d.grid_mod;
     const std::size_t n_col = gov != nullptr ? gov->sec.n_obs : dim;
     device_buffer b_stage((gov != nullptr && gov->sec.staged) ? static_cast<std::size_t>(dim) * N * dsz : 0u, d.device);
 
-    const auto out_doubles = folds ? 2u * gov->sec.n_slots * static_cast<std::size_t>(N) : grid.size() * n_col;
-    device_buffer b_grid(grid.size() * dsz, d.device), b_out((d_out != nullptr && !folds) ? 0u : out_doubles * dsz, d.device);
-    double *const out_ptr = (d_out != nullptr && !folds) ? d_out : b_out.as<double>();
+    const auto out_doubles = ens ? 2u * ens_words : (folds ? 2u * gov->sec.n_slots * static_cast<std::size_t>(N) : grid.size() * n_col);
+    const bool own_out = folds || ens;
+    device_buffer b_grid(grid.size() * dsz, d.device), b_out((d_out != nullptr && !own_out) ? 0u : out_doubles * dsz, d.device);
+    double *const out_ptr = (d_out != nullptr && !own_out) ? d_out : b_out.as<double>();
     device_buffer b_rem_hi(N * dsz, d.device), b_rem_lo(N * dsz, d.device), b_mdt(N * dsz, d.device);
     device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(6u * sizeof(unsigned), d.device),
         b_gidx_prev(N * sizeof(unsigned), d.device);
@@ -439,7 +446,13 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     // The samples and the per-lane bookkeeping at the first grid point: at the start, and again after a rollback (below).
     const auto init_grid_state = [&]() {
         // Row 0 = current state, everything else NaN until reached. (Statistics: hy_grid_obs0 below writes every accumulator.)
-        if (folds) {
+        if (ens) {
+            // (The records in their start state; hy_grid_obs0 below merges row 0.)
+            b_out.upload(ens_start.data(), ens_words * dsz, d.stream);
+            if (d_out != nullptr) {
+                d.to_device();
+            }
+        } else if (folds) {
             if (d_out != nullptr) {
                 d.to_device();
             }
@@ -570,6 +583,10 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
             a.stage = b_stage.as<double>();
         }
         sw.fill(a);
+        if (ens && !multi_step) {
+            // (A single-step sweep may take its samples back: all of them, so all the records as they are now.)
+            device_copy(b_out.as<double>() + ens_words, b_out.get(), ens_words * dsz, d.device, d.stream);
+        }
         sample_mod.launch("hy_grid_post", N, 256, a, d.stream);
         unsigned cnt[6] = {0, 0, 0, 0, 0, 0};
         sw.read_counters(b_cnt, cnt, 4u);
@@ -587,7 +604,11 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
             // (Lock-step sweeps: no samples of this step, src/taylor_adaptive_batch.cpp:1962-1968. The multi-step launches of
             // batch_semantics == 2 keep theirs: every lane on its own.)
             if (!multi_step) {
-                sample_mod.launch("hy_grid_unsample", N, 256, a, d.stream);
+                if (ens) {
+                    device_copy(b_out.get(), b_out.as<double>() + ens_words, ens_words * dsz, d.device, d.stream);
+                } else {
+                    sample_mod.launch("hy_grid_unsample", N, 256, a, d.stream);
+                }
             }
             // A non-finite state was detected: stop (the outcomes of the last step are reported). With coefficients on
             // demand the lanes which did not reach a grid point in this sweep hold the coefficients of OLDER steps:
@@ -638,7 +659,11 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                                   : std::string{})
                 + (folds ? ", statistics " + stat_names(*stats) + " folded over the grid (" + std::to_string(gov->sec.n_slots)
                                + " accumulators per system)"
-                         : std::string{}));
+                         : std::string{})
+                + (ens ? ", ensemble statistics merged across the systems per grid point (" + std::to_string(gov->sec.ens_rec.words)
+                             + " words per grid point and observable, "
+                             + (gov->sec.ens_aggregate ? "aggregated per wavefront" : "one atomic per lane") + ")"
+                       : std::string{}));
     }
     if (multi_step && any_step) {
         // (The accumulated counters / extrema take the place of the last launch's own.)
@@ -651,7 +676,20 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         d.prop_res_dev_newer = true;
         d.step_res_dev_newer = true;
     }
-    if (folds && d_out != nullptr) {
+    if (ens) {
+        // The records to the caller: the words to the device buffer or to grid_call::ens_raw, their values to retval.
+        std::vector<std::uint64_t> raw(ens_words);
+        b_out.download(raw.data(), ens_words * dsz, d.stream);
+        if (d_out != nullptr) {
+            device_copy(d_out, b_out.get(), ens_words * dsz, d.device, d.stream);
+            stream_synchronize(d.device, d.stream);
+        } else {
+            ens_finish(gov->sec.ens_rec, gov->sec.ens, raw.data(), static_cast<std::size_t>(n_grid) * gov->sec.n_obs, retval.data());
+        }
+        if (call.ens_raw != nullptr) {
+            *call.ens_raw = std::move(raw);
+        }
+    } else if (folds && d_out != nullptr) {
         device_copy(d_out, b_out.get(), n_res * dsz, d.device, d.stream);
         stream_synchronize(d.device, d.stream);
     } else if (d_out == nullptr) {
@@ -752,8 +790,27 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, const gri
     if (d_out != nullptr && cb) {
         throw std::invalid_argument("propagate_grid() with a device output buffer does not support callbacks");
     }
-    std::vector<double> retval(d_out != nullptr ? 0u : (stats ? n_col * stats->size() * N : grid.size() * n_col),
+    const auto &ens = call.sampling.ensemble;
+    std::vector<double> retval(d_out != nullptr
+                                   ? 0u
+                                   : (ens ? grid.size() / N * n_col * ens->size() : (stats ? n_col * stats->size() * N : grid.size() * n_col)),
                                std::numeric_limits<double>::quiet_NaN());
+    if (ens) {
+        // (Ensemble statistics: until the loop has run, the records in their start state - nothing was merged.)
+        const auto &sec = d.get_go_module(call.sampling).sec;
+        const auto n_rec = grid.size() / N * n_col;
+        auto start = ens_init(sec.ens_rec, n_rec);
+        if (d_out != nullptr) {
+            d.ensure_device();
+            device_copy(d_out, start.data(), start.size() * sizeof(std::uint64_t), d.device, d.stream);
+            stream_synchronize(d.device, d.stream);
+        } else {
+            ens_finish(sec.ens_rec, sec.ens, start.data(), n_rec, retval.data());
+        }
+        if (call.ens_raw != nullptr) {
+            *call.ens_raw = std::move(start);
+        }
+    }
     if (stats && d_out == nullptr) {
         for (std::size_t k = 0; k < stats->size(); ++k) {
             if ((*stats)[k] == grid_statistic::count) {

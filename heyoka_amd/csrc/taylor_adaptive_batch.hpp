@@ -244,6 +244,10 @@ public:
         step_hooks hooks = {};
         double *d_out = nullptr;
         grid_sampling sampling = {};
+        // sampling.ensemble (grid_ensemble.hpp): the observables are folded across the systems per grid point,
+        // the return value is ret[(point * n_obs + o) * n_stat + k]. ens_raw, if not null, receives the words of the
+        // accumulators, and so does d_out (ens_layout::words * n_grid * n_obs 64-bit words).
+        std::vector<std::uint64_t> *ens_raw = nullptr;
     };
     std::vector<double> propagate_grid(std::vector<double> grid, const grid_call &call);
     // The first meeting of an integrator with the observables of a sampling (nothing to do without): the checks against the
@@ -423,13 +427,17 @@ grid_sampling grid_sampling_from_kw(const KwArgs &...kw_args)
 {
     std::optional<std::vector<expression>> obs;
     std::optional<std::vector<grid_statistic>> stats;
+    std::optional<std::vector<ensemble_statistic>> ens;
     if constexpr (kw::has_v<kw::observables_tag, KwArgs...>) {
         obs = kw::get(kw::observables, 0, kw_args...);
     }
     if constexpr (kw::has_v<kw::statistics_tag, KwArgs...>) {
         stats = kw::get(kw::statistics, 0, kw_args...);
     }
-    return grid_sampling(std::move(obs), std::move(stats));
+    if constexpr (kw::has_v<kw::ensemble_statistics_tag, KwArgs...>) {
+        ens = kw::get(kw::ensemble_statistics, 0, kw_args...);
+    }
+    return grid_sampling(std::move(obs), std::move(stats), std::move(ens));
 }
 
 // HIP source of the post-step kernel of the device-resident propagate_grid() loop (exposed for the build-time
@@ -1136,10 +1144,17 @@ public:
         // (kw::observables, kw::statistics: the checks against the system come before anything runs.)
         auto gs = detail::grid_sampling_from_kw(kw_args...);
         m_core.prepare_grid_sampling(gs);
+        // (kw::ensemble_raw = &words, a std::vector<std::uint64_t> *: the words of the ensemble accumulators, which
+        // ensemble_propagate_grid_batch() merges over its iterations.)
+        std::vector<std::uint64_t> *ens_raw = nullptr;
+        if constexpr (kw::has_v<kw::ensemble_raw_tag, KwArgs...>) {
+            ens_raw = kw::get(kw::ensemble_raw, 0, kw_args...);
+        }
         auto ret = m_core.propagate_grid(std::move(grid), {.max_steps = ops.max_steps,
                                                            .max_delta_ts = std::move(ops.max_delta_ts),
                                                            .hooks = std::move(ops.hooks),
-                                                           .sampling = std::move(gs)});
+                                                           .sampling = std::move(gs),
+                                                           .ens_raw = ens_raw});
         return {std::move(*ops.user_cb), std::move(ret)};
     }
 

@@ -694,6 +694,50 @@ char *hy_grid_stats_source(hy_sys, const hy_expr *obs, size_t n_obs, const int *
                            int high_accuracy);
 int hy_tab_grid_stats_module(hy_tab, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
                              const char **data, size_t *size);
+/* Ensemble statistics (MI355X extension): the observables are folded ACROSS the systems, per grid point and observable. With
+ * Y[g][o][i] the output of hy_tab_propagate_grid_obs() and V the entries of Y[g][o][:] which are not NaN (fill or computed):
+ *   COUNT      the size of V, as a double;
+ *   MIN / MAX  the extremum of V in the total order -inf < ... < -0.0 < +0.0 < ... < +inf; NaN if V is empty;
+ *   SUM        the EXACT sum of V, rounded once to nearest-even: +0.0 for an exact zero or an empty V, +-inf beyond the largest
+ *              double, +inf (-inf) if V holds +inf (-inf), NaN if it holds both;
+ *   SUM_SQ     the same over y * y, one rounded multiplication per value (a product which overflows counts as +inf);
+ *   MEAN       SUM / COUNT, one division; NaN if COUNT is 0.
+ * The variance is the caller's: (SUM_SQ - SUM * SUM / COUNT) / COUNT cancels when the spread is small next to the mean.
+ * The accumulators are integers updated with integer atomics, so the values do not depend on the order of the systems, on the
+ * launches, on the sharding of an ensemble: hy_tab_propagate_grid_ens() writes the words of the accumulators - acc holds
+ * hy_grid_ens_acc_words() words, a record per (g, o) in this order whose size depends on the list alone -, the accumulators
+ * of the shards of an ensemble are added with hy_grid_ens_merge() (at most 2^30 values per record over everything merged),
+ * and hy_grid_ens_finish() rounds them: out[(g * n_obs + o) * n_stats + k], statistics in the order of stats. The integrator
+ * is left, bit for bit, as by hy_tab_propagate_grid_obs(). HY_ERR_INVALID_ARGUMENT before anything runs: as for the _obs
+ * functions, and for a null or empty list of statistics, an unknown code and a statistic named twice.
+ * HEYOKA_AMD_GRID_ENS=peratomic: one atomic per lane and word instead of one per wavefront and word; the same words. */
+#define HY_ENS_STAT_COUNT 0
+#define HY_ENS_STAT_MIN 1
+#define HY_ENS_STAT_MAX 2
+#define HY_ENS_STAT_SUM 3
+#define HY_ENS_STAT_SUM_SQ 4
+#define HY_ENS_STAT_MEAN 5
+int hy_tab_propagate_grid_ens(hy_tab, const double *grid, size_t n_grid, uint64_t max_steps, const double *max_delta_ts,
+                              size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
+                              const int *stats, size_t n_stats, uint64_t *acc);
+/* The same into a caller-owned device buffer d_acc of hy_grid_ens_acc_words() words; no callback. */
+int hy_tab_propagate_grid_ens_device(hy_tab, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                     const double *max_delta_ts, size_t n_mdt, const hy_expr *obs, size_t n_obs,
+                                     const int *stats, size_t n_stats, uint64_t *d_acc);
+/* The number of 64-bit words of the accumulators of n_grid points and n_obs observables (0 and hy_last_error() on error). */
+size_t hy_grid_ens_acc_words(size_t n_grid, size_t n_obs, const int *stats, size_t n_stats);
+/* On the host: accumulators in their start state; one value y into the record (g, o) - the twin of what the kernel does per
+ * system, for those who fold by hand -; dst += src; the values of the accumulators. */
+int hy_grid_ens_init(uint64_t *acc, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats);
+int hy_grid_ens_add(uint64_t *acc, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats, size_t g, size_t o, double y);
+int hy_grid_ens_merge(uint64_t *dst, const uint64_t *src, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats);
+int hy_grid_ens_finish(const uint64_t *acc, size_t n_grid, size_t n_obs, const int *stats, size_t n_stats, double *out);
+/* INTERNAL hooks of the test suite, the counterparts of hy_grid_stats_source() / hy_tab_grid_stats_module() for the module
+ * which merges across the systems (hy_grid_post and hy_grid_obs0 merge; there is no hy_grid_unsample). */
+char *hy_grid_ens_source(hy_sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, uint32_t order,
+                         int high_accuracy);
+int hy_tab_grid_ens_module(hy_tab, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
+                           const char **data, size_t *size);
 /* get_propagate_res(): (outcome, min |h|, max |h|, n_steps) per lane. */
 int hy_tab_get_propagate_res(hy_tab, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps);
 
