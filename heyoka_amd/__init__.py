@@ -67,6 +67,7 @@ __all__ = [
     "GRID_STATISTICS",
     "ENSEMBLE_STATISTICS",
     "ensemble_accumulators",
+    "ensemble_histogram_accumulators",
     "event_log",
     "callback",
     "diff",
@@ -1205,12 +1206,122 @@ class ensemble_accumulators:
         return out
 
 
-def _grid_sampling(observables, statistics, always_observables=False, ensemble_statistics=None):
+HISTOGRAM_MAX_BINS = 4096
+
+
+def _ensemble_histograms(ensemble_histograms, observables=(), statistics=None, n_obs=None):
+    """The lists of bin edges of the observables (None or an empty list: no histogram) as float64 arrays, with the checks and
+    the messages of the library: (lists, C array of all edges, C array of their numbers)."""
+    if observables is None:
+        raise ValueError("The ensemble histograms of propagate_grid() need a list of observables")
+    if statistics is not None:
+        raise ValueError("The ensemble histograms of propagate_grid() cannot be combined with statistics over the grid")
+    edges = [np.zeros(0) if e is None else np.ascontiguousarray(np.asarray(e, dtype=np.float64).ravel())
+             for e in ensemble_histograms]
+    n_obs = len(list(observables)) if n_obs is None else n_obs
+    if len(edges) != n_obs:
+        raise ValueError("The ensemble histograms of propagate_grid() need one list of bin edges per observable: "
+                         "%d observable(s), %d list(s)" % (n_obs, len(edges)))
+    if all(e.size == 0 for e in edges):
+        raise ValueError("The ensemble histograms of propagate_grid() have no bin edges for any observable")
+    for o, e in enumerate(edges):
+        if e.size == 1:
+            raise ValueError("The bin edges of observable %d of propagate_grid() must be at least 2 finite, strictly "
+                             "increasing values" % o)
+        if e.size > HISTOGRAM_MAX_BINS + 1:
+            raise ValueError("The bin edges of observable %d of propagate_grid() make %d bins: at most %d"
+                             % (o, e.size - 1, HISTOGRAM_MAX_BINS))
+    for o, e in enumerate(edges):
+        if e.size and not (np.all(np.isfinite(e)) and np.all(e[:-1] < e[1:])):
+            raise ValueError("The bin edges of observable %d of propagate_grid() must be at least 2 finite, strictly "
+                             "increasing values" % o)
+    table = np.concatenate(edges)
+    earr = (ctypes.c_double * max(table.size, 1))(*table)
+    narr = (ctypes.c_size_t * max(len(edges), 1))(*[e.size for e in edges])
+    return edges, earr, narr
+
+
+class ensemble_histogram_accumulators:
+    """The counters of the ensemble histograms of propagate_grid() for ``n_grid`` points and one list of bin
+    edges per observable (None: no histogram): ``.edges``, the lists as float64 arrays; ``.raw``, the 64-bit counters, per grid
+    point the records of ``B + 2`` slots - underflow, the ``B`` bins ``[E[s-1], E[s])``, overflow - of the observables with
+    edges; ``.counts(o)``, the ``(n_grid, B + 2)`` view of observable ``o``; ``.merge(other)``, which adds the counters of
+    another part of the ensemble; ``.add(g, o, y)``, the host twin of what the kernel does with one value (the slot is
+    ``numpy.searchsorted(E, y, side="right")``, a NaN is skipped); ``.rank_slot(o, k)``, per grid point the smallest slot whose
+    cumulative count reaches the 1-based rank ``k`` (-1 if there is none); ``.quantile_bracket(o, q)``. A new object holds no
+    value."""
+
+    def __init__(self, n_grid, edges):
+        self.edges, self._earr, self._narr = _ensemble_histograms(edges, n_obs=len(edges))
+        self.n_grid, self.n_obs = int(n_grid), len(self.edges)
+        n = lib.hy_grid_hist_acc_words(self.n_grid, self.n_obs, self._narr)
+        if n == 0 and self.n_grid != 0:
+            raise_for(lib.hy_last_error_code() or 4)
+        self.words = n // self.n_grid if self.n_grid else 0
+        self.raw = np.zeros(n, dtype=np.uint64)
+        raise_for(lib.hy_grid_hist_init(self.raw.ctypes.data, self.n_grid, self.n_obs, self._narr))
+
+    def _offset(self, o):
+        if not 0 <= o < self.n_obs or self.edges[o].size == 0:
+            raise ValueError("The observable %d has no histogram" % o)
+        return int(np.sum([e.size + 1 for e in self.edges[:o] if e.size], dtype=np.int64))
+
+    def counts(self, o):
+        off = self._offset(o)
+        return self.raw.reshape(self.n_grid, self.words)[:, off:off + self.edges[o].size + 1]
+
+    def add(self, g, o, y):
+        raise_for(lib.hy_grid_hist_add(self.raw.ctypes.data, self.n_grid, self.n_obs, self._earr, self._narr, int(g), int(o),
+                                       float(y)))
+        return self
+
+    def merge(self, other):
+        if other.n_grid != self.n_grid or [e.size for e in other.edges] != [e.size for e in self.edges]:
+            raise ValueError("Ensemble histograms of different shapes cannot be merged")
+        if any(not np.array_equal(a, b) for a, b in zip(self.edges, other.edges)):
+            raise ValueError("Ensemble histograms of different bin edges cannot be merged")
+        raise_for(lib.hy_grid_hist_merge(self.raw.ctypes.data, other.raw.ctypes.data, self.n_grid, self.n_obs, self._narr))
+        return self
+
+    def rank_slot(self, o, k):
+        self._offset(o)
+        ks = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.uint64), (self.n_grid,)))
+        out = np.empty(self.n_grid, dtype=np.int64)
+        raise_for(lib.hy_grid_hist_rank_slot(self.raw.ctypes.data, self.n_grid, self.n_obs, self._narr, int(o), ks.ctypes.data,
+                                             out.ctypes.data))
+        return out
+
+    def quantile_bracket(self, o, q):
+        """Per grid point the ``[lower, upper)`` edges of the slot which holds the value of rank ``max(1, ceil(q * n))`` among
+        the ``n`` values counted there: an ``(n_grid, 2)`` array, ``-inf`` / ``+inf`` on the open sides of the underflow and
+        overflow slots, NaN where ``n`` is 0. The rank is computed exactly (``fractions.Fraction``)."""
+        import fractions
+        import math
+
+        fq = fractions.Fraction(q)
+        if not 0 <= fq <= 1:
+            raise ValueError("The quantile %r is outside [0, 1]" % (q,))
+        n = self.counts(o).sum(axis=1, dtype=np.uint64)
+        ks = np.array([max(1, math.ceil(fq * int(v))) if v else 0 for v in n], dtype=np.uint64)
+        slots = self.rank_slot(o, ks)
+        ext = np.concatenate(([-np.inf], self.edges[o], [np.inf]))
+        out = np.full((self.n_grid, 2), np.nan)
+        ok = slots >= 0
+        out[ok, 0] = ext[slots[ok]]
+        out[ok, 1] = ext[slots[ok] + 1]
+        return out
+
+
+def _grid_sampling(observables, statistics, always_observables=False, ensemble_statistics=None, ensemble_histograms=None):
     """What propagate_grid() and its relatives do with ``(observables, statistics)``. The call makes the Python-side checks of
     the statistics; the function it returns converts the observables when its turn has come: (suffix of the name of the C
-    entry point - "", "_obs", "_stats" or "_ens" -, the arguments of that entry point for the lists, the observables, the codes
-    of the statistics). ``always_observables``: there is no entry point without observables."""
+    entry point - "", "_obs", "_stats", "_ens" or "_hist" -, the arguments of that entry point for the lists, the observables,
+    the codes of the statistics). ``always_observables``: there is no entry point without observables. With
+    ``ensemble_histograms`` the function carries the lists of edges as its attribute ``edges``."""
     codes = sarr = None
+    hist = None
+    if ensemble_histograms is not None:
+        hist = _ensemble_histograms(ensemble_histograms, observables, statistics)
     if ensemble_statistics is not None:
         codes, sarr = _ensemble_statistics(ensemble_statistics, observables, statistics)
     elif statistics is not None:
@@ -1220,24 +1331,31 @@ def _grid_sampling(observables, statistics, always_observables=False, ensemble_s
         if observables is None and not always_observables:
             return "", (), None, None
         obs, oarr = _handle_array(list(observables))
+        if hist is not None:
+            return "_hist", (oarr, len(obs), sarr, len(codes or ()), hist[1], hist[2]), obs, codes
         if ensemble_statistics is not None:
             return "_ens", (oarr, len(obs), sarr, len(codes)), obs, codes
         if statistics is None:
             return "_obs", (oarr, len(obs)), obs, None
         return "_stats", (oarr, len(obs), sarr, len(codes)), obs, codes
 
+    lists.edges = hist[0] if hist is not None else None
     return lists
 
 
-def grid_observables_source(sys, observables, order=20, high_accuracy=False, statistics=None, ensemble_statistics=None):
+def grid_observables_source(sys, observables, order=20, high_accuracy=False, statistics=None, ensemble_statistics=None,
+                            ensemble_histograms=None):
     """HIP source of the post-step module of propagate_grid() with the section of ``observables`` for the system ``sys`` at
     the Taylor order ``order``: no integrator, no GPU. ``HEYOKA_AMD_GRID_OBS=registers|staged`` overrides how the kernel
     holds the samples of a grid point (default: registers up to 64 state rows read, the staging buffer beyond).
     ``statistics``: the module which folds the observables into these statistics (see propagate_grid());
     ``ensemble_statistics``: the module which merges them across the systems (``HEYOKA_AMD_GRID_ENS=peratomic``: without the
-    aggregation per wavefront)."""
+    aggregation per wavefront); ``ensemble_histograms``: the module which counts them into histograms, alone or with
+    ``ensemble_statistics`` (``HEYOKA_AMD_GRID_HIST=peratomic|aggregate|hybrid``: the way of merging) - its text depends on the
+    numbers of edges, not on their values. ``HEYOKA_AMD_GRID_HIST_TURNS=1|2|4`` overrides the number of aggregation turns of the
+    hybrid mode (the switch of the measurement which chose the built-in one)."""
     s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
-    sfx, largs, obs, _ = _grid_sampling(observables, statistics, True, ensemble_statistics)()
+    sfx, largs, obs, _ = _grid_sampling(observables, statistics, True, ensemble_statistics, ensemble_histograms)()
     return take_str(check_handle(getattr(lib, "hy_grid%s_source" % sfx)(s._h, *largs, int(order), int(bool(high_accuracy)))))
 
 
@@ -1988,7 +2106,7 @@ class taylor_adaptive_batch:
         return self._propagate(lib.hy_tab_propagate_for, delta_t, max_steps, max_delta_t, callback, write_tc, c_output)
 
     def propagate_grid(self, grid, max_steps=0, max_delta_t=None, callback=None, observables=None, statistics=None,
-                       ensemble_statistics=None):
+                       ensemble_statistics=None, ensemble_histograms=None):
         """propagate_grid(): ``(callback, out)`` with ``out[point, var, lane]``, NaN where not reached. ``observables`` (an
         MI355X extension): a list of expressions over the state variables, ``par[...]`` and ``hy.time`` -
         ``out[point, observable, lane]`` then holds, bit for bit, ``cfunc(observables, vars=state variables)`` of the state
@@ -2008,16 +2126,30 @@ class taylor_adaptive_batch:
         not NaN, and ``(callback, acc)`` is returned with ``acc`` an ``ensemble_accumulators``: ``acc.values[point, observable,
         statistic]``. ``sum`` and ``sum_sq`` are the exact sums rounded once, ``min`` / ``max`` order ``-0.0 < +0.0``: the same
         bits for any order of the systems, any loop and any sharding of the ensemble (``acc.merge(other)``). With per-lane
-        grids a point is a row of the grid. The integrator is left as by the call with ``observables`` alone."""
-        lists = _grid_sampling(observables, statistics, False, ensemble_statistics)
+        grids a point is a row of the grid. The integrator is left as by the call with ``observables`` alone.
+
+        ``ensemble_histograms`` (only with ``observables``, alone or with ``ensemble_statistics``, not with ``statistics``): one
+        list of bin edges per observable, or None for an observable without a histogram - finite, strictly increasing, at most
+        4096 bins. Every value which is not NaN is counted, per grid point, in the slot ``numpy.searchsorted(edges, y,
+        side="right")`` - underflow, the bins ``[E[s-1], E[s])``, overflow -, by comparisons alone, and ``(callback, hist)`` is
+        returned with ``hist`` an ``ensemble_histogram_accumulators`` (``hist.counts(o)[point, slot]``); with
+        ``ensemble_statistics`` as well, ``(callback, (acc, hist))``. The counters are the same for any order of the systems, any
+        loop and any sharding of the ensemble (``hist.merge(other)``)."""
+        lists = _grid_sampling(observables, statistics, False, ensemble_statistics, ensemble_histograms)
         g = _f64(grid)
         if g.ndim == 1:
             g = np.repeat(g[:, None], self.batch_size, axis=1)
         g = np.ascontiguousarray(g)
         n_grid = g.shape[0]
         sfx, largs, obs, codes = lists()
-        acc = None
-        if sfx == "_ens":
+        acc = hist = None
+        if sfx == "_hist":
+            hist = ensemble_histogram_accumulators(n_grid, lists.edges)
+            if codes is not None:
+                acc = ensemble_accumulators(n_grid, len(obs), ensemble_statistics)
+            out = hist.raw
+            largs = largs + (acc.raw.ctypes.data if acc is not None else None,)
+        elif sfx == "_ens":
             acc = ensemble_accumulators(n_grid, len(obs), ensemble_statistics)
             out = acc.raw
         elif codes is not None:
@@ -2038,18 +2170,22 @@ class taylor_adaptive_batch:
             raise err[0]
         self._raise_cb_errors()
         raise_for(rc)
+        if hist is not None:
+            return callback, (hist if acc is None else (acc, hist))
         return callback, (out if acc is None else acc)
 
     def propagate_grid_device(self, grid, out_ptr, max_steps=0, max_delta_t=None, observables=None, statistics=None,
-                              ensemble_statistics=None):
+                              ensemble_statistics=None, ensemble_histograms=None):
         """propagate_grid() with the samples written to a caller-owned device buffer (``out_ptr``: device address of
         n_grid * dim * batch_size doubles, layout [point, var, lane]); ``grid``: 1-D (shared by all the lanes) or
         (n_grid, batch_size). Nothing of that size is materialised on the host. With ``observables`` (see
         propagate_grid()) the buffer holds n_grid * len(observables) * batch_size doubles, layout [point, observable, lane];
         with ``statistics`` as well, len(observables) * len(statistics) * batch_size doubles, layout [observable, statistic,
         lane]; with ``ensemble_statistics`` instead, the 64-bit words of the accumulators, as many as
-        ``ensemble_accumulators(n_grid, len(observables), ensemble_statistics).raw`` has."""
-        lists = _grid_sampling(observables, statistics, False, ensemble_statistics)
+        ``ensemble_accumulators(n_grid, len(observables), ensemble_statistics).raw`` has; with ``ensemble_histograms``, those
+        words, if any, followed by the counters, as many as ``ensemble_histogram_accumulators(n_grid,
+        ensemble_histograms).raw`` has."""
+        lists = _grid_sampling(observables, statistics, False, ensemble_statistics, ensemble_histograms)
         g = np.ascontiguousarray(_f64(grid))
         scalar = g.ndim == 1
         if max_delta_t is None:
@@ -2062,12 +2198,13 @@ class taylor_adaptive_batch:
                                                                        int(max_steps), mptr, mn, *largs,
                                                                        ctypes.c_void_p(int(out_ptr))))
 
-    def grid_observables_module(self, observables, statistics=None, ensemble_statistics=None):
+    def grid_observables_module(self, observables, statistics=None, ensemble_statistics=None, ensemble_histograms=None):
         """(HIP source, gfx950 code object) of the post-step module of propagate_grid() with the section of ``observables``
         (kernels hy_grid_post, hy_grid_obs0, hy_grid_unsample) in this integrator: checked against its system and compiled
         on first use. No GPU is needed. ``statistics``: the module which folds them (see propagate_grid());
-        ``ensemble_statistics``: the module which merges them across the systems."""
-        sfx, largs, obs, _ = _grid_sampling(observables, statistics, True, ensemble_statistics)()
+        ``ensemble_statistics``: the module which merges them across the systems; ``ensemble_histograms``: the module which
+        counts them into histograms (no hy_grid_unsample in either)."""
+        sfx, largs, obs, _ = _grid_sampling(observables, statistics, True, ensemble_statistics, ensemble_histograms)()
         src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
         raise_for(getattr(lib, "hy_tab_grid%s_module" % sfx)(self._h, *largs, ctypes.byref(src), ctypes.byref(data),
                                                              ctypes.byref(n)))

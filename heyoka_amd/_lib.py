@@ -313,6 +313,33 @@ SIGNATURES = [
     ("hy_grid_ens_add", c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_double]),
     ("hy_grid_ens_merge", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t]),
     ("hy_grid_ens_finish", c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p]),
+    (
+        "hy_tab_propagate_grid_hist",
+        c_int,
+        [c_void_p, c_void_p, c_size_t, c_uint64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+         c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    (
+        "hy_tab_propagate_grid_hist_device",
+        c_int,
+        [c_void_p, c_void_p, c_size_t, c_int, c_uint64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    (
+        "hy_grid_hist_source",
+        c_void_p,
+        [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, ctypes.c_uint32, c_int],
+    ),
+    (
+        "hy_tab_grid_hist_module",
+        c_int,
+        [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    ("hy_grid_hist_acc_words", c_size_t, [c_size_t, c_size_t, c_void_p]),
+    ("hy_grid_hist_init", c_int, [c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("hy_grid_hist_add", c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_double]),
+    ("hy_grid_hist_merge", c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
+    ("hy_grid_hist_rank_slot", c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
     ("hy_tab_get_propagate_res", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("hy_model_nbody_ex", c_void_p, [c_uint32, c_void_p, c_size_t, c_void_p]),
     ("hy_model_nbody_energy", c_void_p, [c_uint32, c_void_p, c_size_t, c_void_p]),

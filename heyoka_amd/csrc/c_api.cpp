@@ -295,14 +295,37 @@ void check_tab(const char *fn, hy_tab t)
 
 // ---- what propagate_grid() samples (grid_observables.hpp) ----
 // The lists a function fn of the C interface was given: none, observables (lists == 1), observables and statistics (2),
-// observables and ensemble statistics (3: stats holds HY_ENS_STAT_* codes).
+// observables and ensemble statistics (3: stats holds HY_ENS_STAT_* codes), observables, ensemble statistics - none if
+// n_stats is 0 - and ensemble histograms (4: n_edges[o] edges of observable o, one list behind the other in edges).
 struct c_sampling {
     int lists = 0;
     const hy_expr *obs = nullptr;
     size_t n_obs = 0;
     const int *stats = nullptr;
     size_t n_stats = 0;
+    const double *edges = nullptr;
+    const size_t *n_edges = nullptr;
 };
+
+// The lists of edges of n_obs observables out of the arrays of the C interface.
+std::vector<std::vector<double>> edge_lists_from(const char *fn, const double *edges, const size_t *n_edges, size_t n_obs)
+{
+    if (n_edges == nullptr && n_obs != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of the numbers of bin edges is null");
+    }
+    std::vector<std::vector<double>> ret(n_obs);
+    size_t pos = 0;
+    for (size_t o = 0; o < n_obs; ++o) {
+        if (n_edges[o] != 0u && edges == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the array of bin edges is null");
+        }
+        if (n_edges[o] != 0u) {
+            ret[o].assign(edges + pos, edges + pos + n_edges[o]);
+        }
+        pos += n_edges[o];
+    }
+    return ret;
+}
 
 detail::grid_sampling sampling_from(const char *fn, const c_sampling &c)
 {
@@ -328,6 +351,13 @@ detail::grid_sampling sampling_from(const char *fn, const c_sampling &c)
     if (c.lists == 3) {
         return detail::grid_sampling(std::move(ov), {}, detail::ensemble_statistics_from_codes(c.stats, c.n_stats));
     }
+    if (c.lists == 4) {
+        std::optional<std::vector<ensemble_statistic>> ens;
+        if (c.n_stats != 0u) {
+            ens = detail::ensemble_statistics_from_codes(c.stats, c.n_stats);
+        }
+        return detail::grid_sampling(std::move(ov), {}, std::move(ens), edge_lists_from(fn, c.edges, c.n_edges, c.n_obs));
+    }
     return detail::grid_sampling(std::move(ov), detail::grid_statistics_from_codes(c.stats, c.n_stats));
 }
 
@@ -335,7 +365,7 @@ detail::grid_sampling sampling_from(const char *fn, const c_sampling &c)
 // callbacks are touched (hooks_of()) and before anything runs.
 template <typename H>
 int propagate_grid_host(const char *fn, hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts,
-                        size_t n_mdt, const H &hooks_of, const c_sampling &c, double *out)
+                        size_t n_mdt, const H &hooks_of, const c_sampling &c, double *out, uint64_t *out_hist = nullptr)
 {
     return guarded([&] {
         check_tab(fn, t);
@@ -343,16 +373,28 @@ int propagate_grid_host(const char *fn, hy_tab t, const double *grid, size_t n_g
         t->core.prepare_grid_sampling(gs);
         const auto bs = t->core.get_batch_size();
         // (Ensemble statistics: out receives the words of the accumulators, not their values.)
-        std::vector<std::uint64_t> raw;
-        const bool ens = gs.ensemble.has_value();
+        // (Ensemble histograms: out_hist receives the counters; out the words of the accumulators, if there are any.)
+        std::vector<std::uint64_t> raw, hraw;
+        const bool ens = gs.ensemble.has_value(), hist = gs.histograms.has_value();
+        if (hist && out_hist == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the array of the histogram counters is null");
+        }
+        if (hist && ens != (out != nullptr)) {
+            throw std::invalid_argument(std::string(fn) + "(): the array of the ensemble accumulators must be null without ensemble "
+                                                          "statistics, and only then");
+        }
         const auto ret = t->core.propagate_grid(vec_from(grid, n_grid * bs), {.max_steps = static_cast<std::size_t>(max_steps),
                                                                              .max_delta_ts = expand_mdt(mdts, n_mdt, bs),
                                                                              .hooks = hooks_of(),
                                                                              .sampling = std::move(gs),
-                                                                             .ens_raw = ens ? &raw : nullptr});
+                                                                             .ens_raw = ens ? &raw : nullptr,
+                                                                             .hist_raw = hist ? &hraw : nullptr});
+        if (hist) {
+            std::memcpy(out_hist, hraw.data(), hraw.size() * sizeof(std::uint64_t));
+        }
         if (ens) {
             std::memcpy(out, raw.data(), raw.size() * sizeof(std::uint64_t));
-        } else {
+        } else if (!hist) {
             std::memcpy(out, ret.data(), ret.size() * sizeof(double));
         }
     });
@@ -400,6 +442,15 @@ char *grid_source(const char *fn, hy_sys sys, const c_sampling &c, uint32_t orde
         const auto sec = detail::make_grid_obs_section(gs, svars, std::numeric_limits<std::uint32_t>::max());
         return dup_str(detail::make_grid_source(order, static_cast<std::uint32_t>(svars.size()), high_accuracy != 0, &sec));
     });
+}
+
+// hy_grid_hist_*(): the layout of the records of the numbers of edges of n_obs observables.
+detail::hist_layout hist_layout_from(const char *fn, const size_t *n_edges, size_t n_obs)
+{
+    if (n_edges == nullptr && n_obs != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of the numbers of bin edges is null");
+    }
+    return detail::hist_layout_of(n_edges, n_obs);
 }
 
 // hy_grid_ens_*(): the layout of the records of a list of HY_ENS_STAT_* codes.
@@ -2202,6 +2253,81 @@ int hy_grid_ens_finish(const uint64_t *acc, size_t n_grid, size_t n_obs, const i
         std::vector<ensemble_statistic> list;
         const auto l = ens_layout_from("hy_grid_ens_finish", stats, n_stats, list);
         detail::ens_finish(l, list, acc, n_grid * n_obs, out);
+    });
+}
+// ---- ensemble histograms (grid_histogram.hpp) ----
+int hy_tab_propagate_grid_hist(hy_tab t, const double *grid, size_t n_grid, uint64_t max_steps, const double *mdts, size_t n_mdt,
+                               const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs, const int *stats,
+                               size_t n_stats, const double *edges, const size_t *n_edges, uint64_t *acc_ens, uint64_t *acc_hist)
+{
+    return propagate_grid_host("hy_tab_propagate_grid_hist", t, grid, n_grid, max_steps, mdts, n_mdt,
+                               [&] { return wrap_cbs(t, cbs, n_cbs); }, {4, obs, n_obs, stats, n_stats, edges, n_edges},
+                               reinterpret_cast<double *>(acc_ens), acc_hist);
+}
+int hy_tab_propagate_grid_hist_device(hy_tab t, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                      const double *mdts, size_t n_mdt, const hy_expr *obs, size_t n_obs, const int *stats,
+                                      size_t n_stats, const double *edges, const size_t *n_edges, uint64_t *d_acc)
+{
+    return propagate_grid_dev("hy_tab_propagate_grid_hist_device", t, grid, n_grid, scalar_grid, max_steps, mdts, n_mdt,
+                              {4, obs, n_obs, stats, n_stats, edges, n_edges}, reinterpret_cast<double *>(d_acc));
+}
+char *hy_grid_hist_source(hy_sys sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, const double *edges,
+                          const size_t *n_edges, uint32_t order, int high_accuracy)
+{
+    return grid_source("hy_grid_hist_source", sys, {4, obs, n_obs, stats, n_stats, edges, n_edges}, order, high_accuracy);
+}
+int hy_tab_grid_hist_module(hy_tab t, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, const double *edges,
+                            const size_t *n_edges, char **source, const char **data, size_t *size)
+{
+    return grid_module("hy_tab_grid_hist_module", t, {4, obs, n_obs, stats, n_stats, edges, n_edges}, source, data, size);
+}
+size_t hy_grid_hist_acc_words(size_t n_grid, size_t n_obs, const size_t *n_edges)
+{
+    size_t ret = 0;
+    guarded([&] { ret = n_grid * hist_layout_from("hy_grid_hist_acc_words", n_edges, n_obs).words; });
+    return ret;
+}
+int hy_grid_hist_init(uint64_t *acc, size_t n_grid, size_t n_obs, const size_t *n_edges)
+{
+    return guarded([&] {
+        const auto v = detail::hist_init(hist_layout_from("hy_grid_hist_init", n_edges, n_obs), n_grid);
+        std::memcpy(acc, v.data(), v.size() * sizeof(std::uint64_t));
+    });
+}
+int hy_grid_hist_add(uint64_t *acc, size_t n_grid, size_t n_obs, const double *edges, const size_t *n_edges, size_t g, size_t o,
+                     double y)
+{
+    return guarded([&] {
+        // (The numbers of edges are checked, their values are not: one value costs one search, not a pass over the table.)
+        const auto l = hist_layout_from("hy_grid_hist_add", n_edges, n_obs);
+        if (edges == nullptr) {
+            throw std::invalid_argument("hy_grid_hist_add(): the array of bin edges is null");
+        }
+        if (g >= n_grid || o >= n_obs) {
+            throw std::invalid_argument("hy_grid_hist_add(): the record (" + std::to_string(g) + ", " + std::to_string(o)
+                                        + ") is outside the accumulators");
+        }
+        detail::hist_add(l, edges, reinterpret_cast<std::uint64_t *>(acc) + g * l.words, o, y);
+    });
+}
+int hy_grid_hist_merge(uint64_t *dst, const uint64_t *src, size_t n_grid, size_t n_obs, const size_t *n_edges)
+{
+    return guarded([&] {
+        const auto l = hist_layout_from("hy_grid_hist_merge", n_edges, n_obs);
+        detail::hist_merge(l, reinterpret_cast<std::uint64_t *>(dst), reinterpret_cast<const std::uint64_t *>(src), n_grid);
+    });
+}
+int hy_grid_hist_rank_slot(const uint64_t *acc, size_t n_grid, size_t n_obs, const size_t *n_edges, size_t o, const uint64_t *k,
+                           int64_t *slot)
+{
+    return guarded([&] {
+        const auto l = hist_layout_from("hy_grid_hist_rank_slot", n_edges, n_obs);
+        if (o >= n_obs) {
+            throw std::invalid_argument("hy_grid_hist_rank_slot(): the observable " + std::to_string(o) + " is outside the accumulators");
+        }
+        for (size_t g = 0; g < n_grid; ++g) {
+            slot[g] = detail::hist_rank_slot(l, reinterpret_cast<const std::uint64_t *>(acc) + g * l.words, o, k[g]);
+        }
     });
 }
 int hy_tab_get_propagate_res(hy_tab t, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps)

@@ -248,12 +248,27 @@ auto ensemble_propagate_tmpl(const taylor_adaptive_batch<double> &ta, const Time
         // of its accumulators are merged - integer additions, min / max of keys: the order does not matter - into
         // kw::ensemble_result, if given.)
         std::vector<std::vector<std::uint64_t>> ens_raw(gs.ensemble ? n_iter : 0u);
+        // (kw::ensemble_histograms: the counters of the iterations are added into kw::histogram_result, if given.)
+        std::vector<std::vector<std::uint64_t>> hist_raw(gs.histograms ? n_iter : 0u);
         ensemble_run_per_device(n_iter, n_dev, [&](std::size_t i) {
             res[i] = tas[i].propagate_grid(grid, kw::max_steps = max_steps, kw::max_delta_t = max_delta_ts, kw::callback = cb,
                                            kw::observables = gs.observables, kw::statistics = gs.statistics,
                                            kw::ensemble_statistics = gs.ensemble,
-                                           kw::ensemble_raw = gs.ensemble ? &ens_raw[i] : nullptr);
+                                           kw::ensemble_raw = gs.ensemble ? &ens_raw[i] : nullptr,
+                                           kw::ensemble_histograms = gs.histograms,
+                                           kw::histogram_raw = gs.histograms ? &hist_raw[i] : nullptr);
         });
+        if constexpr (kw::has_v<kw::histogram_result_tag, KwArgs...>) {
+            std::vector<std::uint64_t> &merged = *kw::get(kw::histogram_result, 0, kw_args...);
+            merged.clear();
+            if (gs.histograms && n_iter != 0u) {
+                const auto lay = detail::hist_layout_of(*gs.histograms);
+                merged = hist_raw[0];
+                for (std::size_t i = 1; i < n_iter; ++i) {
+                    detail::hist_merge(lay, merged.data(), hist_raw[i].data(), merged.size() / lay.words);
+                }
+            }
+        }
         if constexpr (kw::has_v<kw::ensemble_result_tag, KwArgs...>) {
             std::vector<double> &merged = *kw::get(kw::ensemble_result, 0, kw_args...);
             merged.clear();

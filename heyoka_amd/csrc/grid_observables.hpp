@@ -29,6 +29,7 @@
 #include "expr_section.hpp"
 #include "expression.hpp"
 #include "grid_ensemble.hpp"
+#include "grid_histogram.hpp"
 #include "kw.hpp"
 
 namespace heyoka_amd::detail
@@ -43,10 +44,15 @@ struct grid_sampling {
     std::optional<std::vector<expression>> observables;
     std::optional<std::vector<grid_statistic>> statistics;
     std::optional<std::vector<ensemble_statistic>> ensemble;
+    // ... and / or the histograms of the observables across the ensemble per grid point (grid_histogram.hpp): a
+    // list of bin edges per observable, an empty one for none. Rejected here without observables, together with statistics over
+    // the grid, and when check_ensemble_histograms() says so.
+    std::optional<std::vector<std::vector<double>>> histograms;
 
     grid_sampling() = default;
     explicit grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats = {},
-                           std::optional<std::vector<ensemble_statistic>> ens = {});
+                           std::optional<std::vector<ensemble_statistic>> ens = {},
+                           std::optional<std::vector<std::vector<double>>> hist = {});
 };
 
 // Observables checked against a system: their section (expr_section.hpp: `reads` are the rows the kernel samples) and how
@@ -63,6 +69,16 @@ struct grid_obs_section : expr_section {
     std::vector<ensemble_statistic> ens;
     ens_layout ens_rec;
     bool ens_aggregate = true;
+    // Ensemble histograms, hist.words == 0: none. The records of hist_layout - the numbers of bins, not the edges, which are
+    // data of the call - and the way of merging (HEYOKA_AMD_GRID_HIST).
+    hist_layout hist;
+    hist_mode hist_merge_mode = hist_default_mode;
+    unsigned hist_turns = hist_hybrid_turns;
+    // The module merges into records behind `out` which do not depend on the number of lanes.
+    [[nodiscard]] bool merges() const
+    {
+        return !ens.empty() || hist.words != 0u;
+    }
 };
 
 // The largest number of rows held in registers: see DESIGN 4.3e for the budget.
@@ -82,10 +98,14 @@ grid_obs_section make_grid_obs_section(const grid_sampling &gs, const std::vecto
 // With ensemble statistics in the section: hy_grid_post and hy_grid_obs0 merge the HY_NOUT values of a grid point into the
 // records (g * HY_NOUT + o) of HY_ENS_WORDS 64-bit words behind `out`, which do not depend on the number of lanes; there is no
 // hy_grid_unsample - the host keeps a copy of the records where samples may be taken back.
+// With ensemble histograms in the section, alone or behind ensemble statistics: the same two kernels search the slot of every
+// value of an observable with edges and count it into the HY_HIST_W words of the grid point, which stand behind the records of
+// the ensemble statistics of all grid points; the shadow copy of both and the edge tables follow (grid_histogram.hpp).
 std::string make_grid_source(std::uint32_t order, std::uint32_t dim, bool high_accuracy, const grid_obs_section *sec);
 
 // The key of the module of gs (with observables) inside an integrator: the text of the observables, the way of holding the
-// samples and the statistics (over the grid, or across the ensemble with the way of merging, HEYOKA_AMD_GRID_ENS).
+// samples and the statistics (over the grid, or across the ensemble with the way of merging, HEYOKA_AMD_GRID_ENS), the numbers
+// of bins of the histograms - not their edges - and their way of merging (HEYOKA_AMD_GRID_HIST).
 std::string grid_obs_key(const grid_sampling &gs);
 
 // ---- grid statistics ----

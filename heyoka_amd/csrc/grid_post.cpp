@@ -10,9 +10,19 @@ namespace heyoka_amd::detail
 {
 
 grid_sampling::grid_sampling(std::optional<std::vector<expression>> obs, std::optional<std::vector<grid_statistic>> stats,
-                             std::optional<std::vector<ensemble_statistic>> ens)
-    : observables(std::move(obs)), statistics(std::move(stats)), ensemble(std::move(ens))
+                             std::optional<std::vector<ensemble_statistic>> ens,
+                             std::optional<std::vector<std::vector<double>>> hist)
+    : observables(std::move(obs)), statistics(std::move(stats)), ensemble(std::move(ens)), histograms(std::move(hist))
 {
+    if (histograms) {
+        if (!observables) {
+            throw std::invalid_argument(ensemble_histograms_need_observables);
+        }
+        if (statistics) {
+            throw std::invalid_argument(ensemble_histograms_exclude_statistics);
+        }
+        check_ensemble_histograms(*histograms, observables->size());
+    }
     if (ensemble) {
         if (!observables) {
             throw std::invalid_argument(ensemble_statistics_need_observables);
@@ -51,6 +61,16 @@ std::string grid_obs_key(const grid_sampling &gs)
         }
         const char *ens_env = std::getenv("HEYOKA_AMD_GRID_ENS");
         key += std::string("|") + (ens_env != nullptr ? ens_env : "");
+    }
+    if (gs.histograms) {
+        key += "|histograms:";
+        for (const auto &e : *gs.histograms) {
+            key += std::to_string(e.size()) + ",";
+        }
+        const char *hist_env = std::getenv("HEYOKA_AMD_GRID_HIST");
+        key += std::string("|") + (hist_env != nullptr ? hist_env : "");
+        const char *turns_env = std::getenv("HEYOKA_AMD_GRID_HIST_TURNS");
+        key += std::string("|") + (turns_env != nullptr ? turns_env : "");
     }
     return key;
 }
@@ -160,6 +180,11 @@ grid_obs_section make_grid_obs_section(const grid_sampling &gs, const std::vecto
             }
         }
     }
+    if (gs.histograms) {
+        ret.hist = hist_layout_of(*gs.histograms);
+        ret.hist_merge_mode = hist_mode_from_env();
+        ret.hist_turns = hist_turns_from_env();
+    }
     return ret;
 }
 
@@ -223,7 +248,16 @@ std::string grid_obs_device_functions(const grid_obs_section &sec)
     src << (sec.reads.empty() ? "0u" : "") << "};\n";
     const bool folds = !sec.stats.empty();
     const bool ens = !sec.ens.empty();
-    if (ens) {
+    const bool hist = sec.hist.words != 0u;
+    if (hist) {
+        // (Behind the text of the ensemble statistics, if any, whose HY_ENS_WORDS places the histogram records.)
+        src << (ens ? ens_device_text(sec.ens_rec, sec.ens_aggregate) : std::string{})
+            << hist_device_text(sec.hist, sec.hist_merge_mode, sec.hist_turns, ens) << R"HIP(
+// The observables of lane i at grid point g and time t_hi, merged into the records behind outp, the start of the output: those
+// of the ensemble statistics, if any, and the counters of the histograms (stg points to the staged samples of the lane).
+__device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 i, const u64 N, double *outp, const unsigned g, const double t_hi
+)HIP";
+    } else if (ens) {
         src << ens_device_text(sec.ens_rec, sec.ens_aggregate) << R"HIP(
 // The observables of lane i at grid point g and time t_hi, merged into the records (g * HY_NOUT + o) behind outp, the start of
 // the output (stg points to the staged samples of the lane).
@@ -264,6 +298,23 @@ __device__ __forceinline__ void hy_obs_section(const hy_grid_args &a, const u64 
         src << d;
     }
     src << code.body;
+    if (hist) {
+        // The merges, behind the last value of the section, on the same opaque values: the records of the ensemble statistics
+        // first, with the text of their own variant, then the bin search and the count of every observable with edges.
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            src << "double y" << o << " = " << code.outs[o] << ";\nasm volatile(\"\" : \"+v\"(y" << o << "));\n";
+        }
+        for (std::size_t o = 0; ens && o < code.outs.size(); ++o) {
+            src << "hy_ens_merge((u64 *)outp + ((u64)g * HY_NOUT + " << o << "u) * HY_ENS_WORDS, y" << o << ");\n";
+        }
+        for (std::size_t o = 0; o < code.outs.size(); ++o) {
+            if (sec.hist.bins[o] != 0u) {
+                src << hist_device_call(sec.hist, o, "y" + std::to_string(o));
+            }
+        }
+        src << "}\n";
+        return src.str();
+    }
     if (ens) {
         // The merge, behind the last value of the section, as with the grid statistics: the values are opaque to the backend.
         for (std::size_t o = 0; o < code.outs.size(); ++o) {
@@ -600,7 +651,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         // would hold a pair of SGPRs each across the whole loop, next to the literals of the section, which are moved ahead
         // of the loop as well - the wave has 102 SGPRs, and 512 VGPRs per lane at 256 lanes per workgroup.
         src << "    const double *tc0 = a.tc + i;\n    asm volatile(\"\" : \"+v\"(tc0));\n";
-        if (sec->ens.empty()) {
+        if (!sec->merges()) {
             src << "    double *out0 = a.out + i;\n    asm volatile(\"\" : \"+v\"(out0));\n";
         }
         if (sec->staged) {
@@ -662,7 +713,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_post(const hy_grid_arg
         } else {
             src << "            xs[j] = res;\n            __builtin_amdgcn_sched_barrier(0);\n        }\n";
         }
-        src << "        " << grid_obs_call(*sec, sec->ens.empty() ? "out0" : "a.out", "stg", "xs", "g", "tg.hi");
+        src << "        " << grid_obs_call(*sec, !sec->merges() ? "out0" : "a.out", "stg", "xs", "g", "tg.hi");
     }
     src << R"HIP(        ++g;
     }
@@ -698,7 +749,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
     }
 }
 )HIP";
-    } else if (sec != nullptr && !sec->ens.empty()) {
+    } else if (sec != nullptr && sec->merges()) {
         // (Ensemble statistics: the records are restored by the host from its copy, there is no hy_grid_unsample.)
         src << R"HIP(
 // Row 0 into the records: the observables of the current state at the first grid time (at the start of the call and again
@@ -724,7 +775,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
 )HIP";
     }
     if (sec != nullptr) {
-        if (!sec->ens.empty()) {
+        if (sec->merges()) {
         } else if (!sec->stats.empty()) {
             src << "\n// The start of the accumulators: the observables of the current state at the first grid time (at the start of "
                    "the call and\n// again after a rollback).\n";
@@ -753,7 +804,7 @@ extern "C" __global__ void __launch_bounds__(256) hy_grid_unsample(const hy_grid
                 src << "    xs[" << n_obs0++ << "] = a.state[(u64)" << r << "u * N + i];\n";
             }
         }
-        src << "    " << grid_obs_call(*sec, sec->ens.empty() ? "a.out + i" : "a.out", "stg", "xs", "0u", "a.grid[i]") << "}\n";
+        src << "    " << grid_obs_call(*sec, !sec->merges() ? "a.out + i" : "a.out", "stg", "xs", "0u", "a.grid[i]") << "}\n";
     }
     return src.str();
 }

@@ -87,6 +87,16 @@ HEYOKA_AMD_KWARG(statistics);
 HEYOKA_AMD_KWARG(ensemble_statistics);
 HEYOKA_AMD_KWARG(ensemble_result);
 HEYOKA_AMD_KWARG(ensemble_raw);
+// ... and / or kw::ensemble_histograms = std::vector<std::vector<double>>{...}, one list of bin edges per observable (an empty
+// one: no histogram for it), together with kw::observables, alone or with kw::ensemble_statistics, never with kw::statistics:
+// every value is counted into the slot numpy.searchsorted(edges, y, side="right") of its grid point (grid_histogram.hpp). The
+// output is the values of the ensemble statistics, if any, followed by the counters as doubles, per grid point the records of
+// B + 2 slots of the observables with edges. kw::histogram_raw = &words (std::vector<std::uint64_t> *) receives the counters
+// themselves; ensemble_propagate_grid_batch(): kw::histogram_result = &vec (std::vector<std::uint64_t> *) receives the counters
+// added over all the iterations.
+HEYOKA_AMD_KWARG(ensemble_histograms);
+HEYOKA_AMD_KWARG(histogram_result);
+HEYOKA_AMD_KWARG(histogram_raw);
 // Events (reference: include/heyoka/events.hpp:87-100).
 HEYOKA_AMD_KWARG(direction);
 HEYOKA_AMD_KWARG(cooldown);

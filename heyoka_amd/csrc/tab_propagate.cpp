@@ -34,6 +34,32 @@ double first_step_limit(const dfloat &rem, int t_dir, double mdt)
     return static_cast<double>(t_dir != 0 ? std::min(dfloat(mdt), rem) : std::max(dfloat(-mdt), rem));
 }
 
+// The records of a call with ensemble statistics and / or histograms to the caller: raw holds the ens_words words of the
+// former, then the counters of the latter. retval, if not null, receives the values of the ensemble statistics followed by the
+// counters as doubles; grid_call::ens_raw and hist_raw receive the words of their region.
+void give_records(const grid_obs_section &sec, const tab_core::grid_call &call, std::vector<std::uint64_t> raw, std::size_t ens_words,
+                  std::vector<double> *retval)
+{
+    if (retval != nullptr) {
+        std::size_t n_vals = 0;
+        if (ens_words != 0u) {
+            const auto n_rec = ens_words / sec.ens_rec.words;
+            ens_finish(sec.ens_rec, sec.ens, raw.data(), n_rec, retval->data());
+            n_vals = n_rec * sec.ens.size();
+        }
+        for (std::size_t w = ens_words; w < raw.size(); ++w) {
+            (*retval)[n_vals + (w - ens_words)] = static_cast<double>(raw[w]);
+        }
+    }
+    if (call.hist_raw != nullptr) {
+        call.hist_raw->assign(raw.begin() + static_cast<std::ptrdiff_t>(ens_words), raw.end());
+    }
+    if (call.ens_raw != nullptr) {
+        raw.resize(ens_words);
+        *call.ens_raw = std::move(raw);
+    }
+}
+
 } // namespace
 
 // ---- stepping (reference: src/taylor_adaptive_batch.cpp:1039-1080) ----
@@ -416,14 +442,22 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     // Ensemble statistics: the variant which merges into the records of the grid points, n_grid * n_obs records
     // of ens_rec.words 64-bit words whatever the number of systems, with a copy of the same size behind them: the records
     // as they were before the samples of a sweep which may be taken back.
-    const bool ens = call.sampling.ensemble.has_value();
-    const std::size_t ens_words = ens ? static_cast<std::size_t>(n_grid) * gov->sec.n_obs * gov->sec.ens_rec.words : 0u;
-    const auto ens_start = ens ? ens_init(gov->sec.ens_rec, static_cast<std::size_t>(n_grid) * gov->sec.n_obs) : std::vector<std::uint64_t>{};
+    // Ensemble histograms, alone or with the ensemble statistics: n_grid records of hist.words counters behind
+    // the records above, the copy covers both, and the edge tables - data of the call, not of the module - follow the copy.
+    // `ens` below is "the module merges into records": ens_words counts the words of both regions.
+    const bool with_ens = call.sampling.ensemble.has_value(), with_hist = call.sampling.histograms.has_value();
+    const bool ens = with_ens || with_hist;
+    const std::size_t ens_only_words = with_ens ? static_cast<std::size_t>(n_grid) * gov->sec.n_obs * gov->sec.ens_rec.words : 0u;
+    const std::size_t hist_words = with_hist ? static_cast<std::size_t>(n_grid) * gov->sec.hist.words : 0u;
+    const std::size_t ens_words = ens_only_words + hist_words;
+    auto ens_start = with_ens ? ens_init(gov->sec.ens_rec, static_cast<std::size_t>(n_grid) * gov->sec.n_obs) : std::vector<std::uint64_t>{};
+    ens_start.resize(ens_words, 0u);
+    const auto hist_edges = with_hist ? hist_edge_table(*call.sampling.histograms) : std::vector<double>{};
     aux_module &sample_mod = gov != nullptr ? gov->loaded(d.device) : *d.grid_mod;
     const std::size_t n_col = gov != nullptr ? gov->sec.n_obs : dim;
     device_buffer b_stage((gov != nullptr && gov->sec.staged) ? static_cast<std::size_t>(dim) * N * dsz : 0u, d.device);
 
-    const auto out_doubles = ens ? 2u * ens_words : (folds ? 2u * gov->sec.n_slots * static_cast<std::size_t>(N) : grid.size() * n_col);
+    const auto out_doubles = ens ? 2u * ens_words + hist_edges.size() : (folds ? 2u * gov->sec.n_slots * static_cast<std::size_t>(N) : grid.size() * n_col);
     const bool own_out = folds || ens;
     device_buffer b_grid(grid.size() * dsz, d.device), b_out((d_out != nullptr && !own_out) ? 0u : out_doubles * dsz, d.device);
     double *const out_ptr = (d_out != nullptr && !own_out) ? d_out : b_out.as<double>();
@@ -431,6 +465,9 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
     device_buffer b_tdir(N * sizeof(int), d.device), b_gidx(N * sizeof(unsigned), d.device), b_cnt(6u * sizeof(unsigned), d.device),
         b_gidx_prev(N * sizeof(unsigned), d.device);
     b_grid.upload(grid.data(), grid.size() * dsz, d.stream);
+    if (with_hist) {
+        device_copy(b_out.as<double>() + 2u * ens_words, hist_edges.data(), hist_edges.size() * dsz, d.device, d.stream);
+    }
     std::vector<double> rhi(N), rlo(N), lim(N), mn(N, pinf), mx(N, 0.), tg(N);
     std::vector<unsigned> gidx(N, 1u);
     std::vector<unsigned long long> ns(N, 0u);
@@ -660,10 +697,18 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
                 + (folds ? ", statistics " + stat_names(*stats) + " folded over the grid (" + std::to_string(gov->sec.n_slots)
                                + " accumulators per system)"
                          : std::string{})
-                + (ens ? ", ensemble statistics merged across the systems per grid point (" + std::to_string(gov->sec.ens_rec.words)
-                             + " words per grid point and observable, "
-                             + (gov->sec.ens_aggregate ? "aggregated per wavefront" : "one atomic per lane") + ")"
-                       : std::string{}));
+                + (with_ens ? ", ensemble statistics merged across the systems per grid point (" + std::to_string(gov->sec.ens_rec.words)
+                                  + " words per grid point and observable, "
+                                  + (gov->sec.ens_aggregate ? "aggregated per wavefront" : "one atomic per lane") + ")"
+                            : std::string{})
+                + (with_hist ? ", ensemble histograms counted across the systems per grid point (" + std::to_string(gov->sec.hist.words)
+                                   + " words per grid point, merge mode "
+                                   + hist_mode_names[static_cast<int>(gov->sec.hist_merge_mode)]
+                                   + (gov->sec.hist_merge_mode == hist_mode::hybrid
+                                          ? " of " + std::to_string(gov->sec.hist_turns) + " turns"
+                                          : std::string{})
+                                   + ")"
+                             : std::string{}));
     }
     if (multi_step && any_step) {
         // (The accumulated counters / extrema take the place of the last launch's own.)
@@ -683,12 +728,8 @@ void tab_core::propagate_grid_device_loop(const std::vector<double> &grid, std::
         if (d_out != nullptr) {
             device_copy(d_out, b_out.get(), ens_words * dsz, d.device, d.stream);
             stream_synchronize(d.device, d.stream);
-        } else {
-            ens_finish(gov->sec.ens_rec, gov->sec.ens, raw.data(), static_cast<std::size_t>(n_grid) * gov->sec.n_obs, retval.data());
         }
-        if (call.ens_raw != nullptr) {
-            *call.ens_raw = std::move(raw);
-        }
+        give_records(gov->sec, call, std::move(raw), ens_only_words, d_out == nullptr ? &retval : nullptr);
     } else if (folds && d_out != nullptr) {
         device_copy(d_out, b_out.get(), n_res * dsz, d.device, d.stream);
         stream_synchronize(d.device, d.stream);
@@ -791,25 +832,27 @@ std::vector<double> tab_core::propagate_grid(std::vector<double> grid, const gri
         throw std::invalid_argument("propagate_grid() with a device output buffer does not support callbacks");
     }
     const auto &ens = call.sampling.ensemble;
+    const auto &hist = call.sampling.histograms;
+    // (Ensemble statistics and histograms: the values of the former, then the counters of the latter as doubles.)
+    const std::size_t n_rec_vals = (ens ? grid.size() / N * n_col * ens->size() : 0u)
+                                   + (hist ? grid.size() / N * d.get_go_module(call.sampling).sec.hist.words : 0u);
     std::vector<double> retval(d_out != nullptr
                                    ? 0u
-                                   : (ens ? grid.size() / N * n_col * ens->size() : (stats ? n_col * stats->size() * N : grid.size() * n_col)),
+                                   : ((ens || hist) ? n_rec_vals : (stats ? n_col * stats->size() * N : grid.size() * n_col)),
                                std::numeric_limits<double>::quiet_NaN());
-    if (ens) {
-        // (Ensemble statistics: until the loop has run, the records in their start state - nothing was merged.)
+    if (ens || hist) {
+        // (Ensemble statistics, histograms: until the loop has run, the records in their start state - nothing was merged.)
         const auto &sec = d.get_go_module(call.sampling).sec;
         const auto n_rec = grid.size() / N * n_col;
-        auto start = ens_init(sec.ens_rec, n_rec);
+        auto start = ens ? ens_init(sec.ens_rec, n_rec) : std::vector<std::uint64_t>{};
+        const auto ens_words = start.size();
+        start.resize(ens_words + grid.size() / N * sec.hist.words, 0u);
         if (d_out != nullptr) {
             d.ensure_device();
             device_copy(d_out, start.data(), start.size() * sizeof(std::uint64_t), d.device, d.stream);
             stream_synchronize(d.device, d.stream);
-        } else {
-            ens_finish(sec.ens_rec, sec.ens, start.data(), n_rec, retval.data());
         }
-        if (call.ens_raw != nullptr) {
-            *call.ens_raw = std::move(start);
-        }
+        give_records(sec, call, std::move(start), ens_words, d_out == nullptr ? &retval : nullptr);
     }
     if (stats && d_out == nullptr) {
         for (std::size_t k = 0; k < stats->size(); ++k) {

@@ -248,6 +248,10 @@ public:
         // the return value is ret[(point * n_obs + o) * n_stat + k]. ens_raw, if not null, receives the words of the
         // accumulators, and so does d_out (ens_layout::words * n_grid * n_obs 64-bit words).
         std::vector<std::uint64_t> *ens_raw = nullptr;
+        // sampling.histograms (grid_histogram.hpp), alone or with sampling.ensemble: the return value is the one
+        // above, if any, followed by the counters as doubles, ret[... + point * hist_layout::words + word]. hist_raw, if not
+        // null, receives the counters; d_out the words of the accumulators followed by the counters.
+        std::vector<std::uint64_t> *hist_raw = nullptr;
     };
     std::vector<double> propagate_grid(std::vector<double> grid, const grid_call &call);
     // The first meeting of an integrator with the observables of a sampling (nothing to do without): the checks against the
@@ -437,7 +441,11 @@ grid_sampling grid_sampling_from_kw(const KwArgs &...kw_args)
     if constexpr (kw::has_v<kw::ensemble_statistics_tag, KwArgs...>) {
         ens = kw::get(kw::ensemble_statistics, 0, kw_args...);
     }
-    return grid_sampling(std::move(obs), std::move(stats), std::move(ens));
+    std::optional<std::vector<std::vector<double>>> hist;
+    if constexpr (kw::has_v<kw::ensemble_histograms_tag, KwArgs...>) {
+        hist = kw::get(kw::ensemble_histograms, 0, kw_args...);
+    }
+    return grid_sampling(std::move(obs), std::move(stats), std::move(ens), std::move(hist));
 }
 
 // HIP source of the post-step kernel of the device-resident propagate_grid() loop (exposed for the build-time
@@ -1150,11 +1158,17 @@ public:
         if constexpr (kw::has_v<kw::ensemble_raw_tag, KwArgs...>) {
             ens_raw = kw::get(kw::ensemble_raw, 0, kw_args...);
         }
+        // (kw::histogram_raw = &words: the counters of the ensemble histograms, likewise.)
+        std::vector<std::uint64_t> *hist_raw = nullptr;
+        if constexpr (kw::has_v<kw::histogram_raw_tag, KwArgs...>) {
+            hist_raw = kw::get(kw::histogram_raw, 0, kw_args...);
+        }
         auto ret = m_core.propagate_grid(std::move(grid), {.max_steps = ops.max_steps,
                                                            .max_delta_ts = std::move(ops.max_delta_ts),
                                                            .hooks = std::move(ops.hooks),
                                                            .sampling = std::move(gs),
-                                                           .ens_raw = ens_raw});
+                                                           .ens_raw = ens_raw,
+                                                           .hist_raw = hist_raw});
         return {std::move(*ops.user_cb), std::move(ret)};
     }
 

@@ -738,6 +738,52 @@ char *hy_grid_ens_source(hy_sys, const hy_expr *obs, size_t n_obs, const int *st
                          int high_accuracy);
 int hy_tab_grid_ens_module(hy_tab, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, char **source,
                            const char **data, size_t *size);
+/* Ensemble histograms (MI355X extension): the observables are binned ACROSS the systems, per grid point. n_edges[o] is the
+ * number of bin edges of observable o - 0: no histogram for it -, and edges holds the lists one behind the other: E[0] < ... <
+ * E[B], finite, B = n_edges[o] - 1 bins, 1 <= B <= 4096. With Y[g][o][i] the output of hy_tab_propagate_grid_obs(), every
+ * Y[g][o][i] which is not NaN is counted in the slot s = #{ j : E[j] <= y } of the record of (g, o), by comparisons alone -
+ * numpy.searchsorted(E, y, side="right"): slot 0 is the underflow (-inf included), slots 1 ... B are the bins [E[s-1], E[s]),
+ * slot B + 1 is the overflow (y >= E[B], +inf included); -0.0 and +0.0 share a slot. A record is B + 2 unsigned 64-bit
+ * counters in slot order; the records of a grid point follow each other in the order of the observables with edges, and
+ * acc_hist holds hy_grid_hist_acc_words() words, grid point after grid point. The counters do not depend on the order of the
+ * systems, on the launches, on the sharding of an ensemble: those of shards are added with hy_grid_hist_merge().
+ * n_stats != 0: the ensemble statistics of hy_tab_propagate_grid_ens() in the same call, and acc_ens receives the words that
+ * call writes; n_stats == 0: none, and acc_ens is null. The integrator is left, bit for bit, as by
+ * hy_tab_propagate_grid_obs(). HY_ERR_INVALID_ARGUMENT before anything runs: as for the _ens functions, and for no edges at all,
+ * a list of one edge, edges which are not finite and strictly increasing, more than 4096 bins.
+ * HEYOKA_AMD_GRID_HIST=peratomic|aggregate|hybrid: how the lanes of a wavefront merge their counts (one atomic per lane; one per
+ * group of lanes with the same word; K turns of the latter, then the former - the default); the same words.
+ * HEYOKA_AMD_GRID_HIST_TURNS=1|2|4 overrides the K the library was built with: the switch of the measurement behind that choice,
+ * any other value is refused. */
+int hy_tab_propagate_grid_hist(hy_tab, const double *grid, size_t n_grid, uint64_t max_steps, const double *max_delta_ts,
+                               size_t n_mdt, const hy_step_callback_desc *cbs, size_t n_cbs, const hy_expr *obs, size_t n_obs,
+                               const int *stats, size_t n_stats, const double *edges, const size_t *n_edges, uint64_t *acc_ens,
+                               uint64_t *acc_hist);
+/* The same into a caller-owned device buffer d_acc: the hy_grid_ens_acc_words() words of the ensemble statistics (none if
+ * n_stats is 0) followed by the hy_grid_hist_acc_words() words of the histograms; no callback. */
+int hy_tab_propagate_grid_hist_device(hy_tab, const double *grid, size_t n_grid, int scalar_grid, uint64_t max_steps,
+                                      const double *max_delta_ts, size_t n_mdt, const hy_expr *obs, size_t n_obs,
+                                      const int *stats, size_t n_stats, const double *edges, const size_t *n_edges,
+                                      uint64_t *d_acc);
+/* The number of 64-bit words of the histograms of n_grid points (0 and hy_last_error() on error). */
+size_t hy_grid_hist_acc_words(size_t n_grid, size_t n_obs, const size_t *n_edges);
+/* On the host: counters in their start state; one value y into the record (g, o) - the twin of what the kernel does per
+ * system -; dst += src; per grid point g the smallest slot of observable o whose cumulative count reaches the 1-based rank
+ * k[g] (slot[g] = -1 if k[g] is 0 or larger than the number of values counted). hy_grid_hist_add() checks the numbers of
+ * edges, not their values: give it edges which a call of hy_tab_propagate_grid_hist() would accept. */
+int hy_grid_hist_init(uint64_t *acc, size_t n_grid, size_t n_obs, const size_t *n_edges);
+int hy_grid_hist_add(uint64_t *acc, size_t n_grid, size_t n_obs, const double *edges, const size_t *n_edges, size_t g, size_t o,
+                     double y);
+int hy_grid_hist_merge(uint64_t *dst, const uint64_t *src, size_t n_grid, size_t n_obs, const size_t *n_edges);
+int hy_grid_hist_rank_slot(const uint64_t *acc, size_t n_grid, size_t n_obs, const size_t *n_edges, size_t o, const uint64_t *k,
+                           int64_t *slot);
+/* INTERNAL hooks of the test suite, the counterparts of hy_grid_ens_source() / hy_tab_grid_ens_module() for the module which
+ * counts into histograms, with or without ensemble statistics (n_stats == 0). The text depends on the numbers of edges, not on
+ * their values. */
+char *hy_grid_hist_source(hy_sys, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, const double *edges,
+                          const size_t *n_edges, uint32_t order, int high_accuracy);
+int hy_tab_grid_hist_module(hy_tab, const hy_expr *obs, size_t n_obs, const int *stats, size_t n_stats, const double *edges,
+                            const size_t *n_edges, char **source, const char **data, size_t *size);
 /* get_propagate_res(): (outcome, min |h|, max |h|, n_steps) per lane. */
 int hy_tab_get_propagate_res(hy_tab, int64_t *outcome, double *min_h, double *max_h, uint64_t *n_steps);
 
