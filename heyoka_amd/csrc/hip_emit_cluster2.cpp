@@ -1884,10 +1884,26 @@ void cluster2_gen::text_event_equations()
     }
 }
 
-// Reads rounds and body; leaves the work loop up to and including the step body in src, and bk_lds.
+namespace
+{
+
+// (The plain-step text of a block is the ordinary one with a few statements exchanged: every exchange must find its place.)
+std::string exchanged(std::string text, const std::string &from, const std::string &to)
+{
+    const auto pos = text.find(from);
+    if (pos == std::string::npos || text.find(from, pos + 1u) != std::string::npos) {
+        throw std::logic_error("hy_taylor (one lane per pair): the plain-step text does not find exactly one '" + from + "'");
+    }
+    return text.replace(pos, from.size(), to);
+}
+
+} // namespace
+
+// Reads rounds and body; leaves the work loop up to and including the step body in src, bk_lds and plain_step.
 void cluster2_gen::text_pickup()
 {
-    src << R"HIP(
+    plain_step = one_lane && !m4 && jet_lds && !v5_flag("noplainstep");
+    std::string work = R"HIP(
 // Work distribution. Propagation (steps per system differ): a device-side queue, one group of systems at a time (taking
 // chunks of 8 groups per atomic costs 1 % there: consecutive groups no longer run at the same time on neighbouring
 // wavefronts, which is what lets the partial-line accesses to the SoA arrays meet in L2). Single steps (equal cost per
@@ -1917,6 +1933,14 @@ bool live = (base + q) < N;
 u64 s = live ? (base + q) : (N - 1u);
 double t_hi = a.time_hi[s], t_lo = a.time_lo[s];
 )HIP";
+    if (plain_step) {
+        // (The wavefront's number for the static schedule as a scalar: as a vector value it is live across the step loop,
+        // whose two paths leave the allocator one register pair short - it then spills this one.)
+        work = exchanged(work, "const u64 hy_waves = ", "const u64 hy_gwave = (u64)blockIdx.x * HY_WPB + (u64)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);\n"
+                                                         "const u64 hy_waves = ");
+        work = exchanged(work, "hy_waves + gwave) * SPW;", "hy_waves + hy_gwave) * SPW;");
+    }
+    src << work;
     for (std::uint32_t i = 0; i < p.n_par; ++i) {
         src << "const double par_" << i << " = a.pars[(u64)" << i << "u * N + s];\n";
     }
@@ -1927,7 +1951,7 @@ double t_hi = a.time_hi[s], t_lo = a.time_lo[s];
         src << row0_w(ow) << " = a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s];\n";
     });
     src << "HY_WSYNC();\n" << (jet_lds ? "" : "__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, \"wavefront\");\n");
-    src << R"HIP(
+    std::string pickup = R"HIP(
 hy_df tfin, rem;
 tfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;
 bool t_dir = true;
@@ -1970,6 +1994,14 @@ int nf_seen = 0;
 bool need_tc = true;
 const bool hy_tc_only = HY_M4 && ((a.pad & 2) != 0);
 )HIP";
+    if (plain_step) {
+        // (rlb = 0: the first step of a system is an ordinary one, which sets it.)
+        pickup = exchanged(pickup, "hy_df tfin, rem;\ntfin.hi = 0.0; tfin.lo = 0.0; rem.hi = 0.0; rem.lo = 0.0;\n",
+                           "hy_df tfin;\ntfin.hi = 0.0; tfin.lo = 0.0;\n// (A lower bound of the magnitude of the remaining time: see the plain step.)\n"
+                           "double rlb = 0.0;\n");
+        pickup = exchanged(pickup, "    rem = hy_df_sub(tfin, tcur);\n", "    const hy_df rem = hy_df_sub(tfin, tcur);\n");
+    }
+    src << pickup;
     // One-lane pair kernel: the per-system bookkeeping of the step loop (times, limits, counters, outcome: 30 registers
     // which nothing reads during the 20 orders) is parked in LDS between the tails of two steps - written at the end of
     // a tail, read back at the beginning of the next one - instead of being spilled to scratch by the register
@@ -2165,7 +2197,7 @@ void cluster2_gen::text_selector()
     }
     // The limit of this step (remaining time / maximum step). NOTE: computed here, next to its only use, and not at the
     // top of the step: its inputs then do not have to be live (or reloaded) before the 20 orders.
-    src << R"HIP(
+    const std::string limit = R"HIP(
 double lim;
 if (HY_MODE == 1) {
     hy_df m; m.lo = 0.0;
@@ -2179,6 +2211,44 @@ if (HY_MODE == 1) {
 }
 lim = fin ? 0.0 : lim;
 )HIP";
+    if (plain_step) {
+        // The plain step. Almost every step of a propagation is one whose bookkeeping decides nothing: the selector's step
+        // is far from the remaining time and from the maximum step, nobody finishes, the state stays finite. A wavefront all
+        // of whose systems take such a step - one ballot, a wave-uniform branch - leaves out the limit, the remaining time
+        // and every select which freezes a finished system. What a system must satisfy:
+        //   - it is not finished, and this is not the last step its step limit allows;
+        //   - 0 < h_sel and 2 h_sel <= min(rlb, mdt), where h_sel = rho_m * safety and rlb <= |remaining time| (below): the
+        //     ordinary path then computes |lim| >= min(|rem.hi|, mdt) > h_sel, so h = +-h_sel, h != lim, h != rem.hi, the
+        //     outcome is "success" and the step counts. (NaNs compare false: the ordinary path.)
+        //   - its new time and state are finite (tested behind the series, as always: a wavefront which fails only there runs
+        //     the ordinary bookkeeping with the same h).
+        // The launch must be a propagation without grid flags and without Taylor coefficients on request (HY_PLAIN_STEP).
+        // The ordinary path computes the remaining time rem = tfin - t exactly as it used to be carried (the same operation on
+        // the same operands). Neither rem nor lim lives across the final evaluation: what the bookkeeping asks of them, h == lim
+        // and h == rem.hi, is answered here (at_lim, at_rem: both false on a plain step).
+        // rlb for the next step: the ordinary path leaves (|rem.hi| (1 - 2^-50) - |h|) (1 - 2^-50) - 2^-100 (|t| + |h|), a plain
+        // step (rlb - |h|) (1 - 2^-50) - 2^-100 (|t| + |h|). The double-length sum t + h is within 2^-104 (|t| + |h|) of the exact
+        // one and the factors absorb the roundings of these expressions, so rlb never exceeds the magnitude of the exact
+        // tfin - t_new, whose computed high part is within 2^-52 of it; the factor 2 above leaves all that far behind. (A
+        // remaining time which is a NaN, or points against the direction of the propagation, gives an rlb no step passes.)
+        src << "#define HY_PLAIN_STEP ((HY_MODE == 1) & ((a.pad & 4) == 0) & (a.tc == nullptr))\n";
+        src << "const double h_sel = rho_m * " << fp_literal(rhofac(order)) << ";\n";
+        src << "const double h_two = h_sel + h_sel;\n";
+        src << "const bool pl_no = fin | !((h_sel > 0.0) & (h_two <= rlb) & (h_two <= mdt)) | (iter + 1u == a.max_steps);\n";
+        src << "double h;\nbool at_lim = false, at_rem = false;\n";
+        src << "if (HY_PLAIN_STEP && __builtin_amdgcn_ballot_w64(pl_no) == 0ull) {\n"
+               "h = t_dir ? h_sel : -h_sel;\n"
+               "rlb = __builtin_fma(-0x1p-100, fabs(t_hi) + h_sel, (rlb - h_sel) * 0x1.ffffffffffff8p-1);\n} else {\n"
+               "hy_df rem; rem.hi = 0.0; rem.lo = 0.0;\n";
+        src << exchanged(limit, "double lim;\nif (HY_MODE == 1) {\n",
+                         "double lim;\nif (HY_MODE == 1) {\n    hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;\n    rem = hy_df_sub(tfin, tcur);\n");
+        src << "h = hy_min(h_sel, fabs(lim));\nh = (lim < 0.0) ? -h : h;\nh = fin ? 0.0 : h;\n";
+        src << "at_lim = (h == lim);\nat_rem = (h == rem.hi);\n";
+        src << "rlb = __builtin_fma(-0x1p-100, fabs(t_hi) + fabs(h), (hy_min(t_dir ? rem.hi : -rem.hi, 0x1p+1000) * 0x1.ffffffffffff8p-1 - fabs(h))"
+               " * 0x1.ffffffffffff8p-1);\n}\n";
+        return;
+    }
+    src << limit;
     src << "double h = rho_m * " << fp_literal(rhofac(order)) << ";\n";
     src << "h = hy_min(h, fabs(lim));\nh = (lim < 0.0) ? -h : h;\n";
     // A system which is done takes steps of length EXACTLY zero (lim = 0 gives that unless the selector produced a nan):
@@ -2441,12 +2511,18 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
         src << "nfi |= !hy_finite(" << std::get<0>(u3) << ") ? 1 : 0;\n";
     }
     // Any lane of the system: one ballot, then the bits of the system's lanes.
-    src << "{\nconst u64 nfb = __builtin_amdgcn_ballot_w64(nfi != 0);\n";
-    if (L == 64u) {
-        src << "nfi = (nfb != 0ull) ? 1 : 0;\n}\n";
-    } else {
-        src << "nfi = (((nfb >> ((threadIdx.x & 63u) & " << (64u - L) << "u)) & " << ((std::uint64_t(1) << L) - 1u)
-            << "ull) != 0ull) ? 1 : 0;\n}\n";
+    // (Plain steps: only the ordinary path asks which system - below.)
+    const auto nf_of_the_system = [&]() {
+        src << "{\nconst u64 nfb = __builtin_amdgcn_ballot_w64(nfi != 0);\n";
+        if (L == 64u) {
+            src << "nfi = (nfb != 0ull) ? 1 : 0;\n}\n";
+        } else {
+            src << "nfi = (((nfb >> ((threadIdx.x & 63u) & " << (64u - L) << "u)) & " << ((std::uint64_t(1) << L) - 1u)
+                << "ull) != 0ull) ? 1 : 0;\n}\n";
+        }
+    };
+    if (!plain_step) {
+        nf_of_the_system();
     }
     // Taylor coefficients on request (wave-uniform branch). NOTE: every lane stores: the idle lanes of a partially filled
     // owner slot replicate the variable of a valid lane and the lanes beyond the end of the ensemble replicate the
@@ -2465,7 +2541,7 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
         // (fin: a system which left the step loop in an EARLIER iteration idles with zero-length steps until its wavefront is
         // done or its slot is refilled - in a launch from grid point to grid point those must not overwrite the coefficients
         // of its exit step.)
-        src << "const bool tc_sys = ((a.pad & 4) == 0) | (!fin & ((h == 0.0) | (h == lim) | hy_reach));\n";
+        src << "const bool tc_sys = ((a.pad & 4) == 0) | (!fin & ((h == 0.0) | " << (plain_step ? "at_lim" : "(h == lim)") << " | hy_reach));\n";
         src << "if (a.tc != nullptr && tc_sys) {\n";
     } else {
         src << (jet_lds ? "if (a.tc != nullptr && !HY_M4) {\n" : "if (a.tc != nullptr) {\n");
@@ -2486,12 +2562,38 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
     src << "}\n";
     // The new state becomes the order-0 row of the jets (read back by the owner lanes at the top of the next step).
     src << "HY_WSYNC();\n" << jet_fence;
+    if (plain_step) {
+        // The plain step (see text_selector()): what the ordinary bookkeeping below leaves for a system which is not finished,
+        // takes h = +-h_sel != lim, rem.hi and stays finite, without its selects; back to the parked record go the words this
+        // changes. The ordinary path follows as the other branch, up to the stores of the record in text_refill_and_tail().
+        src << "if (HY_PLAIN_STEP && __builtin_amdgcn_ballot_w64(pl_no | (nfi != 0)) == 0ull) {\n";
+        for (const auto &u3 : upd) {
+            src << std::get<2>(u3) << " = " << std::get<0>(u3) << ";\n";
+        }
+        src << "HY_WSYNC();\n" << jet_fence;
+        src << R"HIP(
+{
+    const double ah = fabs(h);
+    t_hi = nt_hi;
+    t_lo = nt_lo;
+    last_h = h;
+    outcome = HY_OC_SUCCESS;
+    n_steps = n_steps + 1u;
+    iter = iter + 1u;
+    min_h = hy_min(min_h, ah);
+    max_h = hy_max(max_h, ah);
+}
+)HIP";
+        bk_store(3);
+        src << "} else {\n";
+        nf_of_the_system();
+    }
     for (const auto &u3 : upd) {
         // (A zero-length step leaves the state untouched bit by bit: x + 0 * ... = x also in the compensated sum.)
         src << std::get<2>(u3) << " = (fin | nostate) ? " << std::get<1>(u3) << " : " << std::get<0>(u3) << ";\n";
     }
     src << "HY_WSYNC();\n" << jet_fence;
-    src << R"HIP(
+    std::string ordinary = R"HIP(
 {
     // Bookkeeping of the reference's step() / propagate_until() loops (src/taylor_adaptive_batch.cpp:632-727,
     // :1395-1520) on values frozen once the system is done.
@@ -2527,6 +2629,16 @@ int nfi = !(hy_finite(nt_hi) && hy_finite(nt_lo)) ? 1 : 0;
     fin = fin | done;
 }
 )HIP";
+    if (plain_step) {
+        // (The remaining time of this step was computed next to its limit, in text_selector(), with the two comparisons; none
+        // is carried.)
+        ordinary = exchanged(ordinary, "    hy_df tnew; tnew.hi = nt_hi; tnew.lo = nt_lo;\n    const hy_df rem_new = hy_df_sub(tfin, tnew);\n", "");
+        ordinary = exchanged(ordinary, "hence nt = t, rem_new = rem, ns_new", "hence nt = t, ns_new");
+        ordinary = exchanged(ordinary, "    rem.hi = rem_new.hi;\n    rem.lo = rem_new.lo;\n", "");
+        ordinary = exchanged(ordinary, "((h == lim) ? HY_OC_TIME_LIMIT", "(at_lim ? HY_OC_TIME_LIMIT");
+        ordinary = exchanged(ordinary, "    done |= (h == rem.hi);\n    gfin = fin ? gfin : (h == rem.hi);\n", "    done |= at_rem;\n    gfin = fin ? gfin : at_rem;\n");
+    }
+    src << ordinary;
 }
 
 // Reads rounds and the variant; leaves the per-system refill, the end of the step loop, the cooperative store of mode 4
@@ -2585,7 +2697,7 @@ if (got) {
         for_each_owner([&](auto &, auto &ow) {
             src << row0_w(ow) << " = a.state[(u64)hy_utbl[" << ow.var_tbl * L << "u + l] * N + s];\n";
         });
-        src << R"HIP(
+        std::string fresh = R"HIP(
     tfin.hi = (a.tfin_hi != nullptr) ? a.tfin_hi[s] : a.tfin_s_hi;
     tfin.lo = (a.tfin_hi != nullptr) ? a.tfin_lo[s] : a.tfin_s_lo;
     hy_df tcur; tcur.hi = t_hi; tcur.lo = t_lo;
@@ -2604,6 +2716,11 @@ if (got) {
 }
 HY_WSYNC();
 )HIP";
+        if (plain_step) {
+            // (The first step of the new system is an ordinary one.)
+            fresh = exchanged(fresh, "    rem = hy_df_sub(tfin, tcur);\n", "    const hy_df rem = hy_df_sub(tfin, tcur);\n    rlb = 0.0;\n");
+        }
+        src << fresh;
         if (bk_lds) {
             bk_store(2);
         }
@@ -2611,6 +2728,10 @@ HY_WSYNC();
     }
     if (bk_lds) {
         bk_store(1);
+    }
+    if (plain_step) {
+        // (The end of the ordinary path: text_final_evaluation_and_update().)
+        src << "}\n";
     }
     src << R"HIP(
 if (__builtin_amdgcn_ballot_w64(!fin) == 0ull) break;
@@ -2718,6 +2839,7 @@ void cluster2_gen::finish()
                 + " slot tables, jets in " + (jet_lds ? "LDS" : "global scratch")
                 + (one_lane ? ", slab layout: " + std::to_string(bank_cost) + " conflict cycles per step in the model" : std::string{})
                 + (lane_sum ? ", later sums reduced across the lanes of the first round" : "")
+                + (plain_step ? ", plain steps leave out the bookkeeping of the step loop" : "")
                 + (ev_inline ? "; event equations, final step size and state update inside the stepper" : "");
 }
 

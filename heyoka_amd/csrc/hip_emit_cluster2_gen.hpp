@@ -56,10 +56,17 @@ struct c2_variant {
     //   nosc      the selector's logarithm / exponential with literal polynomial constants (hy_sel_log(), exp()).
     //   nolanesum the sums of the rounds after the first read their operands from LDS, one round per L nodes, instead of
     //             adding them across the lanes which hold them (plan_lane_sums()): the text of before that item.
+    //   noplainstep every step runs the whole bookkeeping of the step loop (plain_step below): the text of before that item.
     // (nofrx, nobkslab, nowide, novx, nostoreplace, frxlds, norx, bankdbg: where they are read.) Parsed once ('+' separates
     // flags where ',' separates variables: ab.py).
     std::set<std::string> v5_flags;
     bool v5_flag(const char *name) const { return v5_flags.count(name) != 0u; }
+    // One lane per pair, jets in LDS, not the stepper with events: a wavefront none of whose systems is finished, clamped,
+    // at its step limit or non-finite in this step takes a PLAIN STEP - behind one ballot, only what such a step changes
+    // (text_selector(), text_final_evaluation_and_update()). The remaining time is then not carried from step to step: the
+    // ordinary path recomputes it from the final time and the current time, and a lower bound of its magnitude (rlb) takes
+    // its place in the parked record.
+    bool plain_step = false;
 };
 
 // ---- Plan and lane geometry. ----
@@ -324,6 +331,7 @@ struct cluster2_gen : c2_variant, c2_geometry, c2_layout, c2_tables, c2_emit {
     void emit_single_compute(std::uint32_t k, const std::vector<std::string> &rdv), emit_single_history(std::uint32_t k), emit_cluster(std::uint32_t k);
     // Module text helpers.
     void bk_store(int which = 0), bk_load();
+    std::string bk_field(const char *nm) const;
     std::string tail_val(const std::vector<std::string> &names, std::uint32_t k, const std::string &ex);
 };
 

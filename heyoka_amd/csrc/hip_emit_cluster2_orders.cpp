@@ -535,14 +535,15 @@ void cluster2_gen::emit_cluster(std::uint32_t k)
 
 // (which = 0: every field; 1: the fields a step changes; 2: the others - final time and limits, which only change when a
 // system is picked up: an LDS store is the most expensive instruction of the kernel.)
+// (3: the fields a plain step changes - plain_step: neither the flags nor anything a clamped or finished step sets.)
 void cluster2_gen::bk_store(int which)
 {
     std::uint32_t f = 0;
     for (const auto *nm : bk_fields_d) {
-        const std::string n_ = nm;
+        const std::string n_ = bk_field(nm);
         const bool constant = n_ == "tfin.hi" || n_ == "tfin.lo" || n_ == "mdt" || n_ == "step_lim" || n_ == "thr";
-        if (which == 0 || (which == 1) != constant) {
-            src << "bk[" << f << "] = " << nm << ";\n";
+        if (!n_.empty() && (which == 0 || ((which == 1 || which == 3) != constant))) {
+            src << "bk[" << f << "] = " << n_ << ";\n";
         }
         ++f;
     }
@@ -552,14 +553,31 @@ void cluster2_gen::bk_store(int which)
     src << "bk[" << f++ << "] = __longlong_as_double((long long)n_steps);\n";
     src << "bk[" << f++ << "] = __longlong_as_double((long long)iter);\n";
     src << "bk[" << f++ << "] = __longlong_as_double((long long)outcome);\n";
+    if (which == 3) {
+        return;
+    }
     src << "bk[" << f++ << "] = __longlong_as_double((long long)((t_dir ? 1 : 0) | (nf_seen != 0 ? 2 : 0) | (gfin ? 4 : 0)));\n";
+}
+
+// (The field of the parked record under this name: with plain steps the remaining time is not carried - the lower bound of
+// its magnitude sits in the word of its high part and the word of its low part is free, "".)
+std::string cluster2_gen::bk_field(const char *nm) const
+{
+    const std::string n_ = nm;
+    if (plain_step && n_ == "rem.hi") {
+        return "rlb";
+    }
+    return (plain_step && n_ == "rem.lo") ? std::string{} : n_;
 }
 
 void cluster2_gen::bk_load()
 {
     std::uint32_t f = 0;
     for (const auto *nm : bk_fields_d) {
-        src << nm << " = bk[" << f++ << "];\n";
+        if (const auto n_ = bk_field(nm); !n_.empty()) {
+            src << n_ << " = bk[" << f << "];\n";
+        }
+        ++f;
     }
     src << "n_steps = (u64)__double_as_longlong(bk[" << f++ << "]);\n";
     src << "iter = (u64)__double_as_longlong(bk[" << f++ << "]);\n";
