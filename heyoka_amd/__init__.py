@@ -1859,6 +1859,11 @@ class taylor_adaptive_batch:
         return float(lib.hy_tab_get_compile_seconds(self._h))
 
     @property
+    def scratch_per_wave(self):
+        """Doubles of global scratch per resident wavefront which the stepper kernel addresses (0: jets / tape on the chip)."""
+        return int(lib.hy_tab_get_scratch_per_wave(self._h))
+
+    @property
     def hip_source(self):
         return take_str(lib.hy_tab_get_hip_source(self._h))
 

@@ -1591,6 +1591,10 @@ double hy_tab_get_compile_seconds(hy_tab t)
 {
     return t->core.get_compile_seconds();
 }
+unsigned long long hy_tab_get_scratch_per_wave(hy_tab t)
+{
+    return t->core.get_scratch_per_wave();
+}
 char *hy_tab_get_hip_source(hy_tab t)
 {
     return dup_str(t->core.get_hip_source());

@@ -2144,10 +2144,15 @@ emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts
     // The jets of the state variables of the systems of a wavefront ([order][system][variable]): in LDS when they fit next to
     // the slab (round 6: one workgroup per CU runs anyway - one wavefront per SIMD -, and through global scratch they cost
     // the chain of 16 pendula 44 GB of HBM traffic per launch, 1.2 TB/s), otherwise in a per-wavefront global scratch.
+    // (This kernel declares two arrays in LDS, the slab and the jets; 2 KB are kept in hand for their alignment and the
+    // compiler's own use. The slab alone is held to the same limit: a plan whose slab does not fit is declined.)
     const std::uint64_t jet_doubles_per_wave = static_cast<std::uint64_t>(order + 1u) * spw * n_col;
-    const bool jets_in_lds
-        = (static_cast<std::uint64_t>(wpb) * spw * slab_stride + static_cast<std::uint64_t>(wpb) * jet_doubles_per_wave) * 8u + 2048u
-          <= 160u * 1024u;
+    const std::uint64_t lds_slab_bytes = static_cast<std::uint64_t>(wpb) * spw * slab_stride * 8u, lds_limit_bytes = 160u * 1024u;
+    const bool jets_in_lds = lds_slab_bytes + static_cast<std::uint64_t>(wpb) * jet_doubles_per_wave * 8u + 2048u <= lds_limit_bytes;
+    if (!jets_in_lds && lds_slab_bytes + 2048u > lds_limit_bytes) {
+        why_not = "the slabs of the systems of a CU (" + std::to_string(lds_slab_bytes) + " bytes) do not fit in its LDS";
+        return ret;
+    }
     if (jets_in_lds) {
         src << "__shared__ double lds_jets[" << static_cast<std::uint64_t>(wpb) * jet_doubles_per_wave << "];\n";
         src << "double *const jetw = lds_jets + wib * " << jet_doubles_per_wave << "u;\n";

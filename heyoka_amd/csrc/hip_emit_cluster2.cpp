@@ -1059,7 +1059,7 @@ void cluster2_gen::build_glue_rounds()
 }
 
 // Reads rounds, the columns, the geometry and slab_stride; leaves the layout of the jets (n_colp, n_dcolp, n_hslots,
-// jet_rows_doubles, jet_doubles_per_wave), jet_lds, compact_tc, pk_tbl (three more tables per packed owner slot), merged.
+// jet_rows_doubles, jet_doubles_per_wave), jet_lds and what follows from it (tables_of_the_jet_placement()), merged.
 void cluster2_gen::layout_jets_and_schedule()
 {
     n_colp = one_lane ? n_col : n_col + 1u;
@@ -1070,15 +1070,50 @@ void cluster2_gen::layout_jets_and_schedule()
     // per lane), otherwise in a per-wave global scratch.
     jet_rows_doubles = static_cast<std::uint64_t>(order + 1u) * spw * n_colp;
     jet_doubles_per_wave = jet_rows_doubles + (one_lane ? static_cast<std::uint64_t>(spw) * n_dcolp : 0u);
-    const auto lds_doubles_slab = static_cast<std::uint64_t>(wpb) * spw * slab_stride;
-    // (Mode 4: plus the source table of the cooperative store of the Taylor coefficients, 4 bytes per row.)
-    const auto lds_tc_table_bytes = m4 ? static_cast<std::uint64_t>(n_eq) * (order + 1u) * 8u : 0u;
-    jet_lds = (lds_doubles_slab + wpb * jet_doubles_per_wave) * 8u + lds_tc_table_bytes <= 160u * 1024u;
+    // The LDS budget rule: the layout with the jets in LDS is built first - everything hy_taylor declares in LDS
+    // follows from it: the tables of the packed final evaluation, the rows of the mode-4 store - and kept when the
+    // footprint of ALL those arrays (lds_arrays(), which text_kernel_prologue() declares them from) fits in the LDS of a
+    // CU; otherwise it is taken back and the layout with the jets in global scratch is held to the same limit.
+    const auto n_ut_before = utbl.size();
+    jet_lds = true;
+    tables_of_the_jet_placement();
+    if (lds_footprint() > lds_limit_bytes) {
+        const auto with_jets = lds_footprint();
+        utbl.resize(n_ut_before), utexpr.resize(n_ut_before), utbl_is_slot.resize(n_ut_before);
+        pk_tbl.clear();
+        jet_lds = false;
+        tables_of_the_jet_placement();
+        detail::log_message(log_level::debug, "cluster kernel, " + std::to_string(L) + " lanes per system, order " + std::to_string(order)
+                                                  + ": with the jets in LDS the kernel would declare " + std::to_string(with_jets)
+                                                  + " bytes of LDS (limit " + std::to_string(lds_limit_bytes) + "): jets in global scratch, "
+                                                  + std::to_string(lds_footprint()) + " bytes");
+    }
+    if (lds_footprint() > lds_limit_bytes) {
+        why_not = "the slab and the lane tables of the systems of a CU (" + std::to_string(lds_footprint()) + " bytes) do not fit in its LDS ("
+                  + std::to_string(lds_limit_bytes) + " bytes)";
+        res.more_lanes_cure = one_lane;
+        return;
+    }
     if (vexch && (!jet_lds || n_dcol != n_col)) {
         why_not = "one-lane pair kernel: the velocity exchange needs the jets in LDS and one position per velocity";
         res.more_lanes_cure = true;
         return;
     }
+
+    // Merged schedule (lane-pair variant, one glue level after the clusters): round k = cluster(k) + glue(k-1),
+    // one LDS synchronisation per order instead of two.
+    merged = pairk && pl.cluster_level == 1u && pl.max_level == 2u
+             && std::all_of(pl.groups.begin(), pl.groups.end(), [](const auto &g) { return g.level == 2u; });
+    if (one_lane && !merged) {
+        why_not = "one-lane pair kernel: the merged schedule does not apply";
+        return;
+    }
+}
+
+// What follows from where the jets live (jet_lds): compact_tc, pk_tbl (three more tables per packed owner slot) and
+// n_tc_rows - after it the tables are complete, and with them the LDS arrays of the kernel.
+void cluster2_gen::tables_of_the_jet_placement()
+{
     // Stepper with events: compact set of Taylor coefficients (see emitted_module::compact_tc) through the cooperative
     // store of the LDS-resident jets. HEYOKA_AMD_COMPACT_TC=0 switches it off (A/B measurements).
     compact_tc = [&]() {
@@ -1124,15 +1159,63 @@ void cluster2_gen::layout_jets_and_schedule()
             pk_tbl[ow.col] = {add_utbl(std::move(tv), false), add_utbl(std::move(tj), false), add_utbl(std::move(tf), false)};
         }
     });
-
-    // Merged schedule (lane-pair variant, one glue level after the clusters): round k = cluster(k) + glue(k-1),
-    // one LDS synchronisation per order instead of two.
-    merged = pairk && pl.cluster_level == 1u && pl.max_level == 2u
-             && std::all_of(pl.groups.begin(), pl.groups.end(), [](const auto &g) { return g.level == 2u; });
-    if (one_lane && !merged) {
-        why_not = "one-lane pair kernel: the merged schedule does not apply";
-        return;
+    // Rows of the cooperative store of the Taylor coefficients (mode 4; the table itself: text_helpers_and_constant_tables()):
+    // order + 1 per state variable, one for a variable which leaves with its order-0 row only.
+    n_tc_rows = 0;
+    if (m4 && one_lane) {
+        for_each_owner([&](auto &, auto &ow) { n_tc_rows += static_cast<std::size_t>(ow.n_valid) * (ow.derived ? 1u : order + 1u); });
+    } else if (m4) {
+        for (std::uint32_t var = 0; var < n_eq; ++var) {
+            const auto &sd = p.sv_defs[var];
+            n_tc_rows += (compact_tc && sd.type == operand::kind::uvar && sd.idx < n_eq) ? 1u : order + 1u;
+        }
     }
+}
+
+// Every array which hy_taylor declares in LDS, in the order of the declarations: text_kernel_prologue() takes the sizes from
+// here, layout_jets_and_schedule() the decision where the jets live. Reads the geometry, the layout and the tables.
+std::vector<cluster2_gen::lds_array> cluster2_gen::lds_arrays() const
+{
+    std::vector<lds_array> out;
+    out.push_back({"lds_slab", 8u, static_cast<std::uint64_t>(wpb) * spw * slab_stride});
+    if (one_lane && !bk_in_slab) {
+        out.push_back({"lds_bk", 8u, static_cast<std::uint64_t>(wpb) * spw * 16u});
+    }
+    if (jet_lds) {
+        out.push_back({"lds_jet", 8u, wpb * jet_doubles_per_wave});
+        if (m4) {
+            out.push_back({"lds_tcsrc", 8u, std::max<std::uint64_t>(n_tc_rows, 1u)});
+        }
+    }
+    out.push_back({"lds_utbl", 2u, std::max<std::uint64_t>(utbl.size(), 1u) * L});
+    if (one_lane) {
+        out.push_back({"lds_dt", 8u, std::max<std::uint64_t>(dtbl.size(), 1u) * L});
+    }
+    if (!pk_tbl.empty()) {
+        out.push_back({"lds_fac", 8u, 2u * (order + 1u)});
+    }
+    return out;
+}
+
+// Bytes of LDS of a workgroup of hy_taylor: the arrays, each rounded up to the strictest alignment any of them asks for (16
+// bytes, the slab of the wide-read layout) - the compiler is free in how it orders them.
+std::uint64_t cluster2_gen::lds_footprint() const
+{
+    std::uint64_t n = 0;
+    for (const auto &a : lds_arrays()) {
+        n += (a.count * a.elem_bytes + 15u) / 16u * 16u;
+    }
+    return n;
+}
+
+std::uint64_t cluster2_gen::lds_count(const char *name) const
+{
+    for (const auto &a : lds_arrays()) {
+        if (std::string(a.name) == name) {
+            return a.count;
+        }
+    }
+    throw std::logic_error(std::string("no LDS array ") + name);
 }
 
 // The state of the order programs. Reads the variant, opts and the plan; leaves t0_ids, the (empty) coefficient histories
@@ -1559,7 +1642,11 @@ __device__ __forceinline__ double hy_swap1(double x)
                     }
                 }
             }
-            n_tc_rows = tc_src.size();
+            if (n_tc_rows != tc_src.size()) {
+                // (Two computations of one quantity: drift between them is a defect of the generator, not a refusal.)
+                throw std::logic_error("mode 4: the source table of the Taylor coefficients has " + std::to_string(tc_src.size())
+                                       + " rows, the LDS budget counted " + std::to_string(n_tc_rows));
+            }
             src << "__constant__ unsigned long long hy_tc_src[" << std::max<std::size_t>(n_tc_rows, 1u) << "] = {";
             for (const auto &t : tc_src) {
                 if (t.row >= (1ull << 20) || t.off >= (1ull << 20) || t.stride >= (1ull << 20)) {
@@ -1595,7 +1682,7 @@ void cluster2_gen::text_kernel_prologue()
 {
     src << "extern \"C\" __global__ void __launch_bounds__(" << bs << ") hy_taylor(const hy_kargs a)\n{\n";
     src << "__shared__ " << (wide_rd ? "__attribute__((aligned(16))) " : "") << "double lds_slab["
-        << static_cast<std::uint64_t>(wpb) * spw * slab_stride << "];\n";
+        << lds_count("lds_slab") << "];\n";
     src << "const unsigned lane = threadIdx.x & 63u;\nconst unsigned wib = threadIdx.x >> 6;\n";
     src << "const unsigned l = lane % " << L << "u;\nconst unsigned q = lane / " << L << "u;\n";
     src << "const u64 N = a.N;\n";
@@ -1607,12 +1694,12 @@ void cluster2_gen::text_kernel_prologue()
         if (bk_in_slab) {
             src << "double *const bk = slab + " << (slab_stride - 16u) << "u;\n";
         } else {
-            src << "__shared__ double lds_bk[" << wpb * spw * 16u << "];\ndouble *const bk = lds_bk + (wib * " << spw << "u + q) * 16u;\n";
+            src << "__shared__ double lds_bk[" << lds_count("lds_bk") << "];\ndouble *const bk = lds_bk + (wib * " << spw << "u + q) * 16u;\n";
         }
     }
     src << "const u64 gwave = (u64)blockIdx.x * " << wpb << "u + wib;\n";
     if (jet_lds) {
-        src << "__shared__ double lds_jet[" << wpb * jet_doubles_per_wave << "];\n";
+        src << "__shared__ double lds_jet[" << lds_count("lds_jet") << "];\n";
         src << "double *const jetw = lds_jet + wib * " << jet_doubles_per_wave << "u;\n";
         if (vexch) {
             // (The rows of the system of this lane: [system][column].)
@@ -1620,7 +1707,7 @@ void cluster2_gen::text_kernel_prologue()
         }
         if (m4) {
             // Source table of the cooperative store of the Taylor coefficients: row | jet column << 16.
-            src << "__shared__ unsigned long long lds_tcsrc[" << std::max<std::size_t>(n_tc_rows, 1u) << "];\n";
+            src << "__shared__ unsigned long long lds_tcsrc[" << lds_count("lds_tcsrc") << "];\n";
             src << "for (unsigned i = threadIdx.x; i < " << n_tc_rows << "u; i += " << bs
                 << "u) lds_tcsrc[i] = hy_tc_src[i];\n__syncthreads();\n";
         }
@@ -1632,7 +1719,7 @@ void cluster2_gen::text_kernel_prologue()
     // ONE in-order counter (vmcnt) - the address of each group of stores then waits for the acknowledgement of all the
     // stores before it (four owner slots: four round trips per group of systems; with the table in LDS: none).
     {
-        const auto n_ut = std::max<std::size_t>(utbl.size(), 1u) * L;
+        const auto n_ut = lds_count("lds_utbl");
         src << "__shared__ unsigned short lds_utbl[" << n_ut << "];\n";
         src << "for (unsigned i = threadIdx.x; i < " << n_ut << "u; i += " << bs << "u) lds_utbl[i] = hy_utbl[i];\n";
         src << "__syncthreads();\n#define hy_utbl lds_utbl\n";
@@ -1643,7 +1730,7 @@ void cluster2_gen::text_kernel_prologue()
         }
     }
     if (one_lane) {
-        src << "__shared__ double lds_dt[" << std::max<std::size_t>(dtbl.size(), 1u) * L << "];\n";
+        src << "__shared__ double lds_dt[" << lds_count("lds_dt") << "];\n";
         src << "for (unsigned i = threadIdx.x; i < " << dtbl.size() * L << "u; i += " << bs << "u) lds_dt[i] = hy_dtbl[i];\n";
         src << "__syncthreads();\nconst double *const dtl = lds_dt + l;\n";
         if (pp.rx[0] >= 0 && !fuse_rx) {
@@ -1652,7 +1739,7 @@ void cluster2_gen::text_kernel_prologue()
     }
     if (!pk_tbl.empty()) {
         // (Factors of the packed evaluation: row 0 = ones - the series of a variable with a jet column -, row 1 = RN(1 / k).)
-        src << "__shared__ double lds_fac[" << 2u * (order + 1u) << "];\n";
+        src << "__shared__ double lds_fac[" << lds_count("lds_fac") << "];\n";
         src << "for (unsigned i = threadIdx.x; i < " << 2u * (order + 1u) << "u; i += " << bs << "u) lds_fac[i] = (i <= " << order
             << "u) ? 1.0 : hy_rk[i - " << (order + 1u) << "u];\n__syncthreads();\n";
     }

@@ -162,7 +162,7 @@ struct c2_layout {
     std::uint32_t n_hslots = 0; // lane slots of the final Horner / compensated evaluation
     std::uint64_t jet_rows_doubles = 0, jet_doubles_per_wave = 0;
     bool jet_lds = false, compact_tc = false;
-    std::size_t n_tc_rows = 0; // rows of the mode-4 store (set where its source table is emitted)
+    std::size_t n_tc_rows = 0; // rows of the mode-4 store (tables_of_the_jet_placement())
 };
 
 // ---- Tables: per-lane unsigned / double tables (indices handed out in insertion order) and who owns which. ----
@@ -268,6 +268,16 @@ struct cluster2_gen : c2_variant, c2_geometry, c2_layout, c2_tables, c2_emit {
         build_glue_rounds(), layout_jets_and_schedule(), init_order_programs(), emit_step_body(),
         text_helpers_and_constant_tables(), text_kernel_prologue(), text_event_equations(), text_pickup(), text_selector(),
         text_event_exclusion(), text_final_evaluation_and_update(), text_refill_and_tail(), finish();
+    // Parts of layout_jets_and_schedule(): the LDS budget. lds_limit_bytes: the LDS of a CU, what a workgroup may declare.
+    static constexpr std::uint64_t lds_limit_bytes = 160u * 1024u;
+    struct lds_array {
+        const char *name;
+        std::uint32_t elem_bytes;
+        std::uint64_t count;
+    };
+    void tables_of_the_jet_placement();
+    std::vector<lds_array> lds_arrays() const;
+    std::uint64_t lds_footprint() const, lds_count(const char *name) const;
     // Parts of plan_and_select_variant() and of layout_one_lane().
     void number_glue_slots(std::uint32_t ns), place_wide_read_slots(), plan_lane_sums(std::uint32_t n_first), renumber_sv_slots();
     // The rounds of a glue group and the node (index in the group) which lane l computes in round r; false: the lane has

@@ -472,6 +472,10 @@ double tab_core::get_compile_seconds() const
 {
     return m_impl->cmod->compile_seconds;
 }
+std::uint64_t tab_core::get_scratch_per_wave() const
+{
+    return m_impl->emitted.scratch_per_wave;
+}
 
 const std::vector<double> &tab_core::get_time() const
 {

@@ -167,6 +167,8 @@ public:
     // The gfx950 code object of the stepper module (the counterpart of llvm_state::get_object_code()).
     [[nodiscard]] const std::vector<char> &get_code_object() const;
     [[nodiscard]] double get_compile_seconds() const;
+    // emitted_module::scratch_per_wave of the stepper: doubles of global scratch per resident wavefront (0: none).
+    [[nodiscard]] std::uint64_t get_scratch_per_wave() const;
     // "unrolled" / "cluster ..." / "table ...": which code generator was selected, and why.
     [[nodiscard]] std::string get_codegen_info() const;
 

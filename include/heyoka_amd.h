@@ -449,6 +449,10 @@ int hy_tab_get_compact_mode(hy_tab);
  * ignores the event for the step. */
 unsigned long long hy_tab_get_event_detection_failures(hy_tab);
 double hy_tab_get_compile_seconds(hy_tab);
+/* No reference counterpart: doubles of global scratch per resident wavefront which the stepper kernel addresses (its jets or
+ * its tape, where they do not live on the chip; 0: none). The driver sizes the buffer as launch grid x wavefronts per
+ * workgroup x this. */
+unsigned long long hy_tab_get_scratch_per_wave(hy_tab);
 char *hy_tab_get_hip_source(hy_tab);  /* generated HIP module (cf. llvm_state::get_ir()); caller frees */
 char *hy_tab_get_decomposition_str(hy_tab);
 /* No reference counterpart: the rewritten INTERNAL program the stepper was generated from when the planner of the

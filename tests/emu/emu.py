@@ -85,7 +85,7 @@ def host_source(hip_source):
 
 
 class EmulatedKernel:
-    def __init__(self, hip_source, contract=False):
+    def __init__(self, hip_source, contract=False, scratch_per_wave=0):
         os.makedirs(BUILD, exist_ok=True)
         text = host_source(hip_source)
         tag = hashlib.sha256((text + str(contract) + open(os.path.join(HERE, "wave_emu.hpp")).read()).encode()).hexdigest()[:16]
@@ -104,6 +104,11 @@ class EmulatedKernel:
         self.block = int(m.group(1))
         m = re.search(r"#define SPW (\d+)u", hip_source)
         self.lanes_per_system = 64 // int(m.group(1)) if m else 1
+        # Steppers which keep the jets of the state variables (or their tape) in global memory: doubles of a.scratch per
+        # resident wavefront as the MODULE reports them - the integrator's scratch_per_wave (emitted_module::scratch_per_wave),
+        # from which the host driver sizes its buffer: launch grid x wavefronts per workgroup x this.
+        self.scratch_per_wave = int(scratch_per_wave)
+        self.reads_scratch = re.search(r"\ba\.scratch\b", hip_source) is not None
         self.order = None
 
     def _grid(self, n, max_grid):
@@ -150,9 +155,15 @@ class EmulatedKernel:
             out["grid_done"] = np.full(n, -1.0)
             keep.append(th)
             a.tc_thr, a.grid_done = ptr(th), ptr(out["grid_done"])
+        # (Scratch of the steppers which keep their jets or tape in global memory, per resident wave: the module's own figure
+        # unless the caller gives a larger one. A kernel which reads a.scratch is not launched without.)
+        scratch_per_wave = int(scratch_per_wave) or self.scratch_per_wave
+        if self.reads_scratch and scratch_per_wave == 0:
+            raise ValueError("this kernel reads a.scratch: pass the integrator's scratch_per_wave to EmulatedKernel() or to run()")
+        if scratch_per_wave < self.scratch_per_wave:
+            raise ValueError("scratch_per_wave = %d, the module reports %d doubles per wavefront" % (scratch_per_wave, self.scratch_per_wave))
         if scratch_per_wave:
-            # (Jet scratch of the steppers which keep the jets of the state variables in global memory: per resident wave.)
-            sc = np.zeros(self._grid(n, max_grid) * (self.block // 64) * int(scratch_per_wave))
+            sc = np.zeros(self._grid(n, max_grid) * (self.block // 64) * scratch_per_wave)
             keep.append(sc)
             a.scratch = ptr(sc)
         a.N, a.max_steps, a.mode, a.pad = n, max_steps, mode, pad
