@@ -1774,57 +1774,6 @@ bool match_pair_distance_event(const taylor_program &p, std::uint32_t u, pair_di
     return true;
 }
 
-// (hip_emit_cluster.cpp; behind it emit_cluster_v2() - hip_emit_cluster2*.cpp - and emit_cluster_v1(). The dispatch below reads
-// emitted_module::cluster_generation and emitted_module::block_v2_phase, never the prose of the notes.)
-emitted_module emit_cluster_or_empty(const taylor_program &, const emit_options &, std::string &why_not);
-emitted_module emit_cluster_multi_or_empty(const taylor_program &, const emit_options &, std::string &why_not);
-emitted_module emit_table(const taylor_program &, const emit_options &);
-emitted_module emit_block(const taylor_program &, const emit_options &, std::string &why_not);
-bool add_state_aliases(const taylor_program &, taylor_program &);
-bool pad_clusters(const taylor_program &, std::uint32_t, taylor_program &);
-bool insert_unit_scalings(const taylor_program &, taylor_program &);
-bool privatise_cluster_inputs(const taylor_program &, taylor_program &);
-bool linearise_accelerations(const taylor_program &, taylor_program &);
-bool externalise_scalings(const taylor_program &, taylor_program &);
-
-std::string program_to_string(const taylor_program &p)
-{
-    std::ostringstream oss;
-    const auto op = [&](const operand &o) {
-        char buf[64];
-        switch (o.type) {
-            case operand::kind::uvar:
-                oss << "u_" << o.idx;
-                break;
-            case operand::kind::num:
-                std::snprintf(buf, sizeof(buf), "%.17g", o.value);
-                oss << buf;
-                break;
-            default:
-                oss << "p" << o.idx;
-        }
-    };
-    for (const auto &n : p.nodes) {
-        oss << func_kind_name(n.kind) << '(';
-        for (std::size_t a = 0; a < n.args.size(); ++a) {
-            if (a != 0u) {
-                oss << ", ";
-            }
-            op(n.args[a]);
-        }
-        oss << ')';
-        for (const auto d : n.deps) {
-            oss << " [dep " << d << "]";
-        }
-        oss << '\n';
-    }
-    for (const auto &d : p.sv_defs) {
-        op(d);
-        oss << '\n';
-    }
-    return oss.str();
-}
-
 dev_switches dev_switches::from_env()
 {
     dev_switches d;
@@ -1864,235 +1813,6 @@ dev_switches dev_switches::from_env()
     d.v5_pad = str("HEYOKA_AMD_V5_PAD");
     d.block_opts = str("HEYOKA_AMD_BLOCK_OPTS");
     return d;
-}
-
-emitted_module emit_hip_module(const taylor_program &prog, const emit_options &opts)
-{
-    if (opts.order < 2u) {
-        throw std::invalid_argument("The Taylor order must be at least 2");
-    }
-    switch (opts.mode) {
-        case emit_mode::unrolled:
-            return emit_detail::emit_unrolled(prog, opts);
-        case emit_mode::cluster: {
-            std::string why;
-            auto m = emit_cluster_or_empty(prog, opts, why);
-            // Pair-interaction systems whose accelerations are not plain sums over the partners (equal or repeated masses:
-            // sum / sub / negation trees, reactions as glue nodes of their own) miss the one-lane-per-pair kernel only
-            // because of that: retry on the internal program with the accelerations flattened (linearise_accelerations()).
-            // (Generations of the wave-cluster kernels, best first: one lane per pair, lane pairs, pipelined, first one.)
-            // (emitted_module::cluster_generation: 5 > 3 > 2 > 1.)
-            const auto kernel_rank = [](const emitted_module &em) { return em.source.empty() ? 0 : em.cluster_generation; };
-            if (opts.dev.linearise && !opts.dev.cluster_v1 && opts.cluster_kernel != 1 && kernel_rank(m) < 5) {
-                taylor_program lin;
-                if (linearise_accelerations(prog, lin)) {
-                    std::string w2;
-                    auto m2 = emit_cluster_or_empty(lin, opts, w2);
-                    // (Unit masses next to other masses: the elided unit factors of the scaled powers, like below.)
-                    taylor_program lin_scaled;
-                    if (m2.source.empty() && w2.rfind("clusters are not isomorphic", 0) == 0 && insert_unit_scalings(lin, lin_scaled)) {
-                        m2 = emit_cluster_or_empty(lin_scaled, opts, w2);
-                        lin = std::move(lin_scaled);
-                    }
-                    if (kernel_rank(m2) > kernel_rank(m)) {
-                        m2.notes += "; accelerations rewritten as flat sums of scaled pair products in the internal program "
-                                    "(re-associated additions: equal to the decomposition to rounding)";
-                        m2.internal_program = program_to_string(lin);
-                        return m2;
-                    }
-                }
-            }
-            if (m.source.empty() && why.rfind("a state variable is a history operand", 0) == 0
-                && opts.dev.state_aliases) {
-                // Retry with alias u variables for those state variables (see add_state_aliases()).
-                taylor_program aliased;
-                if (add_state_aliases(prog, aliased)) {
-                    auto o2 = opts;
-                    std::string why2;
-                    auto m2 = emit_cluster_or_empty(aliased, o2, why2);
-                    if (m2.source.empty() && why2.rfind("more than 64 clusters", 0) == 0) {
-                        std::string why_b;
-                        m2 = emit_block(aliased, o2, why_b);
-                    }
-                    if (!m2.source.empty()) {
-                        m2.notes += "; state variables in history-operand position aliased by u variables";
-                        m2.internal_program = program_to_string(aliased);
-                        return m2;
-                    }
-                    why += "; with state-variable aliases: " + why2;
-                }
-            }
-            if (m.source.empty() && why.rfind("clusters are not isomorphic", 0) == 0) {
-                // Clusters which are sub-shapes of the largest one (test particles next to massive bodies): pad them
-                // in the internal program (see pad_clusters()).
-                taylor_program padded;
-                if (pad_clusters(prog, opts.order, padded)) {
-                    std::string why2;
-                    auto m2 = emit_cluster_or_empty(padded, opts, why2);
-                    if (!m2.source.empty()) {
-                        m2.notes += "; clusters of " + std::to_string(padded.n_u - prog.n_u)
-                                    + " missing members padded to the shape of the largest one";
-                        m2.internal_program = program_to_string(padded);
-                        return m2;
-                    }
-                    why += "; with padded clusters: " + why2;
-                }
-                // Clusters which differ by an elided unit factor (unit masses next to other masses / test particles).
-                taylor_program scaled_p;
-                if (insert_unit_scalings(prog, scaled_p)) {
-                    std::string why3;
-                    auto m3 = emit_cluster_or_empty(scaled_p, opts, why3);
-                    const taylor_program *base = &scaled_p;
-                    taylor_program padded2;
-                    if (m3.source.empty() && why3.rfind("clusters are not isomorphic", 0) == 0
-                        && pad_clusters(scaled_p, opts.order, padded2)) {
-                        m3 = emit_cluster_or_empty(padded2, opts, why3);
-                        base = &padded2;
-                    }
-                    if (!m3.source.empty()) {
-                        m3.notes += "; " + std::to_string(base->n_u - prog.n_u)
-                                    + " members added to the internal program (unit scalings of elided factors, padding)";
-                        m3.internal_program = program_to_string(*base);
-                        return m3;
-                    }
-                    why += "; with unit scalings: " + why3;
-                }
-            }
-            // Clusters which share coordinate differences or have a negation where the others have a difference (fixed
-            // centres / mascons with repeated or zero coordinates): private copies per cluster in the internal program
-            // (see privatise_cluster_inputs()), then - if needed - the unit scalings and the padding on top of it; wave-cluster
-            // kernels, or block mode beyond 64 clusters.
-            const auto try_private_inputs = [&](emitted_module &res) {
-                taylor_program priv;
-                if (!privatise_cluster_inputs(prog, priv)) {
-                    return false;
-                }
-                std::vector<taylor_program> variants;
-                variants.push_back(priv);
-                taylor_program tmp;
-                if (insert_unit_scalings(priv, tmp)) {
-                    variants.push_back(tmp);
-                }
-                std::string why_p;
-                for (const auto &v : variants) {
-                    std::string w;
-                    auto mp = emit_cluster_or_empty(v, opts, w);
-                    const taylor_program *base = &v;
-                    taylor_program padded;
-                    if (mp.source.empty() && w.rfind("clusters are not isomorphic", 0) == 0
-                        && pad_clusters(v, opts.order, padded)) {
-                        mp = emit_cluster_or_empty(padded, opts, w);
-                        base = &padded;
-                    }
-                    if (mp.source.empty() && w.rfind("more than 64 clusters", 0) == 0) {
-                        std::string wb;
-                        mp = emit_block(*base, opts, wb);
-                        w += wb.empty() ? "" : ("; block mode: " + wb);
-                    }
-                    if (!mp.source.empty()) {
-                        mp.notes += "; internal program with private coordinate differences per cluster ("
-                                    + std::to_string(static_cast<long long>(base->n_u) - static_cast<long long>(prog.n_u))
-                                    + " members more than the decomposition)";
-                        mp.internal_program = program_to_string(*base);
-                        res = std::move(mp);
-                        return true;
-                    }
-                    why_p = w;
-                }
-                why += "; with private cluster inputs: " + why_p;
-                return false;
-            };
-            if (m.source.empty() && why.find("clusters are not isomorphic") != std::string::npos) {
-                emitted_module mp;
-                if (try_private_inputs(mp)) {
-                    return mp;
-                }
-            }
-            if (m.source.empty() && why.rfind("more than 64 clusters", 0) == 0) {
-                // Too many clusters for one wavefront: one system per workgroup.
-                std::string why_b;
-                // Measured on an MI355X: block mode beats the table-driven one-lane-per-system kernels by 5x
-                // (nbody(12), 66 clusters) to 44x (nbody(64)) - it is used whenever it is applicable.
-                auto b = emit_block(prog, opts, why_b);
-                // (Distinct masses: the scalings of the pair products sit inside the clusters, which keeps the decomposition off
-                // the v2 cluster phase - rolled order loop, rows in registers, index-pair convolutions. externalise_scalings()
-                // gives the internal program the clusters of the equal-mass system, the scalings become glue nodes.)
-                if (opts.dev.linearise && !b.block_v2_phase && !opts.exact_division) {
-                    taylor_program ext;
-                    if (externalise_scalings(prog, ext)) {
-                        std::string wl;
-                        auto o2 = opts;
-                        o2.block_no_absorb = true;
-                        auto b2 = emit_block(ext, o2, wl);
-                        if (!b2.source.empty() && b2.block_v2_phase) {
-                            b2.notes += "; scalings of the pair products moved out of the clusters in the internal program (c (d "
-                                        "r^-3) for d (c r^-3): equal to the decomposition to rounding)";
-                            b2.internal_program = program_to_string(ext);
-                            return b2;
-                        }
-                    }
-                }
-                if (!b.source.empty()) {
-                    return b;
-                }
-                why += why_b.empty() ? "; block mode: too few clusters" : ("; block mode: " + why_b);
-                if (why_b.find("clusters are not isomorphic") != std::string::npos) {
-                    emitted_module mp;
-                    if (try_private_inputs(mp)) {
-                        return mp;
-                    }
-                }
-            }
-            // (Decompositions small enough for straight-line code on ONE lane stay there: a handful of clusters spread
-            // over two or four lanes with an LDS exchange is not faster than the registers of a single lane.)
-            if (m.source.empty() && opts.dev.multi_class && !opts.event_stepper && prog.nodes.size() > opts.unroll_max_nodes) {
-                // Clusters of several shapes (point-mass pairs next to oblateness / drag / relativistic terms, mixed
-                // models) or at several dependency levels: one section of straight-line code per CLASS of clusters, cluster
-                // i of a class on lane i of the system (emit_cluster_v1() on a multi-class plan); with alias u variables
-                // for state variables in history position where needed.
-                std::string why_m;
-                auto mm = emit_cluster_multi_or_empty(prog, opts, why_m);
-                if (mm.source.empty() && why_m.rfind("a state variable is a history operand", 0) == 0 && opts.dev.state_aliases) {
-                    taylor_program aliased;
-                    if (add_state_aliases(prog, aliased)) {
-                        std::string why_a;
-                        mm = emit_cluster_multi_or_empty(aliased, opts, why_a);
-                        if (!mm.source.empty()) {
-                            mm.notes += "; state variables in history-operand position aliased by u variables";
-                            mm.internal_program = program_to_string(aliased);
-                        }
-                        why_m += "; with state-variable aliases: " + why_a;
-                    }
-                }
-                if (!mm.source.empty()) {
-                    mm.notes += " (single-class planners: " + why + ")";
-                    return mm;
-                }
-                why += "; multi-class plan: " + why_m;
-            }
-            if (m.source.empty()) {
-                // Not applicable to this DAG: fall back to the generic one-system-per-lane code, unrolled
-                // for small decompositions (registers), table-driven for large ones (bounded code size, the
-                // reason compact mode exists in the reference).
-                auto u = (prog.nodes.size() > opts.unroll_max_nodes) ? emit_table(prog, opts) : emit_detail::emit_unrolled(prog, opts);
-                u.notes += (u.notes.empty() ? "" : "; ") + ("cluster mode not applicable: " + why);
-                return u;
-            }
-            return m;
-        }
-        case emit_mode::table:
-            return emit_table(prog, opts);
-        case emit_mode::block: {
-            std::string why;
-            auto b = emit_block(prog, opts, why);
-            if (b.source.empty()) {
-                throw std::invalid_argument("Block mode is not applicable to this system: " + why);
-            }
-            return b;
-        }
-        default:
-            throw not_implemented_error("The requested code generation mode is not implemented yet");
-    }
 }
 
 } // namespace heyoka_amd

@@ -11,6 +11,7 @@
 #include <array>
 #include <functional>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "decompose.hpp"
@@ -131,7 +132,8 @@ struct emitted_module {
     std::string notes;
     // Which generation of the wave-cluster generators wrote the kernel: 0 = not a wave-cluster kernel, otherwise the numbers
     // of emit_options::cluster_kernel - 1 (first generation, multi-class), 2 (pipelined), 3 (lane pairs), 5 (one lane per
-    // pair). The dispatch in emit_hip_module() reads this, never the prose of `notes`.
+    // pair). The dispatch in emit_hip_module() reads this (and the refusal_code of an attempt which was refused), never the
+    // prose of `notes`.
     int cluster_generation = 0;
     // Block mode: the cluster phase is the rolled "v2 cluster phase" (the pair phase, see hip_emit_block_pair.cpp).
     bool block_v2_phase = false;
@@ -162,6 +164,35 @@ struct emitted_module {
     std::string internal_program;
     // The stepper reduces the state variables of emit_options::angle_reduce after every state update.
     bool angle_reduce_fused = false;
+    // emit_mode::cluster ended on a generic stepper (straight-line or table): no wave-cluster / block planner could shape the
+    // decomposition, `notes` says why ("cluster mode not applicable: ...").
+    bool cluster_fallback = false;
+};
+
+// Why a generator or the planner refused a program: the diagnostic for the notes and the log, and - for the reasons the
+// selection of the stepper reacts to - a code, so that nothing ever depends on the wording of the text.
+//   not_isomorphic     the clusters have different shapes (cured by padding, unit scalings, private inputs, or by planning
+//                      without the absorption of linear nodes)
+//   too_many_clusters  more clusters than plan_limits::max_clusters (block mode takes over)
+//   state_var_history  a state variable is a history operand of a nonlinear function (cured by alias u variables)
+//   other              everything else: a reason nobody reacts to
+enum class refusal_code { none, not_isomorphic, too_many_clusters, state_var_history, other };
+struct emit_refusal {
+    refusal_code code = refusal_code::none;
+    std::string text; // the diagnostic
+    emit_refusal() = default;
+    emit_refusal(refusal_code c, std::string t) : code(c), text(std::move(t)) {}
+    // (Implicit: the generators write `why_not = "...";`.)
+    emit_refusal(std::string t) : code(t.empty() ? refusal_code::none : refusal_code::other), text(std::move(t)) {}
+    emit_refusal(const char *t) : emit_refusal(std::string(t)) {}
+    bool empty() const
+    {
+        return code == refusal_code::none;
+    }
+    void clear()
+    {
+        *this = emit_refusal{};
+    }
 };
 
 // Textual form of a flattened program (see emitted_module::internal_program).

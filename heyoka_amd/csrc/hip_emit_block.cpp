@@ -112,7 +112,7 @@ void block_tables::emit_dtbl(const std::string &name, const std::vector<double> 
     tbl << "};\n";
 }
 
-block_gen::block_gen(const taylor_program &p_, const emit_options &opts_, std::string &why_not_)
+block_gen::block_gen(const taylor_program &p_, const emit_options &opts_, emit_refusal &why_not_)
     : p(p_), opts(opts_), why_not(why_not_), sw(block_switches::parse(opts_.dev.block_opts)), n_eq(p_.n_eq), order(opts_.order),
       e(p_, opts_.order), os(e.os)
 {
@@ -901,7 +901,7 @@ emitted_module block_gen::result()
 
 } // namespace block_detail
 
-emitted_module emit_block(const taylor_program &p, const emit_options &opts, std::string &why_not)
+emitted_module emit_block(const taylor_program &p, const emit_options &opts, emit_refusal &why_not)
 {
     block_detail::block_gen g(p, opts, why_not);
     if (!g.plan() || !g.input_jets()) {

@@ -153,7 +153,7 @@ inline std::string nm2(const char *b, std::uint32_t i, std::uint32_t r)
 struct block_gen : block_geometry, block_input_jets, block_tables, pair_phase {
     const taylor_program &p;
     const emit_options &opts;
-    std::string &why_not;
+    emit_refusal &why_not;
     const block_switches sw;
     const std::uint32_t n_eq, order;
     ssa_emitter e;
@@ -163,7 +163,7 @@ struct block_gen : block_geometry, block_input_jets, block_tables, pair_phase {
     std::uint64_t per_block = 0; // doubles of scratch per workgroup
     std::uint32_t wpb = 0;       // wavefronts per workgroup
 
-    block_gen(const taylor_program &p, const emit_options &opts, std::string &why_not);
+    block_gen(const taylor_program &p, const emit_options &opts, emit_refusal &why_not);
 
     // Stages, in the order emit_block() calls them; a stage which refuses returns false (plan(), input_jets(): with why_not
     // set; pair_phase_applicable(), pair_parameters(): the generic cluster phase takes over).

@@ -48,1743 +48,11 @@ using cluster_detail::cluster_plan;
 using cluster_detail::glue_group;
 using cluster_detail::is_var;
 
-// u variables whose *full history* node n needs (besides, possibly, its own).
-// NOTE: cu (optional) = constant u variables (constant_uvars()): a product with a constant factor is linear in the other
-// one and needs no history (ssa_emitter::node evaluates it as c^[0] * x^[k]). Used by the wave-cluster planner only.
-std::vector<std::uint32_t> history_operands(const dc_node &n, const std::vector<char> *cu = nullptr)
-{
-    std::vector<std::uint32_t> ret;
-    const auto &a = n.args;
-    switch (n.kind) {
-        case func_kind::prod:
-            if (a.size() == 2u && is_var(a[0]) && is_var(a[1])) {
-                if (cu != nullptr && ((*cu)[a[0].idx] != 0 || (*cu)[a[1].idx] != 0)) {
-                    break;
-                }
-                ret = {a[0].idx, a[1].idx};
-            }
-            break;
-        case func_kind::div:
-            if (is_var(a[1])) {
-                ret = {a[1].idx};
-            }
-            break;
-        case func_kind::sum_sq:
-            for (const auto &o : a) {
-                if (is_var(o)) {
-                    ret.push_back(o.idx);
-                }
-            }
-            break;
-        case func_kind::pow:
-            // NOTE: sqrt only needs the current order of its base, but it always needs its own history:
-            // keep things simple and treat the base as a history operand in all cases.
-            if (is_var(a[0])) {
-                ret = {a[0].idx};
-            }
-            break;
-        case func_kind::sin:
-        case func_kind::cos:
-            if (is_var(a[0])) {
-                ret = {a[0].idx};
-                for (const auto d : n.deps) {
-                    ret.push_back(d);
-                }
-            }
-            break;
-        case func_kind::exp:
-        case func_kind::log:
-            if (is_var(a[0])) {
-                ret = {a[0].idx};
-            }
-            break;
-        case func_kind::tan:
-        case func_kind::tanh:
-        case func_kind::sinh:
-        case func_kind::cosh:
-        case func_kind::erf:
-        case func_kind::sigmoid:
-        case func_kind::asin:
-        case func_kind::acos:
-        case func_kind::atan:
-        case func_kind::asinh:
-        case func_kind::acosh:
-        case func_kind::atanh:
-            // Argument + hidden dependency (the functions' own histories are added by the planner).
-            if (is_var(a[0])) {
-                ret = {a[0].idx};
-                for (const auto d : n.deps) {
-                    ret.push_back(d);
-                }
-            }
-            break;
-        default:
-            break;
-    }
-    return ret;
-}
-
-// Kinds that can be evaluated as glue (only current-order operand values).
-bool is_glue_kind(const dc_node &n, const std::vector<char> *cu = nullptr)
-{
-    switch (n.kind) {
-        case func_kind::sum:
-        case func_kind::sub:
-        case func_kind::num_identity:
-        case func_kind::time:
-            return true;
-        case func_kind::prod:
-            if (n.args.size() == 2u && is_var(n.args[0]) && is_var(n.args[1])) {
-                return cu != nullptr && ((*cu)[n.args[0].idx] != 0 || (*cu)[n.args[1].idx] != 0);
-            }
-            return n.args.size() == 2u;
-        case func_kind::div:
-            return !is_var(n.args[1]);
-        default:
-            return history_operands(n, cu).empty();
-    }
-}
-
-struct union_find {
-    std::vector<std::uint32_t> p;
-    explicit union_find(std::size_t n) : p(n)
-    {
-        std::iota(p.begin(), p.end(), 0u);
-    }
-    std::uint32_t find(std::uint32_t x)
-    {
-        while (p[x] != x) {
-            p[x] = p[p[x]];
-            x = p[x];
-        }
-        return x;
-    }
-    void unite(std::uint32_t a, std::uint32_t b)
-    {
-        a = find(a);
-        b = find(b);
-        if (a != b) {
-            p[std::max(a, b)] = std::min(a, b);
-        }
-    }
-};
-
-} // namespace
-
-// Build the plan; returns an empty string on success, otherwise the reason why cluster mode is not applicable.
-// State variables as history operands. The planner groups a nonlinear node with the u variables whose whole history it
-// needs; a *state variable* in that position (model::np1body: |r_i|^2 = sum_sq(x_i, y_i, z_i), x_i * |r_i|^-3) cannot be
-// a member of a cluster. This transformation
-//   - gives every state variable s read by a cluster member a glue copy g_s = sum(s),
-//   - gives every state variable in history position an alias a_s = g_s - z_s (z_s: a constant-zero node of its own),
-//     an ordinary cluster member with the shape of the coordinate differences of a pair cluster, and
-//   - rewires the members to g_s / a_s,
-// so that heliocentric and pair clusters are isomorphic and sit at the same dependency level (both read level-1 glue).
-// The values are unchanged (s + nothing, s - 0). Returns false if the program needs no alias.
-bool add_state_aliases(const taylor_program &p, taylor_program &out)
-{
-    const auto n_eq = p.n_eq;
-    // Cluster members: nodes with history operands, and the u variables in history position.
-    std::vector<char> member(p.n_u, 0);
-    std::set<std::uint32_t> hist_sv;
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        const auto hs = history_operands(p.nodes[i]);
-        if (!hs.empty()) {
-            member[n_eq + i] = 1;
-        }
-        for (const auto h : hs) {
-            if (h < n_eq) {
-                hist_sv.insert(h);
-            } else {
-                member[h] = 1;
-            }
-        }
-    }
-    if (hist_sv.empty()) {
-        return false;
-    }
-    // State variables read by members (in any position).
-    std::set<std::uint32_t> used_sv(hist_sv.begin(), hist_sv.end());
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        if (member[n_eq + i] != 0) {
-            for (const auto &o : p.nodes[i].args) {
-                if (o.type == operand::kind::uvar && o.idx < n_eq) {
-                    used_sv.insert(o.idx);
-                }
-            }
-        }
-    }
-
-    out = p;
-    out.nodes.clear();
-    std::map<std::uint32_t, std::uint32_t> copy_of, alias_of;
-    std::uint32_t next = n_eq;
-    const auto uvar = [](std::uint32_t u) { return operand{operand::kind::uvar, u, 0.}; };
-    for (const auto sv : used_sv) {
-        dc_node g;
-        g.kind = func_kind::sum;
-        g.args.push_back(uvar(sv));
-        out.nodes.push_back(g);
-        copy_of[sv] = next++;
-    }
-    for (const auto sv : hist_sv) {
-        dc_node z;
-        z.kind = func_kind::num_identity;
-        z.args.push_back(operand{operand::kind::num, 0u, 0.});
-        out.nodes.push_back(z);
-        dc_node a;
-        a.kind = func_kind::sub;
-        a.args.push_back(uvar(copy_of.at(sv)));
-        a.args.push_back(uvar(next));
-        out.nodes.push_back(a);
-        alias_of[sv] = next + 1u;
-        next += 2u;
-    }
-    const auto m = next - n_eq;
-    const auto shift = [&](std::uint32_t u) { return u < n_eq ? u : u + m; };
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        auto nn = p.nodes[i];
-        const auto hs = history_operands(p.nodes[i]);
-        const bool is_member = member[n_eq + i] != 0;
-        for (auto &o : nn.args) {
-            if (o.type != operand::kind::uvar) {
-                continue;
-            }
-            if (o.idx >= n_eq) {
-                o.idx = shift(o.idx);
-            } else if (std::find(hs.begin(), hs.end(), o.idx) != hs.end()) {
-                o.idx = alias_of.at(o.idx);
-            } else if (is_member) {
-                o.idx = copy_of.at(o.idx);
-            }
-        }
-        for (auto &d : nn.deps) {
-            d = shift(d);
-        }
-        out.nodes.push_back(std::move(nn));
-    }
-    for (auto &d : out.sv_defs) {
-        if (d.type == operand::kind::uvar) {
-            d.idx = shift(d.idx);
-        }
-    }
-    for (auto &e : out.ev_u) {
-        e = shift(e);
-    }
-    out.n_u = p.n_u + m;
-    return true;
-}
-
-namespace
-{
-
-std::string make_plan_impl(const taylor_program &p, std::uint32_t order, cluster_plan &pl,
-                           const cluster_detail::plan_limits &lim);
-
-} // namespace
-
-// Clusters which differ by an *elided unit factor*. model::nbody() scales r^-3 by G m_j before the three products of a
-// pair; when that factor is exactly 1 (unit masses in G = 1 units) the scaling node is not there and the products read the
-// pow directly, while the pairs of the same system with another factor (-G m_i = -1 towards a test particle, other
-// masses) keep it: the pair clusters are then neither isomorphic nor sub-shapes of each other. This pass restores the
-// missing member in the INTERNAL program (the user-visible decomposition is untouched): every pow node which is read by
-// products with a variable factor but by no scaling product `c * pow`, in a program where other pow nodes are read
-// through such a scaling, gets `s = 1.0 * pow` right behind it, and its product readers read s (x * 1.0 is exact: no
-// value changes). Returns false if there is nothing of that kind.
-bool insert_unit_scalings(const taylor_program &p, taylor_program &out)
-{
-    const auto n_eq = p.n_eq;
-    constexpr auto none = std::numeric_limits<std::uint32_t>::max();
-    std::vector<char> is_pow(p.n_u, 0), scaled(p.n_u, 0), direct(p.n_u, 0);
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        const auto &n = p.nodes[u - n_eq];
-        is_pow[u] = (n.kind == func_kind::pow && n.args.size() == 2u && is_var(n.args[0])) ? 1 : 0;
-    }
-    for (const auto &n : p.nodes) {
-        if (n.kind != func_kind::prod || n.args.size() != 2u) {
-            continue;
-        }
-        for (std::size_t a = 0; a < 2u; ++a) {
-            const auto &o = n.args[a], &other = n.args[1u - a];
-            if (is_var(o) && is_pow[o.idx] != 0) {
-                if (other.type == operand::kind::num || other.type == operand::kind::par) {
-                    scaled[o.idx] = 1;
-                } else if (is_var(other)) {
-                    direct[o.idx] = 1;
-                }
-            }
-        }
-    }
-    bool any_scaled = false, any_todo = false;
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        any_scaled = any_scaled || scaled[u] != 0;
-        any_todo = any_todo || (direct[u] != 0 && scaled[u] == 0);
-    }
-    if (!any_scaled || !any_todo) {
-        return false;
-    }
-    // New index of every old u variable: one slot is inserted behind each pow node to be scaled.
-    std::vector<std::uint32_t> new_idx(p.n_u, none), scal_idx(p.n_u, none);
-    std::uint32_t next = n_eq;
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        new_idx[i] = i;
-    }
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        new_idx[u] = next++;
-        if (direct[u] != 0 && scaled[u] == 0) {
-            scal_idx[u] = next++;
-        }
-    }
-    out = p;
-    out.nodes.clear();
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        auto nn = p.nodes[u - n_eq];
-        const bool var_prod = nn.kind == func_kind::prod && nn.args.size() == 2u && is_var(nn.args[0]) && is_var(nn.args[1]);
-        for (auto &o : nn.args) {
-            if (o.type == operand::kind::uvar) {
-                // (Only the products with a variable factor are rewired: other readers of the pow keep reading it.)
-                o.idx = (var_prod && scal_idx[o.idx] != none) ? scal_idx[o.idx] : new_idx[o.idx];
-            }
-        }
-        for (auto &d : nn.deps) {
-            d = new_idx[d];
-        }
-        out.nodes.push_back(std::move(nn));
-        if (scal_idx[u] != none) {
-            dc_node sc;
-            sc.kind = func_kind::prod;
-            operand one;
-            one.type = operand::kind::num;
-            one.value = 1.;
-            operand src;
-            src.type = operand::kind::uvar;
-            src.idx = new_idx[u];
-            sc.args = {one, src};
-            out.nodes.push_back(std::move(sc));
-        }
-    }
-    for (auto &d : out.sv_defs) {
-        if (d.type == operand::kind::uvar) {
-            d.idx = new_idx[d.idx];
-        }
-    }
-    for (auto &e : out.ev_u) {
-        e = new_idx[e];
-    }
-    out.n_u = next;
-    return true;
-}
-
-// Accelerations as flat sums of scaled pair products. model::nbody() writes the acceleration of a body as whatever its
-// masses let the expression system fold: with distinct numerical masses a plain sum over the partners, each term a product
-// d * (G m r^-3) or its "reaction" c * (d * (G m r^-3)) - the shape the one-lane-per-pair kernel is built for -, but with
-// EQUAL masses the reactions become negations and the sums of a body turn into sum / sub / -1 * sum trees whose kind differs
-// from body to body (default masses: src/model/nbody.cpp:95-130, the grouped branch), and with REPEATED masses the reactions
-// are glue nodes of their own in front of the sums: two glue levels. The lanes of a glue round execute one instruction
-// stream, so those systems fell to the lane-pair / first-generation kernels (1.5e8 ... 5.5e8 system-steps/s against 7.9e8).
-// This pass rewrites the INTERNAL program (the user-visible decomposition is untouched): the definition of every state
-// variable which is a linear tree - sum, sub, prod(number, .) - over products of two variables is flattened into
-// sum_j c_j p_j; every product keeps the appearance with coefficient +1 as the direct one, the other one becomes a node
-// prod(c, p) right behind it (the reaction), and the acceleration becomes ONE sum node over its terms in the order of the
-// flattened tree. The result has the shape of the distinct-mass decomposition. NOTE: the additions of an acceleration are
-// re-associated (one pairwise sum over all the terms instead of the tree of the expression) and nested constant factors are
-// multiplied on the host: the jets of the rewritten program agree with the decomposition to rounding, not bit for bit -
-// the one rewrite of this family with that property (tests: 1e3 eps on the jets of the internal program).
-// Returns false if the program does not have that form or nothing would change.
-bool linearise_accelerations(const taylor_program &p, taylor_program &out)
-{
-    const auto n_eq = p.n_eq;
-    constexpr auto none = std::numeric_limits<std::uint32_t>::max();
-    if (!p.ev_u.empty() || p.n_par != 0u) {
-        return false;
-    }
-    const auto node_of = [&](std::uint32_t u) -> const dc_node & { return p.nodes[u - n_eq]; };
-    const auto is_num = [](const operand &o) { return o.type == operand::kind::num; };
-    // Linear glue: sum over variables, sub of two variables, prod(number, variable).
-    const auto linear = [&](std::uint32_t u) {
-        if (u < n_eq) {
-            return false;
-        }
-        const auto &n = node_of(u);
-        if (!n.deps.empty()) {
-            return false;
-        }
-        if (n.kind == func_kind::sum) {
-            return !n.args.empty() && std::all_of(n.args.begin(), n.args.end(), [](const operand &o) { return is_var(o); });
-        }
-        if (n.kind == func_kind::sub) {
-            return n.args.size() == 2u && is_var(n.args[0]) && is_var(n.args[1]);
-        }
-        return n.kind == func_kind::prod && n.args.size() == 2u && is_num(n.args[0]) && is_var(n.args[1]);
-    };
-    const auto leaf_ok = [&](std::uint32_t u) {
-        if (u < n_eq) {
-            return false;
-        }
-        const auto &n = node_of(u);
-        return n.kind == func_kind::prod && n.args.size() == 2u && is_var(n.args[0]) && is_var(n.args[1]) && n.deps.empty();
-    };
-    // Flattened definitions.
-    struct term {
-        double c;
-        std::uint32_t leaf;
-    };
-    std::vector<std::vector<term>> flat(n_eq);
-    std::vector<char> removed(p.n_u, 0);
-    bool ok = true, any_tree = false;
-    const std::function<void(std::uint32_t, double, std::vector<term> &)> walk = [&](std::uint32_t u, double c, std::vector<term> &dst) {
-        if (!ok) {
-            return;
-        }
-        if (linear(u)) {
-            removed[u] = 1;
-            const auto &n = node_of(u);
-            if (n.kind == func_kind::sum) {
-                for (const auto &o : n.args) {
-                    walk(o.idx, c, dst);
-                }
-            } else if (n.kind == func_kind::sub) {
-                walk(n.args[0].idx, c, dst);
-                walk(n.args[1].idx, -c, dst);
-            } else {
-                walk(n.args[1].idx, c * n.args[0].value, dst);
-            }
-            return;
-        }
-        if (!leaf_ok(u)) {
-            ok = false;
-            return;
-        }
-        dst.push_back({c, u});
-    };
-    std::vector<std::uint32_t> acc_vars;
-    for (std::uint32_t i = 0; i < n_eq && ok; ++i) {
-        const auto &d = p.sv_defs[i];
-        if (d.type != operand::kind::uvar) {
-            return false;
-        }
-        if (d.idx < n_eq) {
-            continue; // (x' = v)
-        }
-        walk(d.idx, 1., flat[i]);
-        acc_vars.push_back(i);
-        const auto &root = node_of(d.idx);
-        // (Already one sum over leaves and reactions: nothing to do for this variable.)
-        any_tree = any_tree || !(root.kind == func_kind::sum && std::all_of(root.args.begin(), root.args.end(), [&](const operand &o) {
-                                     return leaf_ok(o.idx);
-                                 }));
-    }
-    if (!ok || acc_vars.size() < 2u || !any_tree) {
-        return false;
-    }
-    const auto n_terms = flat[acc_vars[0]].size();
-    if (n_terms < 2u) {
-        return false;
-    }
-    // Appearances of every leaf: at most two, one of them with coefficient +1 (the direct product).
-    std::map<std::uint32_t, std::vector<std::pair<std::uint32_t, double>>> app;
-    for (const auto i : acc_vars) {
-        if (flat[i].size() != n_terms) {
-            return false;
-        }
-        for (const auto &t : flat[i]) {
-            if (!std::isfinite(t.c) || t.c == 0.) {
-                return false;
-            }
-            app[t.leaf].emplace_back(i, t.c);
-        }
-    }
-    std::map<std::pair<std::uint32_t, std::uint32_t>, bool> is_reaction; // (variable, leaf) -> reads the reaction node
-    std::map<std::uint32_t, double> rx_coef;                            // leaf -> coefficient of its reaction node
-    for (const auto &[leaf, v] : app) {
-        if (v.size() > 2u || (v.size() == 2u && v[0].first == v[1].first)) {
-            return false;
-        }
-        std::size_t direct = v.size();
-        for (std::size_t a = 0; a < v.size(); ++a) {
-            if (v[a].second == 1.) {
-                direct = a;
-                break;
-            }
-        }
-        if (direct == v.size()) {
-            return false;
-        }
-        for (std::size_t a = 0; a < v.size(); ++a) {
-            is_reaction[{v[a].first, leaf}] = a != direct;
-            if (a != direct) {
-                rx_coef[leaf] = v[a].second;
-            }
-        }
-    }
-    // The removed linear nodes must have no reader outside the trees.
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (removed[u] != 0) {
-            continue;
-        }
-        for (const auto &o : node_of(u).args) {
-            if (is_var(o) && removed[o.idx] != 0) {
-                return false;
-            }
-        }
-        for (const auto dd : node_of(u).deps) {
-            if (removed[dd] != 0) {
-                return false;
-            }
-        }
-    }
-    // New numbering: the kept nodes in their order, a reaction node right behind its product, the sums at the end.
-    std::vector<std::uint32_t> new_idx(p.n_u, none), rx_idx(p.n_u, none);
-    std::uint32_t next = n_eq;
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        new_idx[i] = i;
-    }
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (removed[u] != 0) {
-            continue;
-        }
-        new_idx[u] = next++;
-        if (rx_coef.count(u) != 0u) {
-            rx_idx[u] = next++;
-        }
-    }
-    out = p;
-    out.nodes.clear();
-    const auto uvar = [](std::uint32_t idx) {
-        operand o;
-        o.type = operand::kind::uvar;
-        o.idx = idx;
-        return o;
-    };
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (removed[u] != 0) {
-            continue;
-        }
-        auto nn = node_of(u);
-        for (auto &o : nn.args) {
-            if (o.type == operand::kind::uvar) {
-                o.idx = new_idx[o.idx];
-            }
-        }
-        for (auto &d : nn.deps) {
-            d = new_idx[d];
-        }
-        out.nodes.push_back(std::move(nn));
-        if (rx_idx[u] != none) {
-            dc_node rx;
-            rx.kind = func_kind::prod;
-            operand c;
-            c.type = operand::kind::num;
-            c.value = rx_coef.at(u);
-            rx.args = {c, uvar(new_idx[u])};
-            out.nodes.push_back(std::move(rx));
-        }
-    }
-    for (const auto i : acc_vars) {
-        dc_node sm;
-        sm.kind = func_kind::sum;
-        for (const auto &t : flat[i]) {
-            sm.args.push_back(uvar(is_reaction.at({i, t.leaf}) ? rx_idx[t.leaf] : new_idx[t.leaf]));
-        }
-        out.nodes.push_back(std::move(sm));
-        out.sv_defs[i] = uvar(next++);
-    }
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        if (p.sv_defs[i].idx < n_eq) {
-            out.sv_defs[i] = p.sv_defs[i];
-        }
-    }
-    out.n_u = next;
-    return true;
-}
-
-// Distinct masses in a pair-interaction system: model::nbody() scales the power of the distance ONCE per pair
-// (s = c * r^-3), multiplies the coordinate differences by it and derives the reactions from those products - scaling,
-// scaled products and reactions are members of the pair's cluster. The v2 cluster phase of block mode (rolled order loop,
-// rows in registers, index-pair convolutions: the kernel of model::nbody(64) with its equal masses) wants the clusters of the
-// EQUAL-mass system: differences, sum of squares, power, three unit products. This pass rewrites the INTERNAL program (the
-// user-visible decomposition is untouched): every product d * s reads r^-3 directly, a node c * (d * r^-3) placed right
-// behind it takes its place for the sums which read it, a reaction c' * (d * s) becomes (c' c) * (d * r^-3), the scaling node
-// goes. Equal to the decomposition to rounding (c (d r^-3) against d (c r^-3); the product of the two constants is formed in
-// double precision). Returns false if nothing has that shape.
-bool externalise_scalings(const taylor_program &p, taylor_program &out)
-{
-    const auto n_eq = p.n_eq;
-    constexpr auto none = std::numeric_limits<std::uint32_t>::max();
-    if (!p.ev_u.empty() || p.n_par != 0u) {
-        return false;
-    }
-    const auto node_of = [&](std::uint32_t u) -> const dc_node & { return p.nodes[u - n_eq]; };
-    const auto is_num = [](const operand &o) { return o.type == operand::kind::num; };
-    const auto scaled = [&](const dc_node &n) {
-        return n.kind == func_kind::prod && n.args.size() == 2u && is_num(n.args[0]) && is_var(n.args[1]) && n.deps.empty();
-    };
-    const auto product = [&](const dc_node &n) {
-        return n.kind == func_kind::prod && n.args.size() == 2u && is_var(n.args[0]) && is_var(n.args[1]) && n.deps.empty();
-    };
-    std::vector<std::vector<std::uint32_t>> readers(p.n_u);
-    std::vector<char> dep_read(p.n_u, 0);
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        for (const auto &o : node_of(u).args) {
-            if (is_var(o)) {
-                readers[o.idx].push_back(u);
-            }
-        }
-        for (const auto d : node_of(u).deps) {
-            dep_read[d] = 1;
-        }
-    }
-    std::vector<char> sv_read(p.n_u, 0);
-    for (const auto &d : p.sv_defs) {
-        if (d.type == operand::kind::uvar) {
-            sv_read[d.idx] = 1;
-        }
-    }
-    // Scaling nodes: number * pow, read by products only.
-    std::map<std::uint32_t, std::pair<double, std::uint32_t>> scal;
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        const auto &n = node_of(u);
-        if (!scaled(n) || n.args[1].idx < n_eq || node_of(n.args[1].idx).kind != func_kind::pow || dep_read[u] != 0 || sv_read[u] != 0
-            || readers[u].empty()) {
-            continue;
-        }
-        if (std::all_of(readers[u].begin(), readers[u].end(), [&](std::uint32_t r) {
-                const auto &rn = node_of(r);
-                return product(rn) && (rn.args[0].idx == u) != (rn.args[1].idx == u);
-            })) {
-            scal[u] = {n.args[0].value, n.args[1].idx};
-        }
-    }
-    if (scal.empty()) {
-        return false;
-    }
-    // The products which read them; their readers: sums / differences, or reactions number * product.
-    std::map<std::uint32_t, double> scaled_prod;
-    for (const auto &[s_u, cw] : scal) {
-        for (const auto pr : readers[s_u]) {
-            if (dep_read[pr] != 0) {
-                return false;
-            }
-            for (const auto r : readers[pr]) {
-                const auto &rn = node_of(r);
-                const bool lin = rn.deps.empty() && (rn.kind == func_kind::sum || rn.kind == func_kind::sub || scaled(rn));
-                if (!lin) {
-                    return false;
-                }
-            }
-            scaled_prod[pr] = cw.first;
-        }
-    }
-    // New numbering: the scalings go, number * product right behind every product.
-    std::vector<std::uint32_t> new_idx(p.n_u, none), a_idx(p.n_u, none);
-    std::uint32_t next = n_eq;
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        new_idx[i] = i;
-    }
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (scal.count(u) != 0u) {
-            continue;
-        }
-        new_idx[u] = next++;
-        if (scaled_prod.count(u) != 0u) {
-            a_idx[u] = next++;
-        }
-    }
-    const auto uvar = [](std::uint32_t idx) {
-        operand o;
-        o.type = operand::kind::uvar;
-        o.idx = idx;
-        return o;
-    };
-    const auto num = [](double v) {
-        operand o;
-        o.type = operand::kind::num;
-        o.value = v;
-        return o;
-    };
-    // (What a reader of u reads now.)
-    const auto reads = [&](std::uint32_t u) { return a_idx[u] != none ? a_idx[u] : new_idx[u]; };
-    out = p;
-    out.nodes.clear();
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (scal.count(u) != 0u) {
-            continue;
-        }
-        auto nn = node_of(u);
-        if (scaled_prod.count(u) != 0u) {
-            for (auto &o : nn.args) {
-                o.idx = (scal.count(o.idx) != 0u) ? new_idx[scal.at(o.idx).second] : reads(o.idx);
-            }
-            out.nodes.push_back(std::move(nn));
-            dc_node a;
-            a.kind = func_kind::prod;
-            a.args = {num(scaled_prod.at(u)), uvar(new_idx[u])};
-            out.nodes.push_back(std::move(a));
-            continue;
-        }
-        if (scaled(nn) && scaled_prod.count(nn.args[1].idx) != 0u) {
-            // Reaction: (c' c) * unit product.
-            const auto pr = nn.args[1].idx;
-            nn.args = {num(nn.args[0].value * scaled_prod.at(pr)), uvar(new_idx[pr])};
-            out.nodes.push_back(std::move(nn));
-            continue;
-        }
-        for (auto &o : nn.args) {
-            if (o.type == operand::kind::uvar) {
-                o.idx = reads(o.idx);
-            }
-        }
-        for (auto &d : nn.deps) {
-            d = new_idx[d];
-        }
-        out.nodes.push_back(std::move(nn));
-    }
-    for (auto &d : out.sv_defs) {
-        if (d.type == operand::kind::uvar) {
-            d.idx = reads(d.idx);
-        }
-    }
-    out.n_u = next;
-    return true;
-}
-
-namespace
-{
-
-bool node_of_is_pow(const taylor_program &p, std::uint32_t u)
-{
-    return u >= p.n_eq && p.nodes[u - p.n_eq].kind == func_kind::pow;
-}
-
-} // namespace
-
-// Clusters which SHARE cheap linear members. The sum of squares at the head of a distance cluster reads coordinate
-// differences `c - x` / `x - c` of ONE variable and a number; when several clusters have the same difference (fixed
-// centres / mascons with a repeated coordinate) common-subexpression elimination gives them ONE node, and a coordinate
-// which is zero turns `0 - x` into `-1 * x` (model::fixed_centres with a centre at the origin, a mascon on an axis): the
-// clusters then overlap or differ in the kind of a member, and the cluster planner gives up ("clusters are not
-// isomorphic": table stepper, 100x slower). This pass rewrites the INTERNAL program (the user-visible decomposition is
-// untouched): every sum of squares all of whose arguments are such differences gets PRIVATE copies of them, placed right
-// in front of it in argument order, negations written as `-0.0 - x` (bit for bit the same value as `-1 * x`, signed
-// zeros and NaNs included: -0 - (+0) = -0, -0 - (-0) = +0); the products of the cluster (difference times the -
-// possibly scaled - power of the sum of squares) read the copies; originals which nobody reads any more are dropped.
-// A few redundant subtractions per step buy the cluster kernels. Returns false if nothing of that kind is found.
-bool privatise_cluster_inputs(const taylor_program &p, taylor_program &out)
-{
-    const auto n_eq = p.n_eq;
-    constexpr auto none = std::numeric_limits<std::uint32_t>::max();
-    const auto node_of = [&](std::uint32_t u) -> const dc_node & { return p.nodes[u - n_eq]; };
-    // Cheap linear members: sub(num, var), sub(var, num), prod(-1, var) over a STATE variable or u variable.
-    const auto is_neg = [](const dc_node &n) {
-        return n.kind == func_kind::prod && n.args.size() == 2u && n.args[0].type == operand::kind::num
-               && n.args[0].value == -1. && is_var(n.args[1]);
-    };
-    const auto is_diff = [](const dc_node &n) {
-        return n.kind == func_kind::sub && n.args.size() == 2u
-               && ((n.args[0].type == operand::kind::num && is_var(n.args[1]))
-                   || (is_var(n.args[0]) && n.args[1].type == operand::kind::num));
-    };
-    const auto cheap = [&](std::uint32_t u) { return u >= n_eq && (is_neg(node_of(u)) || is_diff(node_of(u))); };
-
-    // The heads: sums of squares over cheap members only.
-    std::vector<std::uint32_t> heads;
-    std::vector<std::uint32_t> n_head_readers(p.n_u, 0u);
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        const auto &n = node_of(u);
-        if (n.kind != func_kind::sum_sq || n.args.empty()) {
-            continue;
-        }
-        bool ok = true;
-        for (const auto &o : n.args) {
-            ok = ok && is_var(o) && cheap(o.idx);
-        }
-        if (ok) {
-            heads.push_back(u);
-            for (const auto &o : n.args) {
-                ++n_head_readers[o.idx];
-            }
-        }
-    }
-    if (heads.size() < 2u) {
-        return false;
-    }
-    bool needed = false;
-    bool any_diff = false;
-    for (const auto h : heads) {
-        for (const auto &o : node_of(h).args) {
-            needed = needed || n_head_readers[o.idx] > 1u || is_neg(node_of(o.idx));
-            any_diff = any_diff || is_diff(node_of(o.idx));
-        }
-    }
-    if (!needed || !any_diff) {
-        return false;
-    }
-    // Which head does a u variable hang off? pow(head, c) and the scalings num * pow / par * pow of it.
-    std::vector<std::uint32_t> head_of(p.n_u, none);
-    for (const auto h : heads) {
-        head_of[h] = h;
-    }
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        const auto &n = node_of(u);
-        if (n.kind == func_kind::pow && n.args.size() == 2u && is_var(n.args[0]) && head_of[n.args[0].idx] != none) {
-            head_of[u] = head_of[n.args[0].idx];
-        } else if (n.kind == func_kind::prod && n.args.size() == 2u && !is_var(n.args[0]) && is_var(n.args[1])
-                   && node_of_is_pow(p, n.args[1].idx) && head_of[n.args[1].idx] != none) {
-            head_of[u] = head_of[n.args[1].idx];
-        }
-    }
-    // Private copies: copy_idx[(head, position)] in the new numbering; readers: the head itself and the products
-    // cheap * (pow chain of the head).
-    struct rewire {
-        std::uint32_t node, arg, head, pos;
-    };
-    std::vector<rewire> rw;
-    std::vector<std::uint32_t> other_readers(p.n_u, 0u);
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        const auto &n = node_of(u);
-        if (head_of[u] == u) {
-            continue; // (a head: handled below)
-        }
-        for (std::size_t a = 0; a < n.args.size(); ++a) {
-            const auto &o = n.args[a];
-            if (!is_var(o) || !cheap(o.idx) || n_head_readers[o.idx] == 0u) {
-                continue;
-            }
-            bool done = false;
-            if (n.kind == func_kind::prod && n.args.size() == 2u && is_var(n.args[1u - a])) {
-                const auto h = head_of[n.args[1u - a].idx];
-                if (h != none) {
-                    const auto &ha = node_of(h).args;
-                    for (std::uint32_t q = 0; q < ha.size(); ++q) {
-                        if (ha[q].idx == o.idx) {
-                            rw.push_back({u, static_cast<std::uint32_t>(a), h, q});
-                            done = true;
-                            break;
-                        }
-                    }
-                }
-            }
-            if (!done) {
-                ++other_readers[o.idx];
-            }
-        }
-    }
-    for (const auto &d : p.sv_defs) {
-        if (d.type == operand::kind::uvar && d.idx < p.n_u) {
-            ++other_readers[d.idx];
-        }
-    }
-    for (const auto e : p.ev_u) {
-        ++other_readers[e];
-    }
-    // New numbering: the originals which keep a reader stay where they are, the copies of a head go right in front of it.
-    std::vector<std::uint32_t> new_idx(p.n_u, none);
-    std::map<std::pair<std::uint32_t, std::uint32_t>, std::uint32_t> copy_idx;
-    std::uint32_t next = n_eq;
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        new_idx[i] = i;
-    }
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (cheap(u) && n_head_readers[u] != 0u && other_readers[u] == 0u) {
-            continue; // dropped
-        }
-        if (head_of[u] == u) {
-            for (std::uint32_t q = 0; q < node_of(u).args.size(); ++q) {
-                copy_idx[{u, q}] = next++;
-            }
-        }
-        new_idx[u] = next++;
-    }
-    out = p;
-    out.nodes.clear();
-    std::map<std::pair<std::uint32_t, std::uint32_t>, std::pair<std::uint32_t, std::uint32_t>> rw_of;
-    for (const auto &r : rw) {
-        rw_of[{r.node, r.arg}] = {r.head, r.pos};
-    }
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        if (new_idx[u] == none) {
-            continue;
-        }
-        auto nn = node_of(u);
-        if (head_of[u] == u) {
-            for (std::uint32_t q = 0; q < nn.args.size(); ++q) {
-                auto c = node_of(nn.args[q].idx);
-                if (is_neg(c)) {
-                    // -1 * x -> -0.0 - x.
-                    const auto var = c.args[1];
-                    c.kind = func_kind::sub;
-                    c.args[0].type = operand::kind::num;
-                    c.args[0].value = -0.;
-                    c.args[1] = var;
-                }
-                for (auto &o : c.args) {
-                    if (o.type == operand::kind::uvar) {
-                        o.idx = new_idx[o.idx];
-                    }
-                }
-                out.nodes.push_back(std::move(c));
-                nn.args[q].idx = copy_idx[{u, q}];
-            }
-        } else {
-            for (std::size_t a = 0; a < nn.args.size(); ++a) {
-                auto &o = nn.args[a];
-                if (o.type != operand::kind::uvar) {
-                    continue;
-                }
-                const auto it = rw_of.find({u, static_cast<std::uint32_t>(a)});
-                o.idx = (it != rw_of.end()) ? copy_idx[it->second] : new_idx[o.idx];
-            }
-        }
-        for (auto &d : nn.deps) {
-            d = new_idx[d];
-        }
-        out.nodes.push_back(std::move(nn));
-    }
-    for (auto &d : out.sv_defs) {
-        if (d.type == operand::kind::uvar) {
-            d.idx = new_idx[d.idx];
-        }
-    }
-    for (auto &e : out.ev_u) {
-        e = new_idx[e];
-    }
-    out.n_u = next;
-    return true;
-}
-
-// Clusters of different shapes. When every cluster is a *sub-shape* of the largest one (model::nbody with massless
-// bodies: the pairs with a test particle lack the three reaction products of the massive-massive pairs), the smaller
-// clusters are padded in the INTERNAL program (the user-visible decomposition is untouched, like add_state_aliases())
-// with the members they lack - same kinds and operands as in the template, results nobody reads - so that all the
-// clusters are isomorphic and the wave-cluster steppers apply instead of the table-driven one. The embedding of a
-// cluster into the template is found by backtracking over the (small) member lists: kinds, argument structure
-// (member -> member edges, consistent external inputs, structural numbers) and hidden dependencies must match.
-// Returns false if the program is not of that kind.
-bool pad_clusters(const taylor_program &p, std::uint32_t order, taylor_program &out)
-{
-    using cluster_detail::cluster_plan;
-    cluster_plan pl;
-    const auto why = make_plan_impl(p, order, pl, cluster_detail::plan_limits{});
-    if (why.rfind("clusters are not isomorphic", 0) != 0 || pl.clusters.size() < 2u) {
-        return false;
-    }
-    const auto n_eq = p.n_eq;
-    const auto nc = pl.clusters.size();
-    std::size_t tmax = 0;
-    for (std::size_t c = 1; c < nc; ++c) {
-        if (pl.clusters[c].size() > pl.clusters[tmax].size()) {
-            tmax = c;
-        }
-    }
-    const auto &T = pl.clusters[tmax];
-    std::map<std::uint32_t, std::uint32_t> tpos;
-    for (std::uint32_t q = 0; q < T.size(); ++q) {
-        tpos[T[q]] = q;
-    }
-    // (Like the cluster signatures of make_plan(): a factor -1 is an ordinary per-cluster constant.)
-    const auto structural_number = [](const dc_node &n, std::size_t a) { return n.kind == func_kind::pow && a == 1u; };
-    constexpr auto none = std::numeric_limits<std::uint32_t>::max();
-
-    // New members get provisional indices p.n_u, p.n_u + 1, ... and an anchor: the (old) u variable after which they are
-    // inserted, so that the members of a padded cluster come in the order of the template (the planner compares the
-    // clusters member by member, in ascending order of their indices).
-    std::vector<dc_node> new_nodes;
-    std::vector<std::uint32_t> anchor_of; // per new node: old u variable it follows (none: before the first node)
-    std::uint32_t next_u = p.n_u;
-    bool padded_any = false;
-    for (std::size_t c = 0; c < nc; ++c) {
-        if (c == tmax) {
-            continue;
-        }
-        const auto &S = pl.clusters[c];
-        std::map<std::uint32_t, std::uint32_t> spos;
-        for (std::uint32_t q = 0; q < S.size(); ++q) {
-            spos[S[q]] = q;
-        }
-        std::vector<std::uint32_t> f(S.size(), none);      // S position -> T position
-        std::vector<char> used(T.size(), 0);
-        std::map<std::uint32_t, std::uint32_t> ext_t2s, ext_s2t; // external inputs: T's u <-> S's u
-        std::uint64_t budget = 200000;
-        // Try to map S[i], S[i+1], ... (ascending u: the arguments of a member precede it).
-        std::function<bool(std::size_t)> rec = [&](std::size_t i) -> bool {
-            if (i == S.size()) {
-                return true;
-            }
-            if (budget-- == 0u) {
-                return false;
-            }
-            const auto &ns = p.nodes[S[i] - n_eq];
-            for (std::uint32_t q = 0; q < T.size(); ++q) {
-                const auto &nt = p.nodes[T[q] - n_eq];
-                if (used[q] != 0 || nt.kind != ns.kind || nt.args.size() != ns.args.size() || nt.deps.size() != ns.deps.size()) {
-                    continue;
-                }
-                bool ok = true;
-                std::vector<std::pair<std::uint32_t, std::uint32_t>> added; // tentative external pairs (T u, S u)
-                for (std::size_t a = 0; ok && a < ns.args.size(); ++a) {
-                    const auto &so = ns.args[a], &to = nt.args[a];
-                    if (so.type != to.type) {
-                        ok = false;
-                    } else if (is_var(so)) {
-                        const auto it_t = tpos.find(to.idx);
-                        const auto it_s = spos.find(so.idx);
-                        if ((it_t == tpos.end()) != (it_s == spos.end())) {
-                            ok = false;
-                        } else if (it_t != tpos.end()) {
-                            ok = f[it_s->second] == it_t->second;
-                        } else {
-                            const auto e1 = ext_t2s.find(to.idx);
-                            const auto e2 = ext_s2t.find(so.idx);
-                            if (e1 != ext_t2s.end() || e2 != ext_s2t.end()) {
-                                ok = e1 != ext_t2s.end() && e2 != ext_s2t.end() && e1->second == so.idx && e2->second == to.idx;
-                            } else {
-                                ext_t2s[to.idx] = so.idx;
-                                ext_s2t[so.idx] = to.idx;
-                                added.emplace_back(to.idx, so.idx);
-                            }
-                        }
-                    } else if (so.type == operand::kind::num) {
-                        if (structural_number(nt, a) || structural_number(ns, a)) {
-                            ok = so.value == to.value;
-                        }
-                    }
-                }
-                for (std::size_t d = 0; ok && d < ns.deps.size(); ++d) {
-                    const auto it_t = tpos.find(nt.deps[d]);
-                    const auto it_s = spos.find(ns.deps[d]);
-                    ok = it_t != tpos.end() && it_s != spos.end() && f[it_s->second] == it_t->second;
-                }
-                if (ok) {
-                    f[i] = q;
-                    used[q] = 1;
-                    if (rec(i + 1u)) {
-                        return true;
-                    }
-                    used[q] = 0;
-                    f[i] = none;
-                }
-                for (const auto &[tu, su] : added) {
-                    ext_t2s.erase(tu);
-                    ext_s2t.erase(su);
-                }
-            }
-            return false;
-        };
-        if (!rec(0)) {
-            return false;
-        }
-        // Members of the template the cluster lacks: appended to the program, in template order.
-        std::vector<std::uint32_t> inv(T.size(), none); // T position -> u variable of this cluster
-        for (std::size_t i = 0; i < S.size(); ++i) {
-            inv[f[i]] = S[i];
-        }
-        std::uint32_t fallback_ext = none;
-        for (const auto &[su, tu] : ext_s2t) {
-            (void)tu;
-            fallback_ext = su;
-            break;
-        }
-        for (std::uint32_t q = 0; q < T.size(); ++q) {
-            if (inv[q] != none) {
-                continue;
-            }
-            auto nn = p.nodes[T[q] - n_eq];
-            for (auto &o : nn.args) {
-                if (o.type != operand::kind::uvar) {
-                    continue;
-                }
-                if (const auto it = tpos.find(o.idx); it != tpos.end()) {
-                    if (inv[it->second] == none) {
-                        return false; // (template order is topological: cannot happen)
-                    }
-                    o.idx = inv[it->second];
-                } else if (const auto e = ext_t2s.find(o.idx); e != ext_t2s.end()) {
-                    o.idx = e->second;
-                } else if (fallback_ext != none) {
-                    o.idx = fallback_ext;
-                } else {
-                    return false;
-                }
-            }
-            for (auto &d : nn.deps) {
-                const auto it = tpos.find(d);
-                if (it == tpos.end() || inv[it->second] == none) {
-                    return false;
-                }
-                d = inv[it->second];
-            }
-            // Anchor: the member at the previous template position (or its anchor, if that one is new as well).
-            std::uint32_t anc = none;
-            if (q > 0u) {
-                const auto prev = inv[q - 1u];
-                anc = prev < p.n_u ? prev : anchor_of[prev - p.n_u];
-            } else if (!S.empty() && S[0] > n_eq) {
-                anc = S[0] - 1u;
-            }
-            new_nodes.push_back(std::move(nn));
-            anchor_of.push_back(anc);
-            inv[q] = next_u++;
-            padded_any = true;
-        }
-    }
-    if (!padded_any) {
-        return false;
-    }
-    // Rebuild the program with the new members at their places; remap every u-variable index.
-    std::vector<std::uint32_t> new_idx(next_u, none);
-    std::vector<const dc_node *> order_nodes;
-    std::vector<std::uint32_t> order_old; // provisional / old index of the nodes in the new order
-    const auto place_after = [&](std::uint32_t anc) {
-        for (std::size_t j = 0; j < new_nodes.size(); ++j) {
-            if (anchor_of[j] == anc) {
-                order_nodes.push_back(&new_nodes[j]);
-                order_old.push_back(p.n_u + static_cast<std::uint32_t>(j));
-            }
-        }
-    };
-    place_after(none);
-    for (std::uint32_t u = n_eq; u < p.n_u; ++u) {
-        order_nodes.push_back(&p.nodes[u - n_eq]);
-        order_old.push_back(u);
-        place_after(u);
-    }
-    // NOTE: members anchored at a state variable (a cluster whose first member directly follows the state) land first.
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        new_idx[i] = i;
-    }
-    for (std::size_t j = 0; j < order_old.size(); ++j) {
-        new_idx[order_old[j]] = n_eq + static_cast<std::uint32_t>(j);
-    }
-    for (std::size_t j = 0; j < new_nodes.size(); ++j) {
-        if (new_idx[p.n_u + j] == none) {
-            return false; // anchored at something which is not a node (cannot happen for anchors >= n_eq)
-        }
-    }
-    out = p;
-    out.nodes.clear();
-    for (const auto *np : order_nodes) {
-        auto nn = *np;
-        for (auto &o : nn.args) {
-            if (o.type == operand::kind::uvar) {
-                o.idx = new_idx[o.idx];
-            }
-        }
-        for (auto &d : nn.deps) {
-            d = new_idx[d];
-        }
-        out.nodes.push_back(std::move(nn));
-    }
-    for (auto &d : out.sv_defs) {
-        if (d.type == operand::kind::uvar) {
-            d.idx = new_idx[d.idx];
-        }
-    }
-    for (auto &e : out.ev_u) {
-        e = new_idx[e];
-    }
-    out.n_u = next_u;
-    // Arguments must precede their users.
-    for (std::size_t j = 0; j < out.nodes.size(); ++j) {
-        for (const auto &o : out.nodes[j].args) {
-            if (o.type == operand::kind::uvar && o.idx >= n_eq + j) {
-                return false;
-            }
-        }
-    }
-    return true;
-}
-
-std::string cluster_detail::make_plan(const taylor_program &p, std::uint32_t order, cluster_plan &pl,
-                                      const plan_limits &lim)
-{
-    auto why = make_plan_impl(p, order, pl, lim);
-    if (lim.absorb_linear && why.rfind("clusters are not isomorphic", 0) == 0) {
-        // E.g. model::np1body with unit masses: the heliocentric clusters feed scaling products of their own, the pair
-        // clusters do not. Without the absorption those products are glue and the clusters are isomorphic again.
-        auto lim2 = lim;
-        lim2.absorb_linear = false;
-        cluster_plan pl2;
-        const auto why2 = make_plan_impl(p, order, pl2, lim2);
-        if (why2.empty()) {
-            pl = std::move(pl2);
-            return why2;
-        }
-    }
-    return why;
-}
-
-namespace
-{
-
-// Second half of make_plan_impl() for multi-class plans: the clusters are grouped into classes of identical shape and
-// dependency level; constants, exported members and histories are per class; LDS slots and glue groups as usual.
-std::string finish_multi_class_plan(const taylor_program &p, std::uint32_t order, cluster_plan &pl, const std::vector<char> *cu,
-                                    const std::vector<std::uint32_t> &clvl, const std::vector<std::string> &sigs,
-                                    const std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> &num_pos,
-                                    const std::vector<std::vector<double>> &num_val, const std::vector<char> &exported)
-{
-    using cluster_detail::cluster_class;
-    using cluster_detail::glue_group;
-    const auto n_eq = p.n_eq, n_u = p.n_u;
-    const auto nc = pl.clusters.size();
-    // Classes, in the order of their first cluster.
-    std::map<std::pair<std::uint32_t, std::string>, std::size_t> cidx;
-    for (std::size_t c = 0; c < nc; ++c) {
-        const auto key = std::make_pair(clvl[c], sigs[c]);
-        auto it = cidx.find(key);
-        if (it == cidx.end()) {
-            it = cidx.emplace(key, pl.classes.size()).first;
-            pl.classes.emplace_back();
-            pl.classes.back().level = clvl[c];
-        }
-        pl.classes[it->second].members.push_back(static_cast<std::uint32_t>(c));
-    }
-    std::size_t max_members = 0, stored_total = 0;
-    for (auto &cls : pl.classes) {
-        const auto c0 = cls.members[0];
-        const auto &t0 = pl.clusters[c0];
-        max_members = std::max(max_members, cls.members.size());
-        // Constants: literal if identical across the class, otherwise a per-lane table entry.
-        cls.cst_val.assign(cls.members.size(), {});
-        for (std::size_t j = 0; j < num_pos[c0].size(); ++j) {
-            bool same = true;
-            for (const auto c : cls.members) {
-                const auto a = num_val[c][j], b = num_val[c0][j];
-                if (!(a == b || (std::isnan(a) && std::isnan(b))) || std::signbit(a) != std::signbit(b)) {
-                    same = false;
-                }
-            }
-            if (!same) {
-                cls.cst_pos.push_back(num_pos[c0][j]);
-                for (std::size_t m = 0; m < cls.members.size(); ++m) {
-                    cls.cst_val[m].push_back(num_val[cls.members[m]][j]);
-                }
-            }
-        }
-        for (std::uint32_t q = 0; q < t0.size(); ++q) {
-            bool any = false;
-            for (const auto c : cls.members) {
-                any = any || exported[pl.clusters[c][q]] != 0;
-            }
-            if (any) {
-                cls.out_pos.push_back(q);
-            }
-        }
-        // Histories of the template.
-        std::set<std::uint32_t> stored;
-        for (const auto u : t0) {
-            const auto &n = p.nodes[u - n_eq];
-            const auto hs = history_operands(n, cu);
-            for (const auto h : hs) {
-                stored.insert(h);
-            }
-            switch (n.kind) {
-                case func_kind::pow:
-                case func_kind::div:
-                case func_kind::sin:
-                case func_kind::cos:
-                case func_kind::exp:
-                case func_kind::log:
-                case func_kind::sigmoid:
-                case func_kind::asin:
-                case func_kind::acos:
-                case func_kind::atan:
-                case func_kind::asinh:
-                case func_kind::acosh:
-                case func_kind::atanh:
-                    if (!hs.empty()) {
-                        stored.insert(u);
-                    }
-                    break;
-                default:
-                    break;
-            }
-        }
-        for (std::uint32_t q = 0; q < t0.size(); ++q) {
-            if (stored.count(t0[q]) != 0u) {
-                cls.stored_pos.push_back(q);
-            }
-        }
-        stored_total += stored.size();
-    }
-    if (max_members > 64u) {
-        return "more than 64 clusters in a class";
-    }
-    // (Every lane carries the histories of one cluster of EVERY class.)
-    if (stored_total * order * 2u > 420u) {
-        return "the jets of the cluster classes do not fit in the register file (" + std::to_string(stored_total) + " histories)";
-    }
-    pl.L = 2;
-    while (pl.L < max_members && pl.L < 64u) {
-        pl.L *= 2u;
-    }
-    pl.spw = 64u / pl.L;
-    pl.max_level = *std::max_element(pl.lvl.begin(), pl.lvl.end());
-
-    // LDS slots: state variables, exported cluster members (output-major inside a class), glue nodes.
-    pl.slot_of.assign(n_u, -1);
-    std::uint32_t ns = 0;
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        pl.slot_of[i] = static_cast<int>(ns++);
-    }
-    for (const auto &cls : pl.classes) {
-        for (const auto q : cls.out_pos) {
-            for (const auto c : cls.members) {
-                pl.slot_of[pl.clusters[c][q]] = static_cast<int>(ns++);
-            }
-        }
-    }
-    for (std::uint32_t u = n_eq; u < n_u; ++u) {
-        if (pl.cluster_of[u] == -1) {
-            pl.slot_of[u] = static_cast<int>(ns++);
-        }
-    }
-    pl.n_slots = ns;
-
-    // Glue groups: per level, per shape.
-    const auto structural_number = [](const dc_node &n, std::size_t a) {
-        if (n.kind == func_kind::pow && a == 1u) {
-            return true;
-        }
-        return n.kind == func_kind::prod && a == 0u && n.args[0].type == operand::kind::num && n.args[0].value == -1.;
-    };
-    std::map<std::pair<std::uint32_t, std::string>, std::size_t> gidx;
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        const auto u = n_eq + i;
-        if (pl.cluster_of[u] != -1) {
-            continue;
-        }
-        const auto &n = p.nodes[i];
-        std::ostringstream key;
-        key << func_kind_name(n.kind);
-        for (std::size_t a = 0; a < n.args.size(); ++a) {
-            const auto &o = n.args[a];
-            if (is_var(o)) {
-                key << ((cu != nullptr && n.kind == func_kind::prod && (*cu)[o.idx] != 0) ? "k" : "v");
-            } else if (o.type == operand::kind::par) {
-                key << "p" << o.idx;
-            } else if (structural_number(n, a)) {
-                key << "n" << fp_literal(o.value);
-            } else {
-                key << "c";
-            }
-        }
-        const auto k = std::make_pair(pl.lvl[u], key.str());
-        auto it = gidx.find(k);
-        if (it == gidx.end()) {
-            it = gidx.emplace(k, pl.groups.size()).first;
-            pl.groups.emplace_back();
-            pl.groups.back().level = pl.lvl[u];
-            pl.groups.back().key = key.str();
-        }
-        pl.groups[it->second].nodes.push_back(u);
-    }
-    std::stable_sort(pl.groups.begin(), pl.groups.end(),
-                     [](const glue_group &a, const glue_group &b) { return a.level < b.level; });
-    return {};
-}
-
-std::string make_plan_impl(const taylor_program &p, std::uint32_t order, cluster_plan &pl,
-                           const cluster_detail::plan_limits &lim)
-{
-    using cluster_detail::glue_group;
-    const auto n_eq = p.n_eq, n_u = p.n_u;
-    for (const auto &n : p.nodes) {
-        if (n.kind == func_kind::custom) {
-            return "functions defined through node rules run on the straight-line and interpreted steppers";
-        }
-    }
-    pl.n_eq = n_eq;
-    pl.n_u = n_u;
-    // Constant u variables: only the wave-cluster generators (ssa_emitter-based) evaluate products with a constant
-    // factor linearly; the block planner keeps the general treatment.
-    const auto cu_store = constant_uvars(p);
-    const std::vector<char> *cu = lim.jets_in_registers ? &cu_store : nullptr;
-
-    // 1. History edges -> clusters.
-    union_find uf(n_u);
-    std::vector<char> in_h(n_u, 0);
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        if (p.nodes[i].kind >= func_kind::atan2) {
-            // atan2, kepE and the piecewise functions: served by the unrolled / table steppers.
-            return std::string("function served by the unrolled / table steppers: ") + func_kind_name(p.nodes[i].kind);
-        }
-        const auto u = n_eq + i;
-        const auto hs = history_operands(p.nodes[i], cu);
-        for (const auto h : hs) {
-            if (h < n_eq) {
-                return "a state variable is a history operand of a nonlinear function";
-            }
-            uf.unite(u, h);
-            in_h[u] = 1;
-            in_h[h] = 1;
-        }
-    }
-    pl.cluster_of.assign(n_u, -1);
-    std::map<std::uint32_t, int> root_to_cluster;
-    for (std::uint32_t u = n_eq; u < n_u; ++u) {
-        if (in_h[u] == 0) {
-            continue;
-        }
-        const auto r = uf.find(u);
-        auto it = root_to_cluster.find(r);
-        if (it == root_to_cluster.end()) {
-            it = root_to_cluster.emplace(r, static_cast<int>(pl.clusters.size())).first;
-            pl.clusters.emplace_back();
-        }
-        pl.cluster_of[u] = it->second;
-    }
-    if (pl.clusters.size() < 2u) {
-        return "fewer than 2 clusters";
-    }
-    if (pl.clusters.size() > lim.max_clusters && !lim.multi_class) {
-        return "more than " + std::to_string(lim.max_clusters) + " clusters";
-    }
-
-    // 2. Absorb single-source linear nodes into their source cluster.
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        const auto u = n_eq + i;
-        if (!lim.absorb_linear || pl.cluster_of[u] != -1 || !is_glue_kind(p.nodes[i], cu)) {
-            continue;
-        }
-        int src = -2;
-        for (const auto &o : p.nodes[i].args) {
-            if (!is_var(o)) {
-                continue;
-            }
-            const auto c = o.idx < n_eq ? -1 : pl.cluster_of[o.idx];
-            if (src == -2) {
-                src = c;
-            } else if (src != c) {
-                src = -1;
-            }
-        }
-        if (src >= 0) {
-            pl.cluster_of[u] = src;
-        }
-    }
-    for (std::uint32_t u = n_eq; u < n_u; ++u) {
-        if (pl.cluster_of[u] >= 0) {
-            pl.clusters[static_cast<std::size_t>(pl.cluster_of[u])].push_back(u);
-        }
-    }
-
-    // Glue nodes must be of a kind evaluable from current-order values.
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        if (pl.cluster_of[n_eq + i] == -1 && !is_glue_kind(p.nodes[i], cu)) {
-            return std::string("unsupported glue node kind: ") + func_kind_name(p.nodes[i].kind);
-        }
-    }
-
-    // 3. Levels on the contracted graph. lvl of state variables = 0; a cluster runs as a unit.
-    //    First pass: levels of glue nodes and provisional cluster levels, iterated to a fixed point
-    //    (the graph is a DAG unless a cluster depends on itself through glue).
-    const auto nc = pl.clusters.size();
-    std::vector<std::uint32_t> clvl(nc, 1u);
-    pl.lvl.assign(n_u, 0u);
-    bool changed = true;
-    std::uint32_t iters = 0;
-    while (changed) {
-        changed = false;
-        if (++iters > n_u + 2u) {
-            return "cyclic dependency between a cluster and glue nodes";
-        }
-        for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-            const auto u = n_eq + i;
-            const auto c = pl.cluster_of[u];
-            std::uint32_t need = 1;
-            for (const auto &o : p.nodes[i].args) {
-                if (!is_var(o)) {
-                    continue;
-                }
-                const auto oc = o.idx < n_eq ? -1 : pl.cluster_of[o.idx];
-                if (c >= 0 && oc == c) {
-                    continue;
-                }
-                const auto ol = (oc >= 0) ? clvl[static_cast<std::size_t>(oc)] : pl.lvl[o.idx];
-                need = std::max(need, ol + 1u);
-            }
-            if (c >= 0) {
-                if (need > clvl[static_cast<std::size_t>(c)]) {
-                    clvl[static_cast<std::size_t>(c)] = need;
-                    changed = true;
-                }
-            } else if (need != pl.lvl[u]) {
-                pl.lvl[u] = need;
-                changed = true;
-            }
-        }
-    }
-    for (std::size_t c = 1; c < nc && !lim.multi_class; ++c) {
-        if (clvl[c] != clvl[0]) {
-            return "clusters at different dependency levels";
-        }
-    }
-    pl.cluster_level = clvl[0];
-    for (std::uint32_t u = n_eq; u < n_u; ++u) {
-        if (pl.cluster_of[u] >= 0) {
-            pl.lvl[u] = clvl[static_cast<std::size_t>(pl.cluster_of[u])];
-        }
-    }
-    pl.max_level = *std::max_element(pl.lvl.begin(), pl.lvl.end());
-
-    // 4. Which cluster members are read from outside their cluster (glue, other clusters, sv rules)?
-    std::vector<char> exported(n_u, 0);
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        const auto c = pl.cluster_of[n_eq + i];
-        for (const auto &o : p.nodes[i].args) {
-            if (is_var(o) && o.idx >= n_eq && pl.cluster_of[o.idx] >= 0 && pl.cluster_of[o.idx] != c) {
-                exported[o.idx] = 1;
-            }
-        }
-    }
-    for (const auto &d : p.sv_defs) {
-        if (is_var(d) && d.idx >= n_eq && pl.cluster_of[d.idx] >= 0) {
-            exported[d.idx] = 1;
-        }
-    }
-
-    // 5. Isomorphism check + template-relative tables.
-    const auto &t0 = pl.clusters[0];
-    pl.ext_u.assign(nc, {});
-    pl.cst_val.assign(nc, {});
-    std::vector<std::string> sigs(nc);
-    // Numerical operands that must be identical (they select the code shape).
-    const auto structural_number = [](const dc_node &n, std::size_t a) {
-        if (n.kind == func_kind::pow && a == 1u) {
-            return true;
-        }
-        if (n.kind == func_kind::prod && a == 0u && n.args[0].type == operand::kind::num && n.args[0].value == -1.) {
-            return true;
-        }
-        return false;
-    };
-    std::vector<std::vector<std::pair<std::uint32_t, std::uint32_t>>> num_pos(nc), par_pos(nc);
-    std::vector<std::vector<double>> num_val(nc);
-    std::vector<std::vector<std::uint32_t>> par_idx(nc);
-    for (std::size_t c = 0; c < nc; ++c) {
-        const auto &mem = pl.clusters[c];
-        if (mem.size() != t0.size() && !lim.multi_class) {
-            return "clusters are not isomorphic (different sizes)";
-        }
-        std::map<std::uint32_t, std::uint32_t> pos_of, ext_of;
-        for (std::uint32_t q = 0; q < mem.size(); ++q) {
-            pos_of[mem[q]] = q;
-        }
-        std::ostringstream sig;
-        for (std::uint32_t q = 0; q < mem.size(); ++q) {
-            const auto &n = p.nodes[mem[q] - n_eq];
-            // NOTE: whether a member is read from outside is not part of the shape: a position is exported if it is in
-            // any cluster (clusters padded by pad_clusters() carry members nobody reads).
-            sig << func_kind_name(n.kind) << '(';
-            for (std::size_t a = 0; a < n.args.size(); ++a) {
-                const auto &o = n.args[a];
-                if (is_var(o)) {
-                    if (const auto it = pos_of.find(o.idx); it != pos_of.end()) {
-                        sig << 'm' << it->second;
-                    } else {
-                        auto it2 = ext_of.find(o.idx);
-                        if (it2 == ext_of.end()) {
-                            it2 = ext_of.emplace(o.idx, static_cast<std::uint32_t>(pl.ext_u[c].size())).first;
-                            pl.ext_u[c].push_back(o.idx);
-                        }
-                        sig << 'e' << it2->second;
-                    }
-                } else if (o.type == operand::kind::par) {
-                    // Parameters: identical index across the clusters -> plain name, otherwise a per-lane table.
-                    if (lim.generic_pars) {
-                        sig << 'P';
-                        par_pos[c].emplace_back(q, static_cast<std::uint32_t>(a));
-                        par_idx[c].push_back(o.idx);
-                    } else {
-                        sig << 'p' << o.idx;
-                    }
-                } else if (n.kind == func_kind::pow && a == 1u) {
-                    sig << 'n' << fp_literal(o.value);
-                } else {
-                    // NOTE: a factor -1 (a negation in the decomposition) is an ordinary constant here: -G m_i is -1 for a
-                    // unit mass in G = 1 units and something else for the other bodies. Identical across the clusters ->
-                    // it stays in the node (and the emitter negates); otherwise it becomes a per-lane constant and the
-                    // emitter multiplies (ssa_emitter::node() checks for an override before taking the shortcut).
-                    sig << 'c';
-                    num_pos[c].emplace_back(q, static_cast<std::uint32_t>(a));
-                    num_val[c].push_back(o.value);
-                }
-                sig << ',';
-            }
-            sig << ")[";
-            for (const auto d : n.deps) {
-                const auto it = pos_of.find(d);
-                if (it == pos_of.end()) {
-                    return "hidden dependency outside of its cluster";
-                }
-                sig << it->second << ',';
-            }
-            sig << ']';
-        }
-        sigs[c] = sig.str();
-        if (sigs[c] != sigs[0] && !lim.multi_class) {
-            return "clusters are not isomorphic";
-        }
-    }
-    if (lim.multi_class) {
-        return finish_multi_class_plan(p, order, pl, cu, clvl, sigs, num_pos, num_val, exported);
-    }
-    // Constants: literal if identical across clusters, otherwise a per-lane table entry.
-    for (std::size_t j = 0; j < num_pos[0].size(); ++j) {
-        bool same = true;
-        for (std::size_t c = 1; c < nc; ++c) {
-            const auto a = num_val[c][j], b = num_val[0][j];
-            if (!(a == b || (std::isnan(a) && std::isnan(b))) || std::signbit(a) != std::signbit(b)) {
-                same = false;
-            }
-        }
-        if (!same) {
-            pl.cst_pos.push_back(num_pos[0][j]);
-            for (std::size_t c = 0; c < nc; ++c) {
-                pl.cst_val[c].push_back(num_val[c][j]);
-            }
-        }
-    }
-    pl.par_idx.assign(nc, {});
-    for (std::size_t j = 0; j < par_pos[0].size(); ++j) {
-        bool same = true;
-        for (std::size_t c = 1; c < nc; ++c) {
-            same = same && par_idx[c][j] == par_idx[0][j];
-        }
-        if (!same) {
-            pl.par_pos.push_back(par_pos[0][j]);
-            for (std::size_t c = 0; c < nc; ++c) {
-                pl.par_idx[c].push_back(par_idx[c][j]);
-            }
-        }
-    }
-    for (std::uint32_t q = 0; q < t0.size(); ++q) {
-        bool any = false;
-        for (std::size_t c = 0; c < nc; ++c) {
-            any = any || exported[pl.clusters[c][q]] != 0;
-        }
-        if (any) {
-            pl.out_pos.push_back(q);
-        }
-    }
-
-    // 6. Lane-group width.
-    pl.L = 2;
-    while (pl.L < nc && pl.L < 64u) {
-        pl.L *= 2u;
-    }
-    pl.spw = 64u / pl.L;
-
-    // Register estimate: members whose history is needed keep `order` doubles alive.
-    std::set<std::uint32_t> stored;
-    for (const auto u : t0) {
-        const auto &n = p.nodes[u - n_eq];
-        for (const auto h : history_operands(n, cu)) {
-            stored.insert(h);
-        }
-        switch (n.kind) {
-            case func_kind::pow:
-            case func_kind::div:
-            case func_kind::sin:
-            case func_kind::cos:
-            case func_kind::exp:
-            case func_kind::log:
-            case func_kind::sigmoid:
-            case func_kind::asin:
-            case func_kind::acos:
-            case func_kind::atan:
-            case func_kind::asinh:
-            case func_kind::acosh:
-            case func_kind::atanh:
-                if (!history_operands(n, cu).empty()) {
-                    stored.insert(u);
-                }
-                break;
-            default:
-                break;
-        }
-    }
-    if (lim.jets_in_registers && stored.size() * order * 2u > 420u) {
-        return "the jets of a cluster do not fit in the register file";
-    }
-    for (std::uint32_t q = 0; q < t0.size(); ++q) {
-        if (stored.count(t0[q]) != 0u) {
-            pl.stored_pos.push_back(q);
-        }
-    }
-
-    // 7. LDS slots: state variables, exported cluster members, glue nodes; then dummies.
-    pl.slot_of.assign(n_u, -1);
-    std::uint32_t ns = 0;
-    for (std::uint32_t i = 0; i < n_eq; ++i) {
-        pl.slot_of[i] = static_cast<int>(ns++);
-    }
-    // NOTE: output-major numbering: the lanes of a group (one cluster each) write *consecutive* slots for a
-    // given output, i.e. distinct LDS banks (cluster-major numbering gave a stride of n_out doubles between
-    // lanes and 2-way bank conflicts on every ds_write_b64).
-    for (const auto q : pl.out_pos) {
-        for (std::size_t c = 0; c < nc; ++c) {
-            pl.slot_of[pl.clusters[c][q]] = static_cast<int>(ns++);
-        }
-    }
-    for (std::uint32_t u = n_eq; u < n_u; ++u) {
-        if (pl.cluster_of[u] == -1) {
-            pl.slot_of[u] = static_cast<int>(ns++);
-        }
-    }
-    pl.n_slots = ns;
-
-    // 8. Glue groups: per level, per shape.
-    std::map<std::pair<std::uint32_t, std::string>, std::size_t> gidx;
-    for (std::uint32_t i = 0; i < p.nodes.size(); ++i) {
-        const auto u = n_eq + i;
-        if (pl.cluster_of[u] != -1) {
-            continue;
-        }
-        const auto &n = p.nodes[i];
-        std::ostringstream key;
-        key << func_kind_name(n.kind);
-        for (std::size_t a = 0; a < n.args.size(); ++a) {
-            const auto &o = n.args[a];
-            if (is_var(o)) {
-                // (Constant factors of products are part of the shape: they select the linear rule.)
-                key << ((cu != nullptr && n.kind == func_kind::prod && (*cu)[o.idx] != 0) ? "k" : "v");
-            } else if (o.type == operand::kind::par) {
-                // (Per-lane parameter tables in the pipelined generator; the first-generation one checks gpar_generic.)
-                if (lim.generic_pars) {
-                    key << "P";
-                    pl.glue_has_par = true;
-                } else {
-                    key << "p" << o.idx;
-                }
-            } else if (structural_number(n, a)) {
-                key << "n" << fp_literal(o.value);
-            } else {
-                key << "c";
-            }
-        }
-        const auto k = std::make_pair(pl.lvl[u], key.str());
-        auto it = gidx.find(k);
-        if (it == gidx.end()) {
-            it = gidx.emplace(k, pl.groups.size()).first;
-            pl.groups.emplace_back();
-            pl.groups.back().level = pl.lvl[u];
-            pl.groups.back().key = key.str();
-        }
-        pl.groups[it->second].nodes.push_back(u);
-    }
-    std::stable_sort(pl.groups.begin(), pl.groups.end(),
-                     [](const glue_group &a, const glue_group &b) { return a.level < b.level; });
-
-    return {};
-}
-
 } // namespace
 
 // Version 1 of the cluster kernel: separate state-variable phase, 4 LDS synchronisations per order.
 // Returns a module with an empty source (and the reason in why_not) if cluster mode is not applicable.
-emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts, std::string &why_not, bool multi_class)
+emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts, emit_refusal &why_not, bool multi_class)
 {
     using emit_detail::prelude;
     using emit_detail::rhofac;
@@ -2314,24 +582,18 @@ if (l == 0u && live) {
     return ret;
 }
 
-//V2_PLACEHOLDER
-
-// (hip_emit_cluster2.cpp: the generator object cluster2_gen of hip_emit_cluster2_gen.hpp, with hip_emit_cluster2_layout.cpp and
-// hip_emit_cluster2_orders.cpp; sets emitted_module::cluster_generation to 2, 3 or 5.)
-emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts, std::string &why_not);
-
 // Returns a module with an empty source (and the reason in why_not) if cluster mode is not applicable.
-emitted_module emit_cluster_or_empty(const taylor_program &p, const emit_options &opts, std::string &why_not)
+emitted_module emit_cluster_or_empty(const taylor_program &p, const emit_options &opts, emit_refusal &why_not)
 {
     if (!opts.dev.cluster_v1 && opts.cluster_kernel != 1) {
-        std::string why2;
+        emit_refusal why2;
         auto m = emit_cluster_v2(p, opts, why2);
         if (!m.source.empty()) {
             return m;
         }
         auto m1 = emit_cluster_v1(p, opts, why_not, false);
         if (!m1.source.empty()) {
-            m1.notes += " (pipelined cluster kernel not applicable: " + why2 + ")";
+            m1.notes += " (pipelined cluster kernel not applicable: " + why2.text + ")";
         }
         return m1;
     }
@@ -2339,7 +601,7 @@ emitted_module emit_cluster_or_empty(const taylor_program &p, const emit_options
 }
 
 // Clusters of several shapes / at several dependency levels: one section of code per class (see cluster_class).
-emitted_module emit_cluster_multi_or_empty(const taylor_program &p, const emit_options &opts, std::string &why_not)
+emitted_module emit_cluster_multi_or_empty(const taylor_program &p, const emit_options &opts, emit_refusal &why_not)
 {
     return emit_cluster_v1(p, opts, why_not, true);
 }

@@ -24,7 +24,7 @@
 namespace heyoka_amd::cluster2_detail
 {
 
-cluster2_gen::cluster2_gen(const taylor_program &p_, const emit_options &opts_, std::string &why_not_, bool allow_one_lane_,
+cluster2_gen::cluster2_gen(const taylor_program &p_, const emit_options &opts_, emit_refusal &why_not_, bool allow_one_lane_,
                            std::uint32_t min_lanes_)
     : c2_emit(p_, opts_.order), p(p_), opts(opts_), why_not(why_not_), allow_one_lane(allow_one_lane_), min_lanes(min_lanes_),
       n_eq(p_.n_eq), order(opts_.order)
@@ -2934,7 +2934,7 @@ void cluster2_gen::finish()
 namespace heyoka_amd
 {
 
-emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts, std::string &why_not)
+emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts, emit_refusal &why_not)
 {
     // The one-lane pair kernel first (pair-pattern systems without runtime parameters, not the stepper with events); if
     // its shape requirements fail or the jets of its systems do not fit in LDS, the lane-pair / pipelined kernels.
@@ -2942,7 +2942,7 @@ emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts
     // fit in its LDS - and the lane-pair kernel with the jets in global scratch which used to serve them spills 176 / 116
     // registers. More lanes per system than pairs (idle lanes replicate pair 0 and write to dummy slots, like the 16th lane
     // of the outer Solar System) bring the systems per CU down to what fits: the second and third attempts.
-    std::string why1;
+    emit_refusal why1;
     const bool try_one_lane = opts.cluster_kernel == 0 || opts.cluster_kernel == 5;
     for (const std::uint32_t min_lanes : {4u, 8u, 16u}) {
         why1.clear();
@@ -2950,7 +2950,7 @@ emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts
         const bool is_v5 = why1.empty() && at.variant == cluster2_detail::cluster2_variant::one_lane, in_lds = at.jets_in_lds;
         if (try_one_lane) {
             detail::log_message(log_level::debug, "one-lane-per-pair kernel, at least " + std::to_string(min_lanes) + " lanes per system: "
-                                              + (!why1.empty() ? why1 : (!is_v5 ? "not applicable" : (in_lds ? "accepted" : "the jets of the systems of a CU do not fit in its LDS"))));
+                                              + (!why1.empty() ? why1.text : (!is_v5 ? "not applicable" : (in_lds ? "accepted" : "the jets of the systems of a CU do not fit in its LDS"))));
         }
         if (why1.empty() && (in_lds || !is_v5)) {
             why_not.clear();

@@ -254,13 +254,13 @@ struct c2_emit {
 struct cluster2_gen : c2_variant, c2_geometry, c2_layout, c2_tables, c2_emit {
     const taylor_program &p;
     const emit_options &opts;
-    std::string &why_not;
+    emit_refusal &why_not;
     const bool allow_one_lane;
     // (min_lanes: the smallest number of lanes per system of the one-lane-per-pair kernel - see emit_cluster_v2().)
     const std::uint32_t min_lanes, n_eq, order;
     cluster2_attempt res;
 
-    cluster2_gen(const taylor_program &p, const emit_options &opts, std::string &why_not, bool allow_one_lane, std::uint32_t min_lanes);
+    cluster2_gen(const taylor_program &p, const emit_options &opts, emit_refusal &why_not, bool allow_one_lane, std::uint32_t min_lanes);
     cluster2_attempt run();
 
     // Stages, in the order run() calls them (the stage table of hip_emit_cluster2.cpp); a stage which refuses sets why_not.

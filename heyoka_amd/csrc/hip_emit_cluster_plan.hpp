@@ -1,4 +1,4 @@
-// Planning structures of the cluster code generators (see hip_emit_cluster.cpp).
+// Planning structures of the cluster code generators and the planner (hip_emit_cluster_plan.cpp).
 #pragma once
 
 #include <cstdint>
@@ -73,13 +73,21 @@ struct plan_limits {
     bool multi_class = false;
 };
 
-// Build the plan; returns an empty string on success, otherwise the reason why cluster mode is not applicable.
-std::string make_plan(const taylor_program &p, std::uint32_t order, cluster_plan &pl, const plan_limits &lim = {});
+// Build the plan; returns an empty refusal on success, otherwise the reason why cluster mode is not applicable.
+emit_refusal make_plan(const taylor_program &p, std::uint32_t order, cluster_plan &pl, const plan_limits &lim = {});
+// One attempt of make_plan(), without its second attempt with the absorption switched off: pad_clusters() reads the
+// clusters of a plan which was refused as not isomorphic, with the linear nodes absorbed.
+emit_refusal make_plan_impl(const taylor_program &p, std::uint32_t order, cluster_plan &pl, const plan_limits &lim);
 
 inline bool is_var(const operand &o)
 {
     return o.type == operand::kind::uvar;
 }
+
+// u variables whose *full history* node n needs (besides, possibly, its own).
+// NOTE: cu (optional) = constant u variables (constant_uvars()): a product with a constant factor is linear in the other
+// one and needs no history (ssa_emitter::node evaluates it as c^[0] * x^[k]). Used by the wave-cluster planner only.
+std::vector<std::uint32_t> history_operands(const dc_node &n, const std::vector<char> *cu = nullptr);
 
 // Point-mass pair clusters: {d_0, d_1, d_2 = coordinate differences (sub of two external inputs), sum_sq(d_0, d_1, d_2),
 // pow(sum_sq, alpha), [c * pow], d_i * pow, [c_i * (d_i * pow)]} - the shape the lane-pair (v3) and wave-role (v4)

@@ -1,4 +1,4 @@
-// Internal pieces shared by the HIP code generators (hip_emit.cpp, hip_emit_cluster.cpp).
+// Internal pieces shared by the HIP code generators (hip_emit*.cpp), and the entry points of the generators.
 #pragma once
 
 #include <algorithm>
@@ -20,7 +20,34 @@
 namespace heyoka_amd
 {
 enum class taylor_outcome : std::int64_t; // taylor_adaptive_batch.hpp
-}
+
+// The generators emit_hip_module() (hip_emit_select.cpp) chooses between. Those which take an emit_refusal return a module
+// with an empty source, and the reason in why_not, when they do not apply to the program.
+// hip_emit_cluster.cpp: the wave-cluster kernels, best generation first - emit_cluster_v2(), then emit_cluster_v1() - and the
+// first-generation emitter on a multi-class plan (clusters of several shapes / at several dependency levels).
+emitted_module emit_cluster_or_empty(const taylor_program &p, const emit_options &opts, emit_refusal &why_not);
+emitted_module emit_cluster_multi_or_empty(const taylor_program &p, const emit_options &opts, emit_refusal &why_not);
+// Version 1 of the cluster kernel: separate state-variable phase, 4 LDS synchronisations per order.
+emitted_module emit_cluster_v1(const taylor_program &p, const emit_options &opts, emit_refusal &why_not, bool multi_class);
+// hip_emit_cluster2.cpp: the generator object cluster2_gen of hip_emit_cluster2_gen.hpp, with hip_emit_cluster2_layout.cpp and
+// hip_emit_cluster2_orders.cpp; sets emitted_module::cluster_generation to 2, 3 or 5.
+emitted_module emit_cluster_v2(const taylor_program &p, const emit_options &opts, emit_refusal &why_not);
+// hip_emit_block.cpp: one system per workgroup, any number of clusters.
+emitted_module emit_block(const taylor_program &p, const emit_options &opts, emit_refusal &why_not);
+// hip_emit_table.cpp: the table-driven steppers - emit_staged() (hip_emit_staged.cpp: one system per workgroup, the tape in
+// LDS) when the tape of a system fits, one system per lane with the tape in HBM otherwise. Always applicable.
+emitted_module emit_table(const taylor_program &p, const emit_options &opts);
+emitted_module emit_staged(const taylor_program &p, const emit_options &opts, std::string &why_not);
+
+namespace table_detail
+{
+// hip_emit_table.cpp, shared with hip_emit_staged.cpp: the node tables and the device code of the node rules; the fused
+// callback::angle_reducer in the rolled state update of a kernel template.
+void emit_tables_and_rules(std::ostream &src, const taylor_program &p, const emit_options &opts, const std::string &pre_defs,
+                           const char *stride);
+void expand_angle_reduce_marker(std::string &text, const emit_options &opts);
+} // namespace table_detail
+} // namespace heyoka_amd
 
 namespace heyoka_amd::emit_detail
 {
@@ -61,6 +88,9 @@ double rhofac(std::uint32_t order);
 
 // Dense-output kernel.
 void emit_dout(std::ostringstream &os, const taylor_program &p, const emit_options &opts);
+
+// The straight-line stepper (hip_emit.cpp): one system per lane, fully unrolled. Always applicable.
+emitted_module emit_unrolled(const taylor_program &p, const emit_options &opts);
 
 struct ssa_emitter {
     const taylor_program &p;

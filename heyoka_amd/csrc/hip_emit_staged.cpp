@@ -42,13 +42,6 @@
 namespace heyoka_amd
 {
 
-namespace table_detail
-{
-void emit_tables_and_rules(std::ostream &src, const taylor_program &p, const emit_options &opts, const std::string &pre_defs,
-                           const char *stride);
-void expand_angle_reduce_marker(std::string &text, const emit_options &opts);
-}
-
 namespace
 {
 

@@ -905,8 +905,6 @@ void expand_angle_reduce_marker(std::string &text, const emit_options &opts)
 
 } // namespace table_detail
 
-emitted_module emit_staged(const taylor_program &, const emit_options &, std::string &why_not);
-
 emitted_module emit_table(const taylor_program &p, const emit_options &opts)
 {
     // Variant: the staged stepper (hip_emit_staged.cpp: one system per workgroup, the tape in LDS, code specialised per

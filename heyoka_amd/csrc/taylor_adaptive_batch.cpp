@@ -263,7 +263,7 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
     // The planner's verdict: which generator, and - in its notes - why the others did not apply (the reasons of every
     // planner which was tried travel in emitted_module::notes; get_codegen_info() shows the same text).
     detail::log_message(log_level::info, "Taylor batch code generation: " + get_codegen_info());
-    if (d.emitted.mode == emit_mode::table || d.emitted.notes.find("cluster mode not applicable") != std::string::npos) {
+    if (d.emitted.mode == emit_mode::table || d.emitted.cluster_fallback) {
         // A decomposition which left the on-chip steppers for a generic one is worth a line at the default level only
         // when it is big enough to matter.
         detail::log_message(d.prog.nodes.size() > 150u && !d.compact_mode && d.emitter == 0 ? log_level::warn : log_level::debug,

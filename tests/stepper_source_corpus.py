@@ -19,7 +19,8 @@ The corpus: the families of tests/test_batch_independence.py, the block-mode gen
 nbody(64) and nbody(80) - one, four and seven rounds per lane - under every switch of HEYOKA_AMD_BLOCK_OPTS and on the
 systems which keep it on its generic cluster phase, the outer Solar System under every switch of the pipelined / lane-pair / one-lane-per-pair generator
 (hip_emit_cluster2*.cpp), its stepper with events under the switches of the event path, the systems which take the retries
-of emit_hip_module() (block mode with and without the v2 cluster phase, linearised accelerations, multi-class plans), the
+of emit_hip_module() (block mode with and without the v2 cluster phase, linearised accelerations, multi-class plans; as
+select:<case> the cases of tests/test_stepper_selection.py which take its other rungs, with their own switches), the
 first wave-cluster generator with one class of clusters (cluster_kernel="v1"), and the straight-line, HBM-tape and staged
 steppers with events (HY_N_EV > 0, mode 4), without compensated summation and with a fused angle reduction."""
 import hashlib
@@ -38,6 +39,7 @@ for p_ in (os.path.join(HERE, "emu"), os.path.join(os.path.dirname(HERE), "oracl
 import heyoka_amd as hy  # noqa: E402
 from heyoka_amd import configs  # noqa: E402
 import test_batch_independence as tbi  # noqa: E402
+import test_stepper_selection as tss  # noqa: E402
 
 M, G = configs.OUTER_SS_MASSES, configs.OUTER_SS_G
 N = 64
@@ -101,6 +103,10 @@ def corpus():
     out.append(("table_hbm:high_accuracy=False", lambda: outer(emitter="table", high_accuracy=False), hbm))
     for tag, kw, env in (("unrolled", {}, None), ("staged", {"emitter": "table"}, None), ("table_hbm", {"emitter": "table"}, hbm)):
         out.append(("angle_reduce:" + tag, lambda kw=kw: fused_angle_reduce(tan(**kw), [1]), env))
+    # The rungs of the selection ladder (tests/test_stepper_selection.py) which no entry above takes.
+    for name in ("unit_scalings_padded_4", "unit_scalings_padded_6", "padded_par_masses", "private_inputs_cluster", "private_inputs_block",
+                 "no_state_aliases", "no_multi_class", "no_linearised_sums"):
+        out.append(("select:" + name, lambda name=name: tss.build(name), None))
     return out
 
 

@@ -289,7 +289,7 @@ def test_models_step_and_propagate_vs_oracle(name, pins, contract, monkeypatch):
         assert ta.hip_source_mode.startswith("cluster")
     if name in ("np1body6", "np1body8_default"):
         # State variables in history-operand position (|r_i|^2 = sum_sq(x_i, y_i, z_i)) are aliased by u variables so that
-        # the wave-cluster stepper applies (add_state_aliases(), heyoka_amd/csrc/hip_emit_cluster.cpp).
+        # the wave-cluster stepper applies (add_state_aliases(), heyoka_amd/csrc/program_rewrite.cpp).
         assert ta.hip_source_mode.startswith("cluster") and "aliased" in ta.hip_source_mode
     oi = ho.OracleIntegrator(ora(), st, n, **kw)
     n_eq = st.shape[0]
@@ -747,7 +747,7 @@ def test_externalised_scalings_of_the_internal_program(monkeypatch):
 # ------------------------------------------------------------------------------------------------------------------
 # Mixed models (round 6): nonlinear sub-DAGs of SEVERAL shapes in one system. The planner groups the clusters into
 # classes of identical shape and dependency level and runs every class as its own section of straight-line code, cluster i
-# of a class on lane i of the system's lane group (heyoka_amd/csrc/hip_emit_cluster.cpp, cluster_class); what does not fit
+# of a class on lane i of the system's lane group (heyoka_amd/csrc/hip_emit_cluster_plan.hpp, cluster_class); what does not fit
 # the register file goes to the staged table stepper (tape in LDS, hip_emit_staged.cpp). The reference runs any
 # decomposition through its segment / block tables at full SIMD rate (src/taylor_02.cpp:105-207, :983-1189).
 # ------------------------------------------------------------------------------------------------------------------
