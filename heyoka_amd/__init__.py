@@ -64,6 +64,7 @@ __all__ = [
     "step_action",
     "step_action_source",
     "grid_observables_source",
+    "event_observables_source",
     "GRID_STATISTICS",
     "ENSEMBLE_STATISTICS",
     "ensemble_accumulators",
@@ -1359,6 +1360,18 @@ def grid_observables_source(sys, observables, order=20, high_accuracy=False, sta
     return take_str(check_handle(getattr(lib, "hy_grid%s_source" % sfx)(s._h, *largs, int(order), int(bool(high_accuracy)))))
 
 
+def event_observables_source(sys, observables, order=20, high_accuracy=False, compact_tc=False, exact_division=False):
+    """HIP source of the module of the event-log observables (kernel hy_obs_rows, see ``ta.event_log_observables``) for the
+    system ``sys`` at the Taylor order ``order``: no integrator, no GPU. ``compact_tc`` / ``exact_division``: the layout of
+    the Taylor coefficients and the divisions of the stepper whose steps the rows come from (the wave-cluster steppers with
+    events store compact coefficients). ``HEYOKA_AMD_EVENT_OBS=registers|staged`` overrides how the kernel holds the samples
+    of a row (default: registers up to 64 state rows read, the staging buffer beyond)."""
+    s = _to_sys(sys.sys if isinstance(sys, var_ode_sys) else sys)
+    obs, oarr = _handle_array(list(observables))
+    return take_str(check_handle(lib.hy_event_observables_source(s._h, oarr, len(obs), int(order), int(bool(high_accuracy)),
+                                                                 int(bool(compact_tc)), int(bool(exact_division)))))
+
+
 class _angle_reducer:
     """callback::angle_reducer (include/heyoka/callback/angle_reducer.hpp): the step callback which keeps the given state
     variables in [0, 2 pi) - ``x -= 2 pi floor(x / 2 pi)`` after every step. It lives in the library: passed as
@@ -1411,9 +1424,13 @@ class event_log:
     """The rows of an integrator's event log as arrays, in the order in which the callbacks would have been invoked:
     ``system``, ``terminal`` (bool), ``idx`` (event index within its class), ``d_sgn``, ``time`` / ``time_lo`` (trigger
     time, double-length), ``root`` (offset from the beginning of the step), ``abs_der`` (|d eq/dt| at the root), ``state``
-    of shape (n, dim) or None with the states switched off. ``rows``: the raw (n, 8 [+ dim]) array."""
+    of shape (n, dim) or None with the states switched off. ``rows``: the raw (n, 8 [+ dim]) array. With event-log
+    observables set on the integrator (``n_obs`` of them): ``observables`` of shape (n, n_obs), ``state`` is None and
+    ``rows`` is (n, 8 + n_obs); ``observables`` is None otherwise."""
 
-    def __init__(self, rows, with_states):
+    def __init__(self, rows, with_states, n_obs=0):
+        self.observables = rows[:, 8:] if n_obs else None
+        with_states = with_states and not n_obs
         self.rows = rows
         self.system = rows[:, 0].astype(np.int64)
         self.terminal = rows[:, 1] == 0.0
@@ -1669,7 +1686,7 @@ class taylor_adaptive_batch:
         count = n - int(first) if count is None else int(count)
         rows = np.empty((max(count, 0), self.event_log_row_size))
         raise_for(lib.hy_tab_get_event_log(self._h, int(first), count, rows.ctypes.data))
-        return event_log(rows, self.event_log_states)
+        return event_log(rows, self.event_log_states, int(lib.hy_tab_get_event_log_n_observables(self._h)))
 
     @property
     def event_log(self):
@@ -1699,8 +1716,36 @@ class taylor_adaptive_batch:
     def event_log_states(self, on):
         raise_for(lib.hy_tab_set_event_log_states(self._h, 1 if on else 0))
 
+    @property
+    def event_log_observables(self):
+        """Event-log observables (an MI355X extension): a list of expressions over the state variables, ``par[...]``,
+        ``hy.time`` and numbers, or None. While a list is set a row of the log is ``8 + n_obs`` doubles - the header, then
+        the observables at the trigger (``event_log.observables``) in place of the state: bit for bit what
+        ``cfunc(observables, vars=state variables)`` returns for the state columns the same run logs without the list, the
+        parameters of the row's system and ``time`` = the trigger time of the row. The kernel samples only the state rows
+        the expressions read. Set or cleared (None) only while the log is empty; ``event_log_states`` keeps its value and
+        has no effect while a list is set; copies of the integrator keep the list."""
+        n = int(lib.hy_tab_get_event_log_n_observables(self._h))
+        if n == 0:
+            return None
+        return [expression._wrap(lib.hy_tab_get_event_log_observable(self._h, k)) for k in range(n)]
+
+    @event_log_observables.setter
+    def event_log_observables(self, observables):
+        if observables is None:
+            raise_for(lib.hy_tab_set_event_log_observables(self._h, None, 0))
+            return
+        # (An empty list is a list - a non-null array of length 0 -, which the library rejects; only None clears.)
+        obs, oarr = _handle_array(list(observables))
+        raise_for(lib.hy_tab_set_event_log_observables(self._h, oarr, len(obs)))
+
+    def event_log_source(self, which):
+        """HIP source of the event-log kernel 1 (hy_dout_rows) or 2 (hy_obs_rows, with observables set)."""
+        return take_str(check_handle(lib.hy_tab_event_log_source(self._h, int(which))))
+
     def event_log_code_object(self, which):
-        """gfx950 code object of the event-log kernels: 0 row headers, 1 dense output over the rows."""
+        """gfx950 code object of the event-log kernels: 0 row headers, 1 dense output over the rows, 2 the observables
+        over the rows (with ``event_log_observables`` set)."""
         data, n = ctypes.c_void_p(), ctypes.c_size_t()
         raise_for(lib.hy_tab_event_log_code_object(self._h, int(which), ctypes.byref(data), ctypes.byref(n)))
         return ctypes.string_at(data.value, n.value)

@@ -190,6 +190,11 @@ SIGNATURES = [
     ("hy_tab_set_event_log_states", c_int, [c_void_p, c_int]),
     ("hy_tab_get_event_log_states", c_int, [c_void_p]),
     ("hy_tab_event_log_code_object", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    ("hy_tab_set_event_log_observables", c_int, [c_void_p, c_void_p, ctypes.c_uint32]),
+    ("hy_tab_get_event_log_n_observables", ctypes.c_uint32, [c_void_p]),
+    ("hy_tab_get_event_log_observable", c_void_p, [c_void_p, ctypes.c_uint32]),
+    ("hy_tab_event_log_source", c_void_p, [c_void_p, c_int]),
+    ("hy_event_observables_source", c_void_p, [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_int]),
     ("hy_event_action_new", c_void_p, [c_void_p, c_void_p, c_size_t]),
     ("hy_event_action_clone", c_void_p, [c_void_p]),
     ("hy_event_action_free", None, [c_void_p]),

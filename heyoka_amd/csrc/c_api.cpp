@@ -21,6 +21,7 @@
 #include "cfunc.hpp"
 #include "decompose.hpp"
 #include "ensemble.hpp"
+#include "event_observables.hpp"
 #include "expression.hpp"
 #include "expression_diff.hpp"
 #include "hip_backend.hpp"
@@ -1396,6 +1397,78 @@ int hy_tab_event_log_code_object(hy_tab t, int which, const char **data, size_t 
         const auto &co = t->core.event_log_code_object(which);
         *data = co.data();
         *size = co.size();
+    });
+}
+// ---- event-log observables (event_observables.hpp) ----
+namespace
+{
+
+std::vector<expression> event_observables_from(const char *fn, const hy_expr *obs, uint32_t n)
+{
+    if (obs == nullptr && n != 0u) {
+        throw std::invalid_argument(std::string(fn) + "(): the array of observables is null");
+    }
+    std::vector<expression> ov;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (obs[i] == nullptr) {
+            throw std::invalid_argument(std::string(fn) + "(): the observable " + std::to_string(i) + " is a null expression");
+        }
+        ov.push_back(obs[i]->ex);
+    }
+    return ov;
+}
+
+} // namespace
+
+int hy_tab_set_event_log_observables(hy_tab t, const hy_expr *obs, uint32_t n)
+{
+    return guarded([&] {
+        // (n == 0 clears; an empty list behind a non-null pointer is a list, which the section rejects.)
+        if (n == 0u && obs == nullptr) {
+            t->core.set_event_log_observables(std::nullopt);
+        } else {
+            t->core.set_event_log_observables(event_observables_from("hy_tab_set_event_log_observables", obs, n));
+        }
+    });
+}
+uint32_t hy_tab_get_event_log_n_observables(hy_tab t)
+{
+    const auto *p = t->core.get_event_log_observables();
+    return p != nullptr ? static_cast<uint32_t>(p->size()) : 0u;
+}
+hy_expr hy_tab_get_event_log_observable(hy_tab t, uint32_t k)
+{
+    return make_expr([&] {
+        const auto *p = t->core.get_event_log_observables();
+        if (p == nullptr || k >= p->size()) {
+            throw std::out_of_range("hy_tab_get_event_log_observable(): there is no event-log observable " + std::to_string(k));
+        }
+        return (*p)[k];
+    });
+}
+char *hy_tab_event_log_source(hy_tab t, int which)
+{
+    return guarded_ptr([&] { return dup_str(t->core.event_log_source(which)); });
+}
+char *hy_event_observables_source(hy_sys sys, const hy_expr *obs, uint32_t n, uint32_t order, int high_accuracy, int compact_tc,
+                                  int exact_division)
+{
+    return guarded_ptr([&] {
+        if (sys == nullptr) {
+            throw std::invalid_argument("hy_event_observables_source(): the system handle is null");
+        }
+        // (An empty list is the section's to reject: n == 0 does not clear anything here.)
+        const auto ov = event_observables_from("hy_event_observables_source", obs, n);
+        const auto svars = detail::state_variables_of(sys->sys);
+        // (Without an integrator there is no parameter array to check against: whatever the expressions use.)
+        const auto sec = detail::make_event_obs_section(ov, svars, std::numeric_limits<std::uint32_t>::max());
+        const auto prog = make_program(taylor_decompose_sys(sys->sys), static_cast<std::uint32_t>(svars.size()));
+        emit_options eo;
+        eo.order = order;
+        eo.high_accuracy = high_accuracy != 0;
+        eo.compact_tc = compact_tc != 0;
+        eo.exact_division = exact_division != 0;
+        return dup_str(detail::make_event_log_obs_source(prog, eo, sec));
     });
 }
 // Terminal-event actions (event_action.hpp).

@@ -185,6 +185,8 @@ HY_KARGS(doutc_kargs, hy_doutc_args,
 
 // hy_dout_rows (make_event_log_dout_source()). n_rows != nullptr: the number of rows of the step is read from the device
 // (written by hy_evr_scan), n_max bounds it.
+// hy_obs_rows (make_event_log_obs_source(), event-log observables) takes the same block and reads its last two fields: the
+// parameters [n_par * N] and, staged mode only, the samples of the rows of the step [n_reads * n_max]; null for hy_dout_rows.
 HY_KARGS(drow_kargs, hy_drow_args,
     double *rows;
     const double *tc;
@@ -193,6 +195,8 @@ HY_KARGS(drow_kargs, hy_drow_args,
     u64 n_max;
     u64 N;
     unsigned row_doubles, pad;
+    const double *pars;
+    double *stage;
 )
 
 // hy_copy_arrays (make_event_detection_source()).

@@ -211,7 +211,7 @@ void tab_core::impl::launch_event_stepper(const std::vector<double> *lims)
         // (The state columns of the event log are evaluated from the coefficients of every lane with a recorded event. The
         // stepper stores them on demand only where a TERMINAL event is possible - where a step may be truncated -, which
         // does not cover the non-terminal events: with recording callbacks and the states on, every step stores them all.)
-        const bool all_now = ev_all_tc || tc_regenerated || (ev_has_rec && log_states);
+        const bool all_now = ev_all_tc || tc_regenerated || (ev_has_rec && log_fills());
         tc_regenerated = false;
         if (!all_now) {
             if (evs_state.bytes() == 0u) {
@@ -272,9 +272,26 @@ void tab_core::impl::launch_event_detection(bool device_g_eps)
 // coefficients of the step at the roots (hy_dout_rows, hip_emit.hpp).
 void tab_core::impl::log_fill_states(std::uint64_t first_row, const unsigned long long *d_n_rows, std::uint64_t n_max) const
 {
-    const drow_kargs da{d_ev_log.as<double>() + first_row * log_row_doubles(), d_tc.as<double>(), d_state.as<double>(), d_n_rows,
-                        n_max, N, log_row_doubles(), 0u};
-    drow_mod->launch("hy_dout_rows", n_max, 256, da, stream);
+    drow_kargs da{d_ev_log.as<double>() + first_row * log_row_doubles(), d_tc.as<double>(), d_state.as<double>(), d_n_rows,
+                  n_max, N, log_row_doubles(), 0u, nullptr, nullptr};
+    if (!log_obs) {
+        drow_mod->launch("hy_dout_rows", n_max, 256, da, stream);
+        return;
+    }
+    // Event-log observables: hy_obs_rows samples the rows its section reads and stores the observables (event_observables.hpp).
+    if (!obs_mod) {
+        obs_mod = std::make_unique<aux_module>(log_obs->cm, device);
+    }
+    da.pars = d_pars.as<double>();
+    if (log_obs->sec.staged) {
+        // (The samples of the rows of this step, the row index fastest: n_reads * n_max doubles.)
+        const auto need = log_obs->sec.reads.size() * static_cast<std::size_t>(n_max) * sizeof(double);
+        if (d_obs_stage.bytes() < need) {
+            d_obs_stage = device_buffer(std::max(need, 2u * d_obs_stage.bytes()), device);
+        }
+        da.stage = d_obs_stage.as<double>();
+    }
+    obs_mod->launch("hy_obs_rows", n_max, 256, da, stream);
 }
 
 namespace
@@ -525,7 +542,7 @@ void tab_core::impl::ev_apply_on_device(ev_step &s)
         evr_mod->launch("hy_evr_count", N, 256, ra, stream);
         evr_mod->launch("hy_evr_scan", 256, 256, ra, stream);
         evr_mod->launch("hy_evr_write", N, 256, ra, stream);
-        if (log_states) {
+        if (log_fills()) {
             log_fill_states(log_rows, ra.total, s.log_ub);
         }
     }
@@ -757,7 +774,7 @@ void tab_core::impl::ev_log_host_rows(ev_step &s)
         std::copy_n(log_hdrs.data() + r * event_log_header, event_log_header, rows_h.data() + r * w);
     }
     device_copy(d_ev_log.as<double>() + log_rows * w, rows_h.data(), rows_h.size() * sizeof(double), device, stream);
-    if (log_states) {
+    if (log_fills()) {
         log_fill_states(log_rows, nullptr, n_new);
     }
     stream_synchronize(device, stream);
@@ -862,7 +879,9 @@ void tab_core::set_event_log_states(bool on)
     if (on == d.log_states) {
         return;
     }
-    if (d.log_rows != 0u) {
+    // (While observables are set the switch does not shape the rows: it is free to move, and the list can be cleared only on an
+    // empty log anyway.)
+    if (d.log_rows != 0u && !d.log_obs) {
         throw std::invalid_argument("The state columns of the event log can be switched only while the log is empty: it holds "
                                     + std::to_string(d.log_rows) + " row(s) - clear it first");
     }
@@ -882,11 +901,70 @@ bool tab_core::has_event_recorders() const
 const std::vector<char> &tab_core::event_log_code_object(int which) const
 {
     const auto &d = *m_impl;
+    if (which == 2 && d.ev_has_rec) {
+        if (!d.log_obs) {
+            throw std::invalid_argument("This integrator has no event-log observables: no observable kernel was compiled");
+        }
+        return d.log_obs->cm->code;
+    }
     const auto &m = which == 0 ? d.evr_cmod : d.drow_cmod;
     if (!m) {
         throw std::invalid_argument("This integrator has no recording event callbacks: no event-log kernels were compiled");
     }
     return m->code;
+}
+
+void tab_core::set_event_log_observables(std::optional<std::vector<expression>> obs)
+{
+    auto &d = *m_impl;
+    if (!d.ev_has_rec) {
+        throw std::invalid_argument("This integrator has no recording event callbacks: there is no event log to put observables into");
+    }
+    if (!obs && !d.log_obs) {
+        return;
+    }
+    if (d.log_rows != 0u) {
+        throw std::invalid_argument("The observables of the event log can be set or cleared only while the log is empty: it holds "
+                                    + std::to_string(d.log_rows) + " row(s) - clear it first");
+    }
+    if (!obs) {
+        d.log_obs.reset();
+        d.obs_mod.reset();
+        return;
+    }
+    // (The code object lives in the process-wide cache, keyed by the text: the observables and the options of the emitter.)
+    auto v = std::make_shared<impl::log_obs_data>();
+    v->sec = make_event_obs_section(*obs, state_variables_of(d.sys), d.prog.n_par);
+    v->source = make_event_log_obs_source(d.prog, d.log_emit_options(), v->sec);
+    const stopwatch sw;
+    v->cm = hiprtc_compile_source(v->source);
+    log_message(log_level::trace, "event-log observables: kernel compilation runtime: " + sw.str());
+    v->obs = std::move(*obs);
+    d.log_obs = std::move(v);
+    d.obs_mod.reset();
+}
+
+const std::vector<expression> *tab_core::get_event_log_observables() const
+{
+    return m_impl->log_obs ? &m_impl->log_obs->obs : nullptr;
+}
+
+std::string tab_core::event_log_source(int which) const
+{
+    const auto &d = *m_impl;
+    if (!d.ev_has_rec) {
+        throw std::invalid_argument("This integrator has no recording event callbacks: no event-log kernels were compiled");
+    }
+    if (which == 2) {
+        if (!d.log_obs) {
+            throw std::invalid_argument("This integrator has no event-log observables: no observable kernel was compiled");
+        }
+        return d.log_obs->source;
+    }
+    if (which != 1) {
+        throw std::invalid_argument("The event-log kernels with a source text of their own are 1 (hy_dout_rows) and 2 (hy_obs_rows)");
+    }
+    return make_event_log_dout_source(d.prog, d.log_emit_options());
 }
 
 std::uint32_t tab_core::get_n_event_actions() const

@@ -21,6 +21,7 @@
 #include <string>
 
 #include "dfloat.hpp"
+#include "event_observables.hpp"
 #include "hip_backend.hpp"
 #include "hip_emit.hpp"
 #include "grid_observables.hpp"
@@ -551,9 +552,34 @@ struct tab_core::impl {
     mutable device_buffer d_ev_log, d_evr_isrec, d_evr_lane, d_evr_blk;
     mutable std::uint64_t log_rows = 0, log_reserved = 0;
     mutable std::vector<double> log_stash;
+    // ---- event-log observables (event_observables.hpp) ----
+    // The list set on the integrator (null: none), its section, the text and the code object of hy_obs_rows: immutable,
+    // shared by the copies. The module is loaded on the integrator's device at the first step which fills rows; the staging
+    // buffer (staged mode only) holds the samples of the rows of one step and grows with the rows of a step.
+    struct log_obs_data {
+        std::vector<expression> obs;
+        event_obs_section sec;
+        std::string source;
+        std::shared_ptr<const compiled_module> cm;
+    };
+    std::shared_ptr<const log_obs_data> log_obs;
+    mutable std::unique_ptr<aux_module> obs_mod;
+    mutable device_buffer d_obs_stage;
+    // The options of the kernels over the rows of the log: those of the stepper, with the layout of ITS coefficients.
+    [[nodiscard]] emit_options log_emit_options() const
+    {
+        auto eo_log = eo;
+        eo_log.compact_tc = cluster_events && emitted.compact_tc;
+        return eo_log;
+    }
+    // Whether a kernel fills columns behind the header from the Taylor coefficients of the step.
+    [[nodiscard]] bool log_fills() const
+    {
+        return log_obs || log_states;
+    }
     [[nodiscard]] std::uint32_t log_row_doubles() const
     {
-        return event_log_header + (log_states ? dim : 0u);
+        return event_log_header + (log_obs ? log_obs->sec.n_obs : (log_states ? dim : 0u));
     }
     [[nodiscard]] std::uint64_t log_capacity() const
     {

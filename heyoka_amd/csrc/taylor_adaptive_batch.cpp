@@ -297,9 +297,8 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
     }
     if (d.ev_has_rec) {
         // Recording callbacks: the kernels of the event log, in modules of their own.
-        auto eo_log = eo;
-        eo_log.compact_tc = d.cluster_events && d.emitted.compact_tc;
-        d.drow_cmod = hiprtc_compile_source(make_event_log_dout_source(d.prog, eo_log));
+        d.eo = eo;
+        d.drow_cmod = hiprtc_compile_source(make_event_log_dout_source(d.prog, d.log_emit_options()));
         d.evr_cmod = hiprtc_compile_source(make_event_recorder_source(
             ed_max_detected(d.order, static_cast<std::uint32_t>(d.tes.size()), static_cast<std::uint32_t>(d.ntes.size()))));
     }
@@ -361,6 +360,7 @@ tab_core::tab_core(const tab_core &o) : m_impl(o.m_impl ? std::make_unique<impl>
     // (The copy starts with an empty event log.)
     d.ev_has_rec = s.ev_has_rec;
     d.log_states = s.log_states;
+    d.log_obs = s.log_obs;
     d.evr_cmod = s.evr_cmod;
     d.drow_cmod = s.drow_cmod;
     d.act_sections = s.act_sections;
@@ -899,6 +899,8 @@ void tab_core::set_device(int device)
     }
     d.evr_mod.reset();
     d.drow_mod.reset();
+    d.obs_mod.reset();
+    d.d_obs_stage = {};
     d.act.dm.reset();
     for (auto &[k, v] : d.sa_modules) {
         (void)k;

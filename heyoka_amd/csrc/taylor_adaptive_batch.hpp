@@ -356,6 +356,15 @@ public:
     [[nodiscard]] bool get_event_log_states() const;
     [[nodiscard]] bool has_event_recorders() const;
     [[nodiscard]] const std::vector<char> &event_log_code_object(int which) const;
+    // Event-log observables (event_observables.hpp): while a list is set a row is 8 + n_obs doubles, column
+    // 8 + k the value of observable k at the trigger (bit for bit cfunc of the state columns the same run logs without the
+    // list, the parameters of the system and time = column 4); the states switch keeps its value and has no effect. Set or
+    // cleared (nullopt) only while the log is empty; std::invalid_argument without recording callbacks, for an empty list, a
+    // variable which is not a state variable, a par[i] beyond the parameters. The kernel hy_obs_rows is compiled here:
+    // event_log_code_object(2); event_log_source(): the HIP text of 1 (hy_dout_rows) and 2 (hy_obs_rows).
+    void set_event_log_observables(std::optional<std::vector<expression>> obs);
+    [[nodiscard]] const std::vector<expression> *get_event_log_observables() const; // null: none set
+    [[nodiscard]] std::string event_log_source(int which) const;
     // Terminal-event actions (event_action.hpp): their number, the action module (kernel hy_ev_action;
     // std::invalid_argument without actions), and what the marker callback of
     // the C ABI does when it is called directly - the action (one of this integrator's) applied to one system.
@@ -924,6 +933,22 @@ public:
     [[nodiscard]] std::uint32_t get_event_log_row_size() const
     {
         return m_core.get_event_log_row_size();
+    }
+    // Event-log observables (MI355X extension): with a list of expressions over the state variables, par[...]
+    // and the time, a row of the log is 8 + n_obs doubles - the observables at the trigger in place of the state. Only
+    // while the log is empty; an empty optional clears the list.
+    void set_event_log_observables(std::vector<expression> obs)
+    {
+        m_core.set_event_log_observables(std::move(obs));
+    }
+    void clear_event_log_observables()
+    {
+        m_core.set_event_log_observables(std::nullopt);
+    }
+    [[nodiscard]] std::vector<expression> get_event_log_observables() const
+    {
+        const auto *p = m_core.get_event_log_observables();
+        return p != nullptr ? *p : std::vector<expression>{};
     }
     void clear_event_log()
     {

@@ -393,6 +393,25 @@ int hy_tab_get_event_log_states(hy_tab);
  * Code objects (gfx950) of the event-log kernels of an integrator with recording callbacks: which = 0 row headers
  * (hy_evr_count / hy_evr_scan / hy_evr_write), 1 dense output over the rows (hy_dout_rows). Owned by the integrator. */
 int hy_tab_event_log_code_object(hy_tab, int which, const char **data, size_t *size);
+/* Event-log OBSERVABLES (MI355X extension): n expressions over the state variables, par[...] and the time. While the list
+ * is set a row of the log is 8 + n doubles: the header above, then column 8 + k = observable k at the trigger - bit for bit
+ * what a compiled function of the same expressions returns for the state columns the same run logs without the list, the
+ * parameters of the row's system and time = column 4. The kernel hy_obs_rows (code object: which = 2 above) samples only the
+ * state rows the expressions read. The list can be set or cleared (obs == NULL, n == 0) only while the log is empty; the state-column
+ * switch keeps its value and has no effect while a list is set; copies of the integrator keep the list. Errors: no recording
+ * callbacks, a non-empty log, a variable which is not a state variable, a par[i] beyond the parameters of the integrator.
+ * HEYOKA_AMD_EVENT_OBS=registers|staged overrides how the kernel holds the samples (default: registers up to 64 rows read). */
+int hy_tab_set_event_log_observables(hy_tab, const hy_expr *obs, uint32_t n);
+uint32_t hy_tab_get_event_log_n_observables(hy_tab);
+/* Observable k as a new expression handle (caller frees); NULL and hy_last_error() when there is none. */
+hy_expr hy_tab_get_event_log_observable(hy_tab, uint32_t k);
+/* INTERNAL hooks of the test suite: the HIP source (caller frees; NULL and hy_last_error() on error) of the event-log kernel
+ * which = 1 (hy_dout_rows) or 2 (hy_obs_rows) of an integrator, and the source of hy_obs_rows for a system and a list of
+ * observables without an integrator and without a GPU - compact_tc / exact_division: the layout of the Taylor coefficients
+ * and the divisions of the stepper the rows come from (the wave-cluster steppers with events store compact coefficients). */
+char *hy_tab_event_log_source(hy_tab, int which);
+char *hy_event_observables_source(hy_sys, const hy_expr *obs, uint32_t n, uint32_t order, int high_accuracy, int compact_tc,
+                                  int exact_division);
 /* Terminal-event ACTIONS: a library-side terminal callback defined by n assignments vars[k] <- rhs[k] (in this order)
  * instead of code of the caller's - a bounce v <- -c v, an impulse v <- v + dv, a wrap of a coordinate. The left-hand
  * sides are distinct state variables of the system; the right-hand sides may read state variables, parameters, the time
