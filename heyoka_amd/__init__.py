@@ -1769,6 +1769,13 @@ class taylor_adaptive_batch:
         raise_for(lib.hy_tab_event_action_module(self._h, ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
         return take_str(src.value), ctypes.string_at(data.value, n.value)
 
+    def event_jets_module(self):
+        """(HIP source, gfx950 code object) of the companion module of a wave-cluster stepper with events: the kernels
+        hy_dout_c and hy_tc_expand, and hy_ev_jets when the stepper does not evaluate the event equations itself."""
+        src, data, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        raise_for(lib.hy_tab_event_jets_module(self._h, ctypes.byref(src), ctypes.byref(data), ctypes.byref(n)))
+        return take_str(src.value), ctypes.string_at(data.value, n.value)
+
     def reset_cooldowns(self, batch_idx=None):
         raise_for(lib.hy_tab_reset_cooldowns(self._h, -1 if batch_idx is None else int(batch_idx)))
 

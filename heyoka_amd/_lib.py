@@ -201,6 +201,7 @@ SIGNATURES = [
     ("hy_event_action_str", c_void_p, [c_void_p]),
     ("hy_event_action_t", c_int, [c_void_p, c_int, ctypes.c_uint32, c_void_p]),
     ("hy_tab_event_action_module", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("hy_tab_event_jets_module", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     ("hy_tab_n_event_actions", ctypes.c_uint32, [c_void_p]),
     ("hy_tab_event_action_kernel_ms", c_int, [c_void_p, c_void_p, c_void_p]),
     ("hy_event_detection_source", c_void_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),

@@ -1531,6 +1531,10 @@ int hy_tab_event_action_module(hy_tab t, char **source, const char **data, size_
 {
     return guarded([&] { module_out(t->core.event_action_module(), source, data, size); });
 }
+int hy_tab_event_jets_module(hy_tab t, char **source, const char **data, size_t *size)
+{
+    return guarded([&] { module_out(t->core.event_jets_module(), source, data, size); });
+}
 uint32_t hy_tab_n_event_actions(hy_tab t)
 {
     return t->core.get_n_event_actions();

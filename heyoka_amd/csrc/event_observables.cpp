@@ -54,9 +54,7 @@ std::string make_event_log_obs_source(const taylor_program &p, const emit_option
     const auto order = opts.order;
     const auto &reads = sec.reads;
     const auto reads_row = [&](std::uint32_t i) { return std::binary_search(reads.begin(), reads.end(), i); };
-    const auto derived = [&](std::uint32_t i) {
-        return opts.compact_tc && p.sv_defs[i].type == operand::kind::uvar && p.sv_defs[i].idx < n_eq;
-    };
+    const auto rows = emit_detail::make_compact_rows(p, opts);
     // Where the sample of state row i lives: a named scalar, or the slot of the row of the log in the staging buffer.
     const auto slot = [&](std::uint32_t i) {
         const auto pos = static_cast<std::size_t>(std::lower_bound(reads.begin(), reads.end(), i) - reads.begin());
@@ -72,7 +70,7 @@ std::string make_event_log_obs_source(const taylor_program &p, const emit_option
     // (A compact row is sampled from the coefficients of the row which defines it: that row must hold coefficients of its
     // own. hy_dout_rows skips such a chain silently; an observable which reads it is refused.)
     for (const auto i : reads) {
-        if (derived(i) && derived(p.sv_defs[i].idx)) {
+        if (rows.derived(i) && rows.derived(p.sv_defs[i].idx)) {
             throw std::invalid_argument("An observable of the event log reads the state variable " + std::to_string(i)
                                         + ", which the compact Taylor coefficients define through another derived variable ("
                                         + std::to_string(p.sv_defs[i].idx) + "): this chain cannot be sampled");
@@ -83,14 +81,7 @@ std::string make_event_log_obs_source(const taylor_program &p, const emit_option
     os << emit_detail::prelude() << emit_detail::rules_source(sec.prog);
     os << drow_kargs_text();
     if (opts.compact_tc) {
-        // (The table and the uncontracted product of hy_dout_rows.)
-        os << "__device__ __forceinline__ double hy_mul_nc(double x, double y)\n{\n    double t = x * y;\n"
-              "    asm(\"\" : \"+v\"(t));\n    return t;\n}\n";
-        os << "__constant__ double hy_rk_c[" << (order + 1u) << "] = {0.0";
-        for (std::uint32_t k = 1; k <= order; ++k) {
-            os << "," << fp_literal(opts.exact_division ? static_cast<double>(k) : 1. / static_cast<double>(k));
-        }
-        os << "};\n";
+        emit_detail::emit_compact_preamble(os, opts, nullptr);
     }
     // (hy_use(), see the section below. What it buys - the additions of the section contracted with the same products as in the
     // kernel of cfunc - is a property of the compiler, not of the language: the contract with cfunc is held by the GPU tests of
@@ -118,16 +109,17 @@ std::string make_event_log_obs_source(const taylor_program &p, const emit_option
     }
     os << "} else {\nconst double h = row[6];\n(void)h;\n";
     if (opts.compact_tc) {
-        const std::string xk = opts.exact_division ? "(ck / hy_rk_c[k + 1u])" : "hy_mul_nc(ck, hy_rk_c[k + 1u])";
         for (std::uint32_t j = 0; j < n_eq; ++j) {
-            if (derived(j)) {
+            if (rows.derived(j)) {
                 continue;
             }
             // The rows defined by row j which are read: they are sampled from the coefficients of j and their own order 0.
             std::vector<std::uint32_t> kids;
+            std::vector<std::string> sfx;
             for (const auto i : reads) {
-                if (derived(i) && p.sv_defs[i].idx == j) {
+                if (rows.parent[i] == static_cast<int>(j)) {
                     kids.push_back(i);
+                    sfx.push_back("_" + std::to_string(i));
                 }
             }
             const bool want_v = reads_row(j);
@@ -138,47 +130,7 @@ std::string make_event_log_obs_source(const taylor_program &p, const emit_option
             for (const auto i : kids) {
                 os << "const double x0_" << i << " = a.tc[((u64)" << i << "u * " << (order + 1u) << "u) * N + s];\n";
             }
-            if (opts.high_accuracy) {
-                os << "double ck = c[0];\ndouble cur_h = h;\n";
-                if (want_v) {
-                    os << "double rv = ck, cv = 0.0;\n";
-                }
-                for (const auto i : kids) {
-                    os << "double rx_" << i << " = x0_" << i << ", cx_" << i << " = 0.0;\n";
-                }
-                os << "for (unsigned k = 0; k < " << order << "u; ++k) {\n";
-                for (const auto i : kids) {
-                    os << "{\nconst double tmp = " << xk << " * cur_h;\nconst double y = tmp - cx_" << i << ";\nconst double t = rx_"
-                       << i << " + y;\n";
-                    os << "cx_" << i << " = (t - rx_" << i << ") - y;\nrx_" << i << " = t;\n}\n";
-                }
-                os << "ck = c[(u64)(k + 1u) * N];\n";
-                if (want_v) {
-                    os << "{\nconst double tmp = ck * cur_h;\nconst double y = tmp - cv;\nconst double t = rv + y;\n";
-                    os << "cv = (t - rv) - y;\nrv = t;\n}\n";
-                }
-                os << "cur_h = cur_h * h;\n}\n";
-            } else {
-                os << "double ck = c[(u64)" << order << "u * N];\n";
-                if (want_v) {
-                    os << "double rv = ck;\n";
-                }
-                for (const auto i : kids) {
-                    os << "double rx_" << i << " = 0.0;\n";
-                }
-                os << "for (unsigned k = " << order - 1u << "u;; --k) {\n";
-                os << "ck = c[(u64)k * N];\n";
-                if (want_v) {
-                    os << "rv = ck + rv * h;\n";
-                }
-                for (const auto i : kids) {
-                    os << "rx_" << i << " = (k == " << order - 1u << "u) ? " << xk << " : (" << xk << " + rx_" << i << " * h);\n";
-                }
-                os << "if (k == 0u) break;\n}\n";
-                for (const auto i : kids) {
-                    os << "rx_" << i << " = x0_" << i << " + rx_" << i << " * h;\n";
-                }
-            }
+            emit_detail::emit_compact_recurrence(os, opts, want_v, sfx);
             if (want_v) {
                 os << set(j, "rv");
             }
@@ -190,16 +142,7 @@ std::string make_event_log_obs_source(const taylor_program &p, const emit_option
     } else {
         for (const auto i : reads) {
             os << "{\nconst double *c = " << coeffs(i) << ";\n";
-            if (opts.high_accuracy) {
-                os << "double res = c[0], comp = 0.0, cur_h = h;\n";
-                os << "for (unsigned k = 1; k <= " << order << "u; ++k) {\n";
-                os << "const double tmp = c[(u64)k * N] * cur_h;\nconst double y = tmp - comp;\nconst double t = res + y;\n";
-                os << "comp = (t - res) - y;\nres = t;\ncur_h = cur_h * h;\n}\n";
-            } else {
-                os << "double res = c[(u64)" << order << "u * N];\n";
-                os << "for (unsigned k = 1; k <= " << order << "u; ++k) {\n";
-                os << "res = c[(u64)(" << order << "u - k) * N] + res * h;\n}\n";
-            }
+            emit_detail::emit_plain_recurrence(os, opts);
             os << set(i, "res") << "}\n";
         }
     }

@@ -93,8 +93,9 @@ struct emit_options {
     // Block mode: linear nodes fed by one cluster stay glue nodes (plan_limits::absorb_linear off) - the internal program whose
     // scalings were moved out of the clusters for the v2 cluster phase (externalise_scalings()).
     bool block_no_absorb = false;
-    // emit_event_jets(): the stepper it accompanies leaves out the Taylor coefficients of order >= 1 of the state variables
-    // defined by another state variable (emitted_module::compact_tc): read them as parent^[k-1] / k.
+    // emit_event_jets() and the kernels of dense_output_text.hpp: the stepper they accompany leaves out the Taylor coefficients
+    // of order >= 1 of the state variables defined by another state variable (emitted_module::compact_tc): read them as
+    // parent^[k-1] / k.
     bool compact_tc = false;
     // Stepper with events on the one-lane-per-pair kernel: the decomposition of the system WITH the event equations
     // (prog.ev_u). When set, the stepper evaluates the event equations itself from
@@ -106,9 +107,6 @@ struct emit_options {
     // ever truncated, so nothing behind the stepper reads the Taylor coefficients of the state variables: they are stored
     // on request only (hy_kargs::pad bit 0; a later get_tc() regenerates them from the snapshot of the step).
     std::uint32_t n_t_events = 0;
-    // emit_event_jets(): only the kernels which serve the compact Taylor coefficients (hy_dout_c, hy_tc_expand) - the
-    // stepper evaluates the event equations itself (emitted_module::events_in_stepper).
-    bool ev_helpers_only = false;
     // callback::angle_reducer fused into the propagate kernel: sorted indices of the state variables which
     // are reduced to [0, 2 pi) right after every state update. Empty: no reduction, and not a byte of the source differs. Only
     // the straight-line, the table (both tape placements) and the first-generation / multi-class wave-cluster generators
@@ -145,8 +143,9 @@ struct emitted_module {
     // The stepper implements mode 4 in its cluster form (see hy_kargs::sel_norms).
     bool cluster_mode4 = false;
     // Mode 4 writes a COMPACT set of Taylor coefficients: for a state variable x defined by another state variable
-    // (x' = v) only the order-0 row; x^[k] = v^[k-1] / k is left to the consumers (hy_ev_jets, hy_dout_c, hy_tc_expand in
-    // the module of emit_event_jets()): half of the 6 KB per system of an N-body ensemble never travel.
+    // (x' = v) only the order-0 row; x^[k] = v^[k-1] / k is left to the consumers (hy_dout_c and hy_tc_expand in the module
+    // of emit_compact_tc_module(), with hy_ev_jets in the one of emit_event_jets()): half of the 6 KB per system of an N-body
+    // ensemble never travel.
     bool compact_tc = false;
     // Mode 4 also evaluates the event equations, takes the final step size and updates the state (emit_options::ev_prog).
     bool events_in_stepper = false;
@@ -204,14 +203,21 @@ emitted_module emit_hip_module(const taylor_program &prog, const emit_options &o
 // of the event equations from the jets of the state variables in a.tc (only the part of the decomposition the event
 // equations depend on), the norms of the step-size selector extended to the event equations and the final step size.
 // prog is the decomposition of the system *with* the event equations (prog.ev_u). Returns a module with an empty source
-// (and the reason in why_not) when the event equations need too much of the decomposition.
+// (and the reason in why_not) when the event equations need too much of the decomposition. With emit_options::compact_tc
+// the kernels of emit_compact_tc_module() come first in the module. (hip_emit_events.cpp)
 emitted_module emit_event_jets(const taylor_program &prog, const emit_options &opts, std::string &why_not);
+
+// The companion module of a stepper which stores compact Taylor coefficients (emit_options::compact_tc) and evaluates the
+// event equations itself (emitted_module::events_in_stepper): only the kernels which serve the compact coefficients -
+// hy_dout_c, the dense output (state update of a step with events), and hy_tc_expand, which fills in the rows the stepper
+// left out for whoever reads the full array afterwards. (dense_output_text.cpp)
+emitted_module emit_compact_tc_module(const taylor_program &prog, const emit_options &opts);
 
 // Dense output over the ROWS of the event log (event_detection.hpp): hy_dout_rows evaluates the Taylor coefficients of
 // the row's system at the row's root and fills the state columns of the row, with the operations and the operation
 // order of hy_dout (full coefficients) or - emit_options::compact_tc - of hy_dout_c (the rows of the variables defined
 // by another state variable are derived: x^[k] = v^[k-1] / k); rows of terminal events copy the state after the step.
-// A module of its own, compiled only for integrators with recording callbacks.
+// A module of its own, compiled only for integrators with recording callbacks. (dense_output_text.cpp)
 std::string make_event_log_dout_source(const taylor_program &prog, const emit_options &opts);
 
 // The same computation as straight-line statements for use INSIDE a stepper (the one-lane-per-pair kernel in mode 4): sv(i, k)
@@ -239,7 +245,7 @@ struct ev_lane_hooks {
 };
 
 // skip_events (optional, one flag per event equation): event equations which the caller evaluates by other means - their
-// entry of ev_coeffs stays empty and the nodes only they depend on are not generated.
+// entry of ev_coeffs stays empty and the nodes only they depend on are not generated. (hip_emit_events.cpp)
 bool emit_event_jets_inline(const taylor_program &prog, const emit_options &opts,
                             const std::function<std::string(std::uint32_t, std::uint32_t)> &sv,
                             const std::function<std::string(std::uint32_t, std::uint32_t, const std::string &)> &ev_store,
@@ -250,6 +256,7 @@ bool emit_event_jets_inline(const taylor_program &prog, const emit_options &opts
 //     +-((a_0 - b_0)^2 + (a_1 - b_1)^2 + (a_2 - b_2)^2) + c,        a_i, b_i state variables,
 // written with products, pow(., 2) or sum_sq and sums / differences in any nesting? The close-encounter events of an
 // N-body problem have this form - and the pair kernels hold the Taylor coefficients of exactly these squared distances.
+// (hip_emit_events.cpp)
 struct pair_distance_event {
     std::array<std::pair<std::uint32_t, std::uint32_t>, 3> diffs; // (a_i, b_i), state variable indices
     double c = 0;

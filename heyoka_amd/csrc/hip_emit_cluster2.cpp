@@ -1127,9 +1127,7 @@ void cluster2_gen::tables_of_the_jet_placement()
             return false;
         }
         // (Chains x' = v, v' = a only: the parent of a derived variable is not derived itself.)
-        const auto derived = [&](std::uint32_t var) {
-            return p.sv_defs[var].type == operand::kind::uvar && p.sv_defs[var].idx < n_eq;
-        };
+        const auto derived = [&](std::uint32_t var) { return emit_detail::defined_by_state_variable(p, var); };
         bool any = false;
         for (std::uint32_t var = 0; var < n_eq; ++var) {
             if (derived(var)) {
@@ -1166,8 +1164,7 @@ void cluster2_gen::tables_of_the_jet_placement()
         for_each_owner([&](auto &, auto &ow) { n_tc_rows += static_cast<std::size_t>(ow.n_valid) * (ow.derived ? 1u : order + 1u); });
     } else if (m4) {
         for (std::uint32_t var = 0; var < n_eq; ++var) {
-            const auto &sd = p.sv_defs[var];
-            n_tc_rows += (compact_tc && sd.type == operand::kind::uvar && sd.idx < n_eq) ? 1u : order + 1u;
+            n_tc_rows += (compact_tc && emit_detail::defined_by_state_variable(p, var)) ? 1u : order + 1u;
         }
     }
 }
@@ -1634,8 +1631,7 @@ __device__ __forceinline__ double hy_swap1(double x)
                 });
             } else {
                 for (std::uint32_t var = 0; var < n_eq; ++var) {
-                    const auto &sd = p.sv_defs[var];
-                    const bool derived = compact_tc && sd.type == operand::kind::uvar && sd.idx < n_eq;
+                    const bool derived = compact_tc && emit_detail::defined_by_state_variable(p, var);
                     for (std::uint32_t k = 0; k <= (derived ? 0u : order); ++k) {
                         tc_src.push_back({static_cast<std::uint64_t>(var) * (order + 1u) + k,
                                           static_cast<std::uint64_t>(k) * spw * n_colp + col_of[var], n_colp});

@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "dense_output_text.hpp" // emit_dout(), the dense-output kernel of every stepper module
 #include "hip_emit.hpp"
 #include "node_rule.hpp"
 
@@ -85,9 +86,6 @@ inline constexpr const char *wsync_macro
 
 // Scaling + safety factor of the step-size selector, folded on the host in double precision.
 double rhofac(std::uint32_t order);
-
-// Dense-output kernel.
-void emit_dout(std::ostringstream &os, const taylor_program &p, const emit_options &opts);
 
 // The straight-line stepper (hip_emit.cpp): one system per lane, fully unrolled. Always applicable.
 emitted_module emit_unrolled(const taylor_program &p, const emit_options &opts);

@@ -102,7 +102,7 @@ HY_KARGS(hy_kargs, hy_kargs,
 namespace detail
 {
 
-// hy_dout, the dense-output kernel of every stepper module (emit_dout()). The kernel takes the fields one by one: its
+// hy_dout, the dense-output kernel of every stepper module (emit_dout(), dense_output_text.cpp). The kernel takes the fields one by one: its
 // parameter list is dout_kargs_parameters().
 HY_KARGS(dout_kargs, hy_dout_args,
     double *out;              // [n_eq * N]
@@ -172,7 +172,7 @@ HY_KARGS(ev_stop_kargs, hy_ev_stop_args,
     unsigned n_te, pad;
 )
 
-// hy_dout_c, hy_tc_expand (emit_event_jets()). hfull != nullptr: only the lanes whose step was truncated - hs[s] !=
+// hy_dout_c, hy_tc_expand (emit_compact_tc_module(), dense_output_text.cpp). hfull != nullptr: only the lanes whose step was truncated - hs[s] !=
 // hfull[s] - are updated: the stepper which evaluates the event equations itself has already taken the full step
 // everywhere.
 HY_KARGS(doutc_kargs, hy_doutc_args,
@@ -183,7 +183,7 @@ HY_KARGS(doutc_kargs, hy_doutc_args,
     const double *hfull;
 )
 
-// hy_dout_rows (make_event_log_dout_source()). n_rows != nullptr: the number of rows of the step is read from the device
+// hy_dout_rows (make_event_log_dout_source(), dense_output_text.cpp). n_rows != nullptr: the number of rows of the step is read from the device
 // (written by hy_evr_scan), n_max bounds it.
 // hy_obs_rows (make_event_log_obs_source(), event-log observables) takes the same block and reads its last two fields: the
 // parameters [n_par * N] and, staged mode only, the samples of the rows of the step [n_reads * n_max]; null for hy_dout_rows.

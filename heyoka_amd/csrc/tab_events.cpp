@@ -985,6 +985,15 @@ tab_core::module_view tab_core::event_action_module() const
     return {m_impl->act.source, m_impl->act.cm->code};
 }
 
+tab_core::module_view tab_core::event_jets_module() const
+{
+    if (!m_impl->ev_cmod) {
+        throw std::invalid_argument("This integrator has no companion module of a wave-cluster stepper with events: no such "
+                                    "kernel was compiled");
+    }
+    return {m_impl->ev_emitted.source, m_impl->ev_cmod->code};
+}
+
 void tab_core::apply_event_action(const event_action &act, std::uint32_t batch_idx)
 {
     auto &d = *m_impl;

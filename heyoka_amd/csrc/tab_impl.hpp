@@ -351,8 +351,10 @@ struct tab_core::impl {
     std::uint64_t ed_slots = 0;
     std::uint64_t ed_failures = 0;
     // Events on the wave-cluster steppers: the main stepper is built from the system alone and runs in mode 4 (jets of
-    // the state variables, no update); hy_ev_jets (emit_event_jets()) derives the jets of the event equations and the
-    // final step size from them.
+    // the state variables, no update); hy_ev_jets (emit_event_jets(), hip_emit_events.cpp) derives the jets of the event
+    // equations and the final step size from them. The companion module ev_emitted / ev_cmod holds it and, on compact
+    // coefficients, hy_dout_c and hy_tc_expand - those two alone (emit_compact_tc_module(), dense_output_text.cpp) when the
+    // stepper evaluates the event equations itself. tab_core::event_jets_module() shows the module.
     bool cluster_events = false;
     emitted_module ev_emitted;
     std::shared_ptr<const compiled_module> ev_cmod;

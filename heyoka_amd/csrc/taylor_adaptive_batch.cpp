@@ -227,8 +227,8 @@ tab_core::tab_core(sys_t sys, std::vector<double> state, std::uint32_t batch_siz
                 auto eo_ev = eo;
                 eo_ev.compact_tc = m.compact_tc;
                 // (Event equations inside the stepper: the companion module only serves the compact Taylor coefficients.)
-                eo_ev.ev_helpers_only = m.events_in_stepper && m.compact_tc;
-                auto evm = emit_event_jets(d.prog, eo_ev, why);
+                auto evm = (m.events_in_stepper && m.compact_tc) ? emit_compact_tc_module(d.prog, eo_ev)
+                                                                 : emit_event_jets(d.prog, eo_ev, why);
                 if (!evm.source.empty()) {
                     d.cluster_events = true;
                     d.emitted = std::move(m);

@@ -373,6 +373,9 @@ public:
     // in ms, number of timed launches) since the construction.
     [[nodiscard]] std::pair<double, std::uint64_t> get_event_action_kernel_ms() const;
     [[nodiscard]] module_view event_action_module() const;
+    // The companion module of a wave-cluster stepper with events (hy_dout_c and hy_tc_expand; hy_ev_jets when the stepper does
+    // not evaluate the event equations itself); std::invalid_argument for an integrator without one.
+    [[nodiscard]] module_view event_jets_module() const;
     void apply_event_action(const event_action &act, std::uint32_t batch_idx);
     // ---- variational integrators (reference: taylor.hpp is_variational() ... eval_taylor_map(); taylor_map.hpp) ----
     [[nodiscard]] bool is_variational() const noexcept;

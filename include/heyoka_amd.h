@@ -439,6 +439,9 @@ int hy_event_action_t(hy_tab, int d_sgn, uint32_t batch_idx, void *user);
 /* Introspection hook (test suite): HIP source (hy_free_str()) and gfx950 code object (owned by the integrator) of the
  * action module of an integrator with actions; error without one. Either output may be NULL. */
 int hy_tab_event_action_module(hy_tab, char **source, const char **data, size_t *size);
+/* The same for the companion module of a wave-cluster stepper with events (kernels hy_dout_c and hy_tc_expand; hy_ev_jets
+ * when the stepper does not evaluate the event equations itself); error for an integrator without one. */
+int hy_tab_event_jets_module(hy_tab, char **source, const char **data, size_t *size);
 uint32_t hy_tab_n_event_actions(hy_tab);
 /* While hy_tab_set_event_timing() is on, every launch of hy_ev_action runs between two HIP events: the sum of the kernel
  * durations (ms) and the number of timed launches since the construction. */

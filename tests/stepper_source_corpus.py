@@ -22,7 +22,8 @@ systems which keep it on its generic cluster phase, the outer Solar System under
 of emit_hip_module() (block mode with and without the v2 cluster phase, linearised accelerations, multi-class plans; as
 select:<case> the cases of tests/test_stepper_selection.py which take its other rungs, with their own switches), the
 first wave-cluster generator with one class of clusters (cluster_kernel="v1"), and the straight-line, HBM-tape and staged
-steppers with events (HY_N_EV > 0, mode 4), without compensated summation and with a fused angle reduction."""
+steppers with events (HY_N_EV > 0, mode 4), without compensated summation and with a fused angle reduction; as aux:<module>
+the auxiliary modules which evaluate dense output from the coefficient buffer (aux_corpus())."""
 import hashlib
 import json
 import os
@@ -39,6 +40,7 @@ for p_ in (os.path.join(HERE, "emu"), os.path.join(os.path.dirname(HERE), "oracl
 import heyoka_amd as hy  # noqa: E402
 from heyoka_amd import configs  # noqa: E402
 import test_batch_independence as tbi  # noqa: E402
+import test_event_observables as teo  # noqa: E402
 import test_stepper_selection as tss  # noqa: E402
 
 M, G = configs.OUTER_SS_MASSES, configs.OUTER_SS_G
@@ -107,6 +109,57 @@ def corpus():
     for name in ("unit_scalings_padded_4", "unit_scalings_padded_6", "padded_par_masses", "private_inputs_cluster", "private_inputs_block",
                  "no_state_aliases", "no_multi_class", "no_linearised_sums"):
         out.append(("select:" + name, lambda name=name: tss.build(name), None))
+    out += aux_corpus()
+    return out
+
+
+def aux_module(ta, pair):
+    """A (source, code object) pair of an auxiliary module of ta, as an object with the three attributes main() reads."""
+    return types.SimpleNamespace(hip_source=pair[0], code_object=pair[1], hip_source_mode=ta.hip_source_mode)
+
+
+def aux_corpus():
+    """The modules which evaluate dense output from the coefficient buffer next to the steppers: the companion module of the
+    wave-cluster stepper with events (hy_dout_c and hy_tc_expand; with hy_ev_jets when the event equations are kept out of
+    the stepper), hy_dout_rows and hy_obs_rows of the event log - on compact coefficients (outer Solar System) and on full
+    ones (the pendulum of tests/test_event_observables.py), in both arithmetics and with exact divisions."""
+    def log_module(make, which, obs=None):
+        def build():
+            ta = make()
+            if obs is not None:
+                ta.event_log_observables = obs()
+            return aux_module(ta, (ta.event_log_source(which), ta.event_log_code_object(which)))
+        return build
+
+    def event_jets(ta):
+        return aux_module(ta, ta.event_jets_module())
+
+    def outer_rec(high_accuracy=True, **kw):
+        # (The outer Solar System with recording callbacks of tests/test_event_observables.py.)
+        return teo._outer_ss(high_accuracy, **kw)[0]
+
+    def outer_obs():
+        # Positions (rows derived from the velocities on compact coefficients), and a velocity on its own (a defining row).
+        vx, vy = hy.make_vars("vx_2", "vy_2")
+        return [teo._pair_distance2(), vx * vx + vy * vy]
+
+    out = []
+    variants = (("default", {}), ("exact_division", {"exact_division": True}), ("high_accuracy=False", {"high_accuracy": False}))
+    for tag, env in (("in_stepper", None), ("no_events_in_stepper", {"HEYOKA_AMD_NO_EVENTS_IN_STEPPER": "1"})):
+        for vtag, kw in variants:
+            name = "%s:%s" % (tag, vtag)
+            rec = lambda kw=kw: outer_rec(**kw)
+            out.append(("aux:event_jets:" + name, lambda kw=kw: event_jets(outer_ev(**kw)), env))
+            out.append(("aux:event_log1:" + name, log_module(rec, 1), env))
+            if env is None:
+                for mode in ("registers", "staged"):
+                    out.append(("aux:event_log2:%s:%s" % (mode, vtag), log_module(rec, 2, outer_obs), {"HEYOKA_AMD_EVENT_OBS": mode}))
+    for ha in (False, True):
+        pend = lambda ha=ha: teo._cpu_ta(high_accuracy=ha)[0]
+        out.append(("aux:event_log1:pendulum:high_accuracy=%s" % ha, log_module(pend, 1), None))
+        for mode in ("registers", "staged"):
+            out.append(("aux:event_log2:pendulum:%s:high_accuracy=%s" % (mode, ha),
+                        log_module(pend, 2, lambda: teo._pendulum_obs(*hy.make_vars("x", "v"))), {"HEYOKA_AMD_EVENT_OBS": mode}))
     return out
 
 
